@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- feature-raster fwd+bwd views/s (BASELINE.json metric) on N GPUs of one node.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,9 +12,13 @@ random cotangent G -> loss.backward() -> (N>1) sum of d loss/d _semantic_feature
 region.  Workload at N=1 = BASELINE.json configs[2] "C3": 1.5 M Gaussians, 1920x1080, D=512 --
 the configuration the metric is quoted on; it fits one MI355X.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline` (dominant
-kernel, measured with HIP events inside the timed region) and `cpu_baseline` (the CPU oracle
-timed on a bounded tile sample of the same workload, rank 0, N=1 only).
+Prints ONE JSON line (rank 0) with the driver's contract keys.  A plain run does only what that
+line's headline needs: set-up, warm-up, the timed steps, the line.  `--full` adds everything
+else the benchmark measures, after the timed steps: `roofline` / `kernels` / `stages_ms` (a
+second pass of the same steps with every kernel bracketed by HIP events), `cpu_baseline` (the
+CPU oracle timed on a bounded tile sample of the same workload, rank 0, N=1 only), the other
+precisions, workloads and collectives.  `--dump-outputs DIR` writes what the last timed step
+handed its caller as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -84,7 +88,48 @@ def parse():
                     help="N>1: one view per GPU + gradient exchange (view: north_star's decomposition, the default), "
                          "every GPU renders all N views for its channel shard with no exchange (channel), or whichever "
                          "two probe steps show faster (auto)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: per-kernel roofline, CPU baseline, optimizer step, "
+                         "the other precisions, workloads and collectives (the --no-* options above trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, render, alphas, radii, feature gradient) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_CAP = 1 << 21  # elements per dumped array (twice that for feature_grad): at most ~59 MB in all
+
+
+def _row_sample(x, cap):
+    """x [R, C]: whole when it holds at most `cap` elements, else the same seeded sample of its rows on every run."""
+    keep = max(1, cap // max(x.shape[1], 1))
+    if x.shape[0] <= keep:
+        return x
+    idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    return x.index_select(0, idx.to(x.device))
+
+
+def dump_outputs(out_dir, pkg, grad):
+    """What the timed step handed its caller in its last step, as DIR/<name>.npy (float32; the row sums float64):
+    loss (<render, G>), render [pixels, D], alphas [pixels, 1], radii [N, 1], feature_grad [N, D], feature_grad_row_sums
+    [N, 1].  An array above its cap is a fixed seeded sample of its rows (the same rows for the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    render = pkg["render"].detach()
+    grad = grad.detach()
+    row_sums = torch.cat([c.double().sum(1) for c in grad.split(1 << 16)])  # (chunked: no float64 copy of the whole table)
+    arrays = {
+        "loss": pkg["loss"].reshape(1),
+        "render": _row_sample(render.permute(1, 2, 0).reshape(-1, render.shape[0]), DUMP_CAP),  # [D,H,W] view of [H,W,D]
+        "alphas": _row_sample(pkg["alphas"].detach().reshape(-1, 1), DUMP_CAP),
+        "radii": _row_sample(pkg["radii"].reshape(-1, 1), DUMP_CAP).float(),
+        "feature_grad": _row_sample(grad, 2 * DUMP_CAP).float(),
+        "feature_grad_row_sums": _row_sample(row_sums.reshape(-1, 1), DUMP_CAP),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_baseline(pc, cam, d, width, height, target_s):
@@ -371,6 +416,7 @@ def main():
                     reduce_feature_grad(pc_._semantic_feature.grad, mode=ex["mode"])
             if exchange:  # trainable geometry (not the GAD stage): its gradients travel as one packed [N,11] block
                 reduce_geometry_grads(pc_, mode=ex["mode"])
+            pkg_["loss"] = loss.detach()
             return pkg_
         step_.set_collective = set_collective
         return step_, pc_, cams[-1], dl
@@ -436,41 +482,56 @@ def main():
             step, pc, cam, d_local = build(mode)
 
     for _ in range(args.warmup):
-        pkg = step()
+        step()
     torch.cuda.synchronize()
-    info = pkg["info"]
-    n_isects = info["n_isects"]
-    n_visible = int((pkg["radii"] > 0).sum().item())
 
-    # workload statistics for the roofline model (outside the timed region)
-    counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    _lib.check(_lib.load().gags_raster_stats(width, height, _lib.ptr(info["means2d"][0]), _lib.ptr(info["conics"][0]),
-                                             _lib.ptr(info["opacities"][0].contiguous()),
-                                             _lib.ptr(info["isect_offsets"]), _lib.ptr(info["flatten_ids"]),
-                                             n_isects, _lib.ptr(counts), None), "gags_raster_stats")
-    torch.cuda.synchronize()
-    q_eval, q_blend = (int(v) for v in counts.tolist())
-    del pkg, info
-
-    profiler.enable(True)
     barrier()
     torch.cuda.synchronize()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
-    for i in range(args.steps):
-        marks[i].record()
-        step()
-    marks[args.steps].record()
+    for _ in range(args.steps):
+        last = None  # (the previous step's outputs are freed before the next step allocates, as when none are kept)
+        last = step()
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
-    stages = profiler.summary()
-    profiler.enable(False)
-    per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    exposed_ms = exposed[-1].exposed_ms() if exposed else None
+    range_ms = exposed[-1].range_ms if exposed else None
+    if rank == 0 and args.dump_outputs:  # before any later step overwrites the gradient's persistent buffer
+        dump_outputs(args.dump_outputs, last, pc._semantic_feature.grad)
+    info = last["info"]
+    n_isects = info["n_isects"]
+    n_visible = int((last["radii"] > 0).sum().item())
+
+    if args.full:
+        # workload statistics for the roofline model (outside the timed region)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        _lib.check(_lib.load().gags_raster_stats(width, height, _lib.ptr(info["means2d"][0]), _lib.ptr(info["conics"][0]),
+                                                 _lib.ptr(info["opacities"][0].contiguous()),
+                                                 _lib.ptr(info["isect_offsets"]), _lib.ptr(info["flatten_ids"]),
+                                                 n_isects, _lib.ptr(counts), None), "gags_raster_stats")
+        torch.cuda.synchronize()
+        q_eval, q_blend = (int(v) for v in counts.tolist())
+    del last, info
+
+    if args.full:
+        # per-kernel times: the timed steps once more, every kernel (group) bracketed by HIP events on its launch stream
+        profiler.enable(True)
+        barrier()
+        torch.cuda.synchronize()
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        for i in range(args.steps):
+            marks[i].record()
+            step()
+        marks[args.steps].record()
+        torch.cuda.synchronize()
+        barrier()
+        stages = profiler.summary()
+        profiler.enable(False)
+        per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
 
     # R9 (outside the metric, which is fwd+bwd): the optimizer step on the gradient the last step left
     adam = None
-    if rank == 0 and pc._semantic_feature.grad is not None:
+    if args.full and rank == 0 and pc._semantic_feature.grad is not None:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         pc.optimizer.step()
         for i in range(5):
@@ -483,12 +544,10 @@ def main():
         adam = {"kernel": "adam_step_kernel", "avg_launch_ms": ms, "bound": "hbm", "achieved": nbytes / ms / 1e6,
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / ms / 1e6 / HBM_PEAK_GBS}
 
-    exposed_ms = exposed[-1].exposed_ms() if exposed else None
-    range_ms = exposed[-1].range_ms if exposed else None
     # "verify RCCL picks the direct/mesh algorithm": the same step with the OTHER collective, a few steps, so
     # that one N-GPU run yields the rs_ag / allreduce comparison (MAX over ranks; outside `value`)
     collective_ms = None
-    if world > 1 and mode == "view" and not args.no_allreduce:
+    if args.full and world > 1 and mode == "view" and not args.no_allreduce:
         collective_ms = {args.grad_reduce: 1e3 * dt / args.steps}
         other = "allreduce" if args.grad_reduce == "rs_ag" else "rs_ag"
         # (under the gloo debug transport rs_ag on device tensors is slow or refused: recorded as measured / null, same code path)
@@ -518,78 +577,8 @@ def main():
     value = world * args.steps / dt  # every rank renders one view per step (weak scaling)
 
     if rank == 0:
-        # Per-kernel roofline.  Each entry is ONE kernel bracketed by HIP events on the
-        # launch stream; algorithmic work per launch:
-        #   raster_fwd  : 14*Q_eval + 2*D*Q_blend flops              (weights + feature passes; fp32 MFMA bound)
-        #   bwd_rows    : 2*D*Q_blend flops                           (weight tile, MFMA, row stores)
-        #   bwd_reduce  : 2*B*D*4 bytes, B = Gaussians that blended anything: each one's gradient row formed from at least one
-        #                 partial row and written once (HBM bound; the kernel actually reads one row per touched (tile,
-        #                 Gaussian) -- 4.7 per blended Gaussian at C3 -- and, since round 6's persistent gradient buffer, no
-        #                 longer writes the zero rows of the other N - B Gaussians)
-        #   raster_bwd  : 14*Q_eval + 2*D*Q_blend flops              (single-kernel atomic backward, if used)
-        rows = profiler.notes().get("bwd_rows", 0)
-        g_last = pc._semantic_feature.grad
-        n_blended = int((g_last != 0).any(dim=1).sum().item()) if g_last is not None else 0  # rows of the gradient that are not zero
-        blk = profiler.notes().get("fwd_blk_rows")
-        slots = int(blk.sum().item()) if blk is not None else 0  # (block, Gaussian) pairs that blended: one weight row each
         dl = d_local  # feature width of one launch on this rank (D, or the rank's channel shard)
         pix = width * height
-        #   raster_weights : HBM bytes = 40 I (ids, records, hit flags) + 264 slots (weight row, ids) + 12 P (alpha, last id, T)
-        #                    (reported against HBM; the kernel is VALU-bound -- 14 flops per evaluated pair -- and says so)
-        #   raster_fwd_feat: 2*D*Q_blend flops  (priced against the fp32 matrix peak: the arithmetic it replaces; issued as six
-        #                    v_mfma_f32_32x32x16_bf16 terms per product on operands split into three bf16 terms)
-        work = {
-            "raster_weights": ("hbm", 40.0 * n_isects + 264.0 * slots + 12.0 * pix),
-            "raster_fwd_feat": ("mfma", 2.0 * dl * q_blend),
-            "bwd_rows": ("mfma", 2.0 * dl * q_blend),
-            "bwd_reduce": ("hbm", 8.0 * dl * n_blended),
-            "raster_bwd": ("mfma", 14.0 * q_eval + 2.0 * dl * q_blend),
-        }
-        kernels = {}
-        for name, (bound, amount) in work.items():
-            if name in stages and stages[name][0] > 0:
-                ms = stages[name][0]
-                if bound == "mfma":
-                    ach, peak, unit = amount / (ms * 1e-3) / 1e12, FP32_MATRIX_PEAK_TFLOPS, "TFLOP/s"
-                else:
-                    ach, peak, unit = amount / (ms * 1e-3) / 1e9, HBM_PEAK_GBS, "GB/s"
-                kernels[name] = {"bound": bound, "avg_launch_ms": ms, "achieved": ach, "peak": peak, "unit": unit,
-                                 "frac": ach / peak}
-        # HBM traffic per launch from the committed rocprofv3 PMC passes of this very command
-        # (tools/pmc_passes.sh -> profiles/*_pmc_traffic.json: 2*FETCH_SIZE + WRITE_SIZE, separate passes)
-        traffic, traffic_src = pmc_traffic(args) if world == 1 else ({}, None)
-        for name, members in STAGE_KERNELS.items():
-            if name in kernels:
-                tb = [_traffic_of(traffic, m) for m in members]
-                kernels[name]["traffic"] = sum(tb) if all(t is not None for t in tb) else None
-                # matrix work the kernel ISSUES per launch (SQ_INSTS_MFMA x flops per instruction, same PMC passes) next
-                # to the algorithmic flops: the ratio is the padding (zero halves, ragged 32-row tiles, split terms)
-                mi = _traffic_of(traffic, members[0], "mfma_insts")
-                if name in MFMA_FLOP and mi:
-                    ms = kernels[name]["avg_launch_ms"]
-                    issued = mi * MFMA_FLOP[name]
-                    pipe_peak = (FP32_MATRIX_PEAK_TFLOPS if (name == "bwd_rows" and (args.raster_flags & _lib.GAGS_BWD_F32MFMA))
-                                 or (name == "raster_fwd_feat" and (args.raster_flags & _lib.GAGS_FWD_EXACT)) else F16_MATRIX_PEAK_TFLOPS)
-                    kernels[name]["issued_flops"] = issued
-                    kernels[name]["mfma_issue_frac"] = issued / (ms * 1e-3) / 1e12 / pipe_peak
-                    kernels[name]["mfma_busy_cycles"] = _traffic_of(traffic, members[0], "mfma_busy_cycles")
-                    kernels[name]["busy_cu_cycles"] = _traffic_of(traffic, members[0], "busy_cu_cycles")
-        if "raster_weights" in kernels:
-            kernels["raster_weights"]["note"] = ("VALU-bound (14 flops per evaluated pair: 14*Q_eval = %.1f GFLOP per launch); priced "
-                                                 "against HBM by the bytes it has to move" % (14.0 * q_eval / 1e9))
-        if "raster_fwd_feat" in kernels and not (args.raster_flags & _lib.GAGS_FWD_EXACT):
-            kernels["raster_fwd_feat"]["note"] = ("algorithmic fp32 flops (2 D Q_blend) against the fp32 matrix peak; issued as 6 "
-                                                  "v_mfma_f32_32x32x16_bf16 terms per product, both operands split into three bf16 terms "
-                                                  "in registers (exact operands; fp32-equivalent, DESIGN.md 4)")
-        if "bwd_rows" in kernels and not (args.raster_flags & _lib.GAGS_BWD_F32MFMA):
-            kernels["bwd_rows"]["note"] = ("algorithmic fp32 flops (2 D Q_blend) against the fp32 matrix peak; the kernel issues them as "
-                                           "3 v_mfma_f32_32x32x16_f16 terms per product on two-term split operands (one fp32-level rounding per operand: as close "
-                                           "to float64 as fp32 matrix arithmetic, DESIGN.md 4); 32-row MFMA tiles "
-                                           "are chunks of 32 consecutive tile rows x one 8x8 block (58 % of their rows are non-zero at C3)")
-        dom = max(kernels, key=lambda k_: kernels[k_]["avg_launch_ms"])
-        prefix = STAGE_KERNELS.get(dom, (dom,))[0]
-        names = [k_ for k_ in traffic if k_.startswith(prefix)]  # the kernel's full short name in the committed profile
-        roof = dict(kernels[dom], kernel=dom, rocprof_name=names[0] if len(names) == 1 else prefix, traffic_source=traffic_src)
         line = {
             "metric": "feature-raster fwd+bwd views/s",
             "value": value, "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -610,8 +599,7 @@ def main():
                                                                      else "0.0009 z_mean: meets SURVEY 8d's stated median radius / I~5N; "
                                                                           "the literal 0.004 constant is reported as heavy_workload"),
                        "isects_per_visible": n_isects / max(n_visible, 1),
-                       "visible": n_visible, "n_isects": n_isects, "pairs_evaluated": q_eval,
-                       "pairs_blended": q_blend, "bwd_rows": rows, "gaussians_blended": n_blended,
+                       "visible": n_visible, "n_isects": n_isects,
                        "parallelism": (f"channel-shard{world} (no data-path collective)" if mode == "channel"
                                        else f"view-dp{world}" + ((" + RCCL all-reduce of the feature gradient" if args.grad_reduce == "allreduce"
                                                                   else " + RCCL reduce-scatter/all-gather of the feature gradient")
@@ -625,15 +613,9 @@ def main():
                                           "rows_exchanged_last_step": (exposed[-1].rows_exchanged if exposed else None),
                                           "collective_ms_per_step": collective_ms,
                                           "rccl": rccl_info()})},
-            "roofline": roof,
-            "kernels": kernels,
             "activation_getters": "fused: exp / normalize / sigmoid of scene/gaussian_model.py:116-139 run inside the projection kernel "
                                   "(gags_project_fwd_raw, bit-identical to torch's) on every render, inside the timed region; no getter "
                                   "kernels are launched, so the activation cache of gags_amd/scene.py has nothing left to save here",
-            "stages_ms": {k: round(v[0], 4) for k, v in sorted(stages.items())},
-            "step_ms": {"median": per_step[len(per_step) // 2], "p10": per_step[int(0.1 * (len(per_step) - 1))],
-                        "p90": per_step[int(round(0.9 * (len(per_step) - 1)))]},
-            "optimizer_step": adam,
         }
         # whole-step view of the metric's "HBM-roofline %": compulsory traffic of one view, every tensor once
         # (SURVEY.md 8d):  72 N + 36 I + 2 V D s_f + 2 P (D s_o + 8) + 4 V D   bytes, s_f = s_o = 4
@@ -642,9 +624,89 @@ def main():
         gbs = b_view * views_per_gpu_step / (ms_per_step * 1e-3) / 1e9
         line["hbm_roofline_step"] = {"algorithmic_bytes_per_view": b_view, "achieved": gbs, "peak": HBM_PEAK_GBS,
                                      "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # Per-kernel roofline.  Each entry is ONE kernel bracketed by HIP events on the
+            # launch stream; algorithmic work per launch:
+            #   raster_fwd  : 14*Q_eval + 2*D*Q_blend flops              (weights + feature passes; fp32 MFMA bound)
+            #   bwd_rows    : 2*D*Q_blend flops                           (weight tile, MFMA, row stores)
+            #   bwd_reduce  : 2*B*D*4 bytes, B = Gaussians that blended anything: each one's gradient row formed from at least one
+            #                 partial row and written once (HBM bound; the kernel actually reads one row per touched (tile,
+            #                 Gaussian) -- 4.7 per blended Gaussian at C3 -- and, since round 6's persistent gradient buffer, no
+            #                 longer writes the zero rows of the other N - B Gaussians)
+            #   raster_bwd  : 14*Q_eval + 2*D*Q_blend flops              (single-kernel atomic backward, if used)
+            rows = profiler.notes().get("bwd_rows", 0)
+            g_last = pc._semantic_feature.grad
+            n_blended = int((g_last != 0).any(dim=1).sum().item()) if g_last is not None else 0  # rows of the gradient that are not zero
+            blk = profiler.notes().get("fwd_blk_rows")
+            slots = int(blk.sum().item()) if blk is not None else 0  # (block, Gaussian) pairs that blended: one weight row each
+            #   raster_weights : HBM bytes = 40 I (ids, records, hit flags) + 264 slots (weight row, ids) + 12 P (alpha, last id, T)
+            #                    (reported against HBM; the kernel is VALU-bound -- 14 flops per evaluated pair -- and says so)
+            #   raster_fwd_feat: 2*D*Q_blend flops  (priced against the fp32 matrix peak: the arithmetic it replaces; issued as six
+            #                    v_mfma_f32_32x32x16_bf16 terms per product on operands split into three bf16 terms)
+            work = {
+                "raster_weights": ("hbm", 40.0 * n_isects + 264.0 * slots + 12.0 * pix),
+                "raster_fwd_feat": ("mfma", 2.0 * dl * q_blend),
+                "bwd_rows": ("mfma", 2.0 * dl * q_blend),
+                "bwd_reduce": ("hbm", 8.0 * dl * n_blended),
+                "raster_bwd": ("mfma", 14.0 * q_eval + 2.0 * dl * q_blend),
+            }
+            kernels = {}
+            for name, (bound, amount) in work.items():
+                if name in stages and stages[name][0] > 0:
+                    ms = stages[name][0]
+                    if bound == "mfma":
+                        ach, peak, unit = amount / (ms * 1e-3) / 1e12, FP32_MATRIX_PEAK_TFLOPS, "TFLOP/s"
+                    else:
+                        ach, peak, unit = amount / (ms * 1e-3) / 1e9, HBM_PEAK_GBS, "GB/s"
+                    kernels[name] = {"bound": bound, "avg_launch_ms": ms, "achieved": ach, "peak": peak, "unit": unit,
+                                     "frac": ach / peak}
+            # HBM traffic per launch from the committed rocprofv3 PMC passes of this very command
+            # (tools/pmc_passes.sh -> profiles/*_pmc_traffic.json: 2*FETCH_SIZE + WRITE_SIZE, separate passes)
+            traffic, traffic_src = pmc_traffic(args) if world == 1 else ({}, None)
+            for name, members in STAGE_KERNELS.items():
+                if name in kernels:
+                    tb = [_traffic_of(traffic, m) for m in members]
+                    kernels[name]["traffic"] = sum(tb) if all(t is not None for t in tb) else None
+                    # matrix work the kernel ISSUES per launch (SQ_INSTS_MFMA x flops per instruction, same PMC passes) next
+                    # to the algorithmic flops: the ratio is the padding (zero halves, ragged 32-row tiles, split terms)
+                    mi = _traffic_of(traffic, members[0], "mfma_insts")
+                    if name in MFMA_FLOP and mi:
+                        ms = kernels[name]["avg_launch_ms"]
+                        issued = mi * MFMA_FLOP[name]
+                        pipe_peak = (FP32_MATRIX_PEAK_TFLOPS if (name == "bwd_rows" and (args.raster_flags & _lib.GAGS_BWD_F32MFMA))
+                                     or (name == "raster_fwd_feat" and (args.raster_flags & _lib.GAGS_FWD_EXACT)) else F16_MATRIX_PEAK_TFLOPS)
+                        kernels[name]["issued_flops"] = issued
+                        kernels[name]["mfma_issue_frac"] = issued / (ms * 1e-3) / 1e12 / pipe_peak
+                        kernels[name]["mfma_busy_cycles"] = _traffic_of(traffic, members[0], "mfma_busy_cycles")
+                        kernels[name]["busy_cu_cycles"] = _traffic_of(traffic, members[0], "busy_cu_cycles")
+            if "raster_weights" in kernels:
+                kernels["raster_weights"]["note"] = ("VALU-bound (14 flops per evaluated pair: 14*Q_eval = %.1f GFLOP per launch); priced "
+                                                     "against HBM by the bytes it has to move" % (14.0 * q_eval / 1e9))
+            if "raster_fwd_feat" in kernels and not (args.raster_flags & _lib.GAGS_FWD_EXACT):
+                kernels["raster_fwd_feat"]["note"] = ("algorithmic fp32 flops (2 D Q_blend) against the fp32 matrix peak; issued as 6 "
+                                                      "v_mfma_f32_32x32x16_bf16 terms per product, both operands split into three bf16 terms "
+                                                      "in registers (exact operands; fp32-equivalent, DESIGN.md 4)")
+            if "bwd_rows" in kernels and not (args.raster_flags & _lib.GAGS_BWD_F32MFMA):
+                kernels["bwd_rows"]["note"] = ("algorithmic fp32 flops (2 D Q_blend) against the fp32 matrix peak; the kernel issues them as "
+                                               "3 v_mfma_f32_32x32x16_f16 terms per product on two-term split operands (one fp32-level rounding per operand: as close "
+                                               "to float64 as fp32 matrix arithmetic, DESIGN.md 4); 32-row MFMA tiles "
+                                               "are chunks of 32 consecutive tile rows x one 8x8 block (58 % of their rows are non-zero at C3)")
+            dom = max(kernels, key=lambda k_: kernels[k_]["avg_launch_ms"])
+            prefix = STAGE_KERNELS.get(dom, (dom,))[0]
+            names = [k_ for k_ in traffic if k_.startswith(prefix)]  # the kernel's full short name in the committed profile
+            roof = dict(kernels[dom], kernel=dom, rocprof_name=names[0] if len(names) == 1 else prefix, traffic_source=traffic_src)
+            line["config"].update(pairs_evaluated=q_eval, pairs_blended=q_blend, bwd_rows=rows, gaussians_blended=n_blended)
+            line.update({
+                "roofline": roof,
+                "kernels": kernels,
+                "stages_ms": {k: round(v[0], 4) for k, v in sorted(stages.items())},
+                "step_ms": {"median": per_step[len(per_step) // 2], "p10": per_step[int(0.1 * (len(per_step) - 1))],
+                            "p90": per_step[int(round(0.9 * (len(per_step) - 1)))]},
+                "optimizer_step": adam,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(pc, cam, d, width, height, args.cpu_seconds)
-        if world == 1 and d % 128 == 0 and not (args.no_heavy or args.raster_flags):
+        if args.full and world == 1 and d % 128 == 0 and not (args.no_heavy or args.raster_flags):
             # the same workload with the backward's contraction on the fp32 matrix instructions (rounds 1-2's default,
             # gags_amd._lib.GAGS_BWD_F32MFMA), reported next to `value` for comparison; DESIGN.md section 4
             args.raster_flags = _lib.GAGS_BWD_F32MFMA
@@ -695,7 +757,7 @@ def main():
                 "note": "same workload with GAGS_FWD_EXACT | GAGS_BWD_F32MFMA: both contractions on v_mfma_f32_32x32x2_f32 (forward "
                         "bit-identical to the oracle's sequential chain, backward plain fp32 matrix arithmetic): the strict-fp32 step",
                 "value": fsteps / fdt, "unit": "views/s", "ms_per_step": 1e3 * fdt / fsteps, "steps": fsteps}
-        if world == 1 and not (args.no_heavy or args.raster_flags):
+        if args.full and world == 1 and not (args.no_heavy or args.raster_flags):
             # north_star's "feature / geometry gradients": the same workload with EVERY parameter requiring grad (joint
             # training; the reference's GAD stage freezes the geometry).  Reported next to `value`, never as `value`.
             geo = [pc._xyz, pc._scaling, pc._rotation, pc._opacity]
@@ -719,7 +781,7 @@ def main():
                 "note": "same workload, gradients of features AND means, quats, scales, opacities (SURVEY A9 + K2): geometry "
                         "dot products on the 16-bit matrix cores with fp32-equivalent split operands (gags_raster_bwd_geom), no atomics",
                 "value": gsteps / gdt, "unit": "views/s", "ms_per_step": 1e3 * gdt / gsteps, "steps": gsteps}
-        if world == 1 and d % 128 == 0 and d > 128 and not (args.no_heavy or args.raster_flags):
+        if args.full and world == 1 and d % 128 == 0 and d > 128 and not (args.no_heavy or args.raster_flags):
             # The N > 1 code path priced on ONE GPU (no multi-GPU box is reachable from the build): the by-view step exactly as
             # rank 0 of 8 runs it, with every collective replaced by two device copies of the block it would exchange
             # (OverlappedGradReducer(loopback=...)): range-staged backward, gags_blended_mask, gags_compact_mask, pack and unpack
@@ -777,7 +839,7 @@ def main():
                 "rows_per_256_channels": {"view_dp_step_ms": vdt256, "overhead_ms": vdt256 - pdt, "exposed_ms_last_step": exposed256},
                 "exposed_ms_last_step": red.exposed_ms(), "range_exchange_ms_last_step": red.range_ms, "steps": vsteps}
             del red, G_dp
-        if world == 1 and args.config == "C3" and not (args.no_heavy or args.n or args.d):
+        if args.full and world == 1 and args.config == "C3" and not (args.no_heavy or args.n or args.d):
             # second reading of SURVEY 8d (gags_amd/synthetic.py): same N / resolution / D, ~4.4x larger splats
             del step, pc
             torch.cuda.empty_cache()
@@ -798,7 +860,7 @@ def main():
                 "workload": f"C3H: {n} Gaussians, {width}x{height}, D={d}, splat scale 0.004 z_mean (SURVEY 8d literal)",
                 "value": hsteps / hdt, "unit": "views/s", "ms_per_step": 1e3 * hdt / hsteps, "steps": hsteps,
                 "n_isects": hi, "visible": hv, "isects_per_visible": hi / max(hv, 1)}
-        if world == 1 and args.config == "C3" and not (args.no_heavy or args.n or args.d or args.raster_flags):
+        if args.full and world == 1 and args.config == "C3" and not (args.no_heavy or args.n or args.d or args.raster_flags):
             # BASELINE.json configs[2] says "full GAD.sh distillation loop": one train.py:142-174 iteration at the width the
             # reference really rasterizes (D = 16, train.py:68) -- render -> CNN_scale_decoder / CNN_decoder -> losses ->
             # backward through decoders and rasterizer -- through gags_amd.distill.distillation_loss, the composition

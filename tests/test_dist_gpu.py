@@ -396,7 +396,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--config", "C2", "--n-gaussians", "20000", "--feature-dim", "256",  # (torchrun's argparse claims a bare --n)
-            "--no-cpu-baseline", "--no-heavy"]
+            "--full", "--no-cpu-baseline", "--no-heavy"]  # (--full: the comparison with the other collective)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -411,6 +411,36 @@ def test_bench_two_ranks_under_torch_distributed_run():
     assert "view-dp2" in line["config"]["parallelism"]
     assert ge["collective_ms_per_step"]["allreduce"] > 0 and "version" in ge["rccl"]
     assert "rs_ag" in ge["collective_ms_per_step"]  # the other collective was attempted (gloo refuses it on device tensors: null)
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """bench.py --gpus 1 as the driver runs it, on a small workload: one JSON line with the contract keys, the timed steps
+    asked for and nothing that --full adds; --dump-outputs writes the last timed step's outputs (float32 / float64, at most
+    64 MB), bit-identical in a second run with the same arguments (seeded inputs, no atomics)."""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+           "--config", "C2", "--n-gaussians", "20000", "--feature-dim", "256"]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run(cmd + ["--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["metric"] == "feature-raster fwd+bwd views/s" and line["unit"] == "views/s" and line["dtype"] == "f32"
+        assert line["higher_is_better"] is True and line["steps"] == 4 and line["value"] > 0
+        assert line["ms_per_step"] * line["value"] == pytest.approx(1e3)  # one view per step
+        assert not {"roofline", "kernels", "stages_ms", "cpu_baseline", "optimizer_step", "heavy_workload"} & set(line)
+        dumps.append({f.stem: np.load(f) for f in out.iterdir()})
+    assert set(dumps[0]) == {"loss", "render", "alphas", "radii", "feature_grad", "feature_grad_row_sums"}
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64e6
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a, dumps[1][name], err_msg=name)
+    assert dumps[0]["render"].shape[1] == 256 and dumps[0]["radii"].shape == (20000, 1)
+    assert np.count_nonzero(dumps[0]["radii"]) > 0 and np.count_nonzero(dumps[0]["feature_grad_row_sums"]) > 0
 
 
 @pytest.mark.parametrize("d,c0,c1", [(256, 128, 256), (37, 5, 30), (130, 2, 130), (64, 0, 64)])

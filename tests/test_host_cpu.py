@@ -99,3 +99,36 @@ def test_frozen_activations_are_cached_and_invalidated():
     o = m.get_opacity
     assert o.requires_grad and m.get_opacity is not o
     assert torch.allclose(m.get_rotation.norm(dim=1), torch.ones(n))
+
+
+def test_bench_dump_keeps_small_arrays_whole_and_samples_the_same_rows_of_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files (row sums float64); an array above its cap is written as a seeded sample of its
+    rows, in their order, the same on every call."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAP", 600)
+    g = torch.Generator().manual_seed(0)
+    n, d, h, w = 1000, 8, 12, 10
+    hwd = torch.randn(h, w, d, generator=g)
+    hwd[..., 0] = torch.arange(h * w, dtype=torch.float32).reshape(h, w)  # channel 0 = pixel index
+    grad = torch.randn(n, d, generator=g)
+    grad[:, 0] = torch.arange(n, dtype=torch.float32)  # column 0 = row index
+    pkg = {"render": hwd.permute(2, 0, 1), "alphas": torch.rand(h, w, generator=g), "loss": torch.tensor(2.5),
+           "radii": torch.arange(n, dtype=torch.int32)}  # radii = row index
+    for k in (0, 1):
+        bench.dump_outputs(str(tmp_path / str(k)), pkg, grad)
+    z = [{f.stem: np.load(f) for f in (tmp_path / str(k)).iterdir()} for k in (0, 1)]
+    assert set(z[0]) == {"loss", "render", "alphas", "radii", "feature_grad", "feature_grad_row_sums"}
+    for name, a in z[0].items():
+        assert a.dtype == (np.float64 if name == "feature_grad_row_sums" else np.float32), name
+        np.testing.assert_array_equal(a, z[1][name], err_msg=name)
+    assert z[0]["loss"].tolist() == [2.5]
+    np.testing.assert_array_equal(z[0]["alphas"][:, 0], pkg["alphas"].reshape(-1).numpy())  # 120 elements: whole
+    rows = z[0]["render"]  # 960 elements: 600 // 8 = 75 pixels
+    assert rows.shape == (75, d) and np.all(np.diff(rows[:, 0]) > 0)
+    np.testing.assert_array_equal(rows, hwd.reshape(-1, d).numpy()[rows[:, 0].astype(np.int64)])
+    idx = z[0]["radii"][:, 0].astype(np.int64)
+    assert len(idx) == 600 and np.all(np.diff(idx) > 0)
+    np.testing.assert_allclose(z[0]["feature_grad_row_sums"][:, 0], grad.double().sum(1).numpy()[idx], rtol=1e-12)
+    rows = z[0]["feature_grad"]  # twice the cap: 1200 // 8 = 150 rows
+    assert rows.shape == (150, d) and np.all(np.diff(rows[:, 0]) > 0)
+    np.testing.assert_array_equal(rows, grad.numpy()[rows[:, 0].astype(np.int64)])

@@ -12,7 +12,7 @@ libs = [a for a in sys.argv[1:] if a.endswith(".so")]
 rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 3
 envs = [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == "--env"]  # applied to the LAST library only
 code = ("import sys, runpy; sys.path.insert(0, %r); import gags_amd._lib as L; L.LIB_PATH = %r; "
-        "sys.argv = ['bench.py', '--steps', '20', '--warmup', '3', '--no-cpu-baseline', '--no-heavy']; "
+        "sys.argv = ['bench.py', '--steps', '20', '--warmup', '3', '--full', '--no-cpu-baseline', '--no-heavy']; "
         "runpy.run_path(%r, run_name='__main__')")
 res = {}
 for r in range(rounds):

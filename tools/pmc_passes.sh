@@ -13,7 +13,7 @@ while read -r CTRS; do
   [ -z "$CTRS" ] && continue
   i=$((i+1))
   timeout 600 rocprofv3 --kernel-trace --pmc $CTRS -d "$OUT/pass$i" -o pmc --output-format csv -- \
-      ${PMC_CMD:-python "$R/bench.py" --no-cpu-baseline} "$@" > "$OUT/pass$i.log" 2>&1
+      ${PMC_CMD:-python "$R/bench.py" --full --no-cpu-baseline} "$@" > "$OUT/pass$i.log" 2>&1
 done <<'LIST'
 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE
 SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU
