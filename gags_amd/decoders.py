@@ -54,19 +54,6 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class _H16Mode:
-    """The 16-bit operand type of the fast kernels: which instantiation of the library's entry points (suffix) and which
-    torch dtype their 16-bit tensors have.  bf16: the "bf16" mode; f16: IEEE half, the "f16" tier (csrc/half16.h)."""
-
-    def __init__(self, name, sfx, dtype):
-        self.name, self.sfx, self.dtype = name, sfx, dtype
-
-    def fn(self, base):
-        return getattr(_lib.load(), base + self.sfx)
-
-
-_BF16 = _H16Mode("bf16", "", torch.bfloat16)
-_F16 = _H16Mode("f16", "_h16", torch.float16)
 # f16 tier: the gradient entering a backward chain is multiplied by a power of two S such that S * max|cotangent proxy| is
 # 2^F16_TARGET_LOG2 (half has 5 exponent bits: unscaled, the 1e-9 .. 1e-6 gradients of a mean-reduced loss at 1080p would be
 # flushed; conversions saturate at 65504, so a proxy that underestimates costs accuracy on the largest elements, never an inf)
@@ -83,6 +70,111 @@ def _pow2_scale(amax, target_log2=F16_TARGET_LOG2, div=1.0):
     return out[0:1], out[1:2]
 
 
+class _SplitTier:
+    """An fp32-tensor tier: fp32 weights, activations and gradients, every operand split into `terms` bfloat16 terms
+    inside the kernels (3: "exact", 2: "bf16x2"); no fused chain kernels, no gradient scaling."""
+    fused, dtype, distill_bwd = False, torch.float32, "gags_decoder_head_distill_bwd_f32"
+
+    def __init__(self, name, terms):
+        self.name, self.terms = name, terms
+
+    def weights(self, params):
+        # private copies (2.4 MB for CNN_decoder), with the transposes the input-gradient GEMMs contract made NOW: for fp32
+        # [co, ci, 1, 1] weights `[:, :, 0, 0].contiguous().float()` is a VIEW of the live parameter, and a backward that runs
+        # after an in-place optimizer step would silently differentiate the new weights (ADVICE r3)
+        wb = []
+        for wt, bs in zip(params[0::2], params[1::2]):
+            wm = wt.detach()[:, :, 0, 0].float().clone()
+            wm._gags_t = wm.t().contiguous()
+            wb.append((wm, bs.detach().float().clone()))
+        return wb
+
+    def first_activation(self, p, xp, k):
+        return xp
+
+    def layer(self, p, w, b, a1, a2=None, **kw):
+        return _xlayer(p, w, b, a1, a2, terms=self.terms, **kw)
+
+    def logits(self, p, w, b, a1, a2=None):
+        return _xlayer(p, w, b, a1, a2, relu=False, ldy=_logits_ld(w.shape[0]), terms=self.terms)
+
+    def wgrad(self, p, dz, a1, a2, w, shape, scale):
+        dw, db = _xwgrad(p, dz, a1, a2, *w.shape, terms=self.terms)
+        return dw.reshape(shape), db
+
+    def cotangent_scale(self, g, div=1.0):
+        return None, None
+
+    def head_bwd(self, p, c, head, logits, g, layout):
+        dz = torch.empty(p, c, device=g.device)
+        check(_lib.load().gags_decoder_head_bwd_exact(p, c, logits.shape[1], head, ptr(logits), ptr(g), layout, ptr(dz), c,
+                                                      _st()), "gags_decoder_head_bwd_exact")
+        return dz
+
+    def input_grad(self, gin, h, w, c_in):
+        return gin.view(h, w, c_in).permute(2, 0, 1)
+
+
+class _HalfTier:
+    """A 16-bit tier: bf16 operands ("bf16") or IEEE half ("f16": the library's entry points with suffix _h16, csrc/half16.h),
+    fp32 accumulation, 16-bit activations and gradients between layers, weights packed once (`_pack_weights`), the fused
+    chain kernels.  `scaled`: the backward multiplies the cotangent by a power of two and the results by its inverse."""
+    fused = True
+
+    def __init__(self, name, sfx, dtype, scaled):
+        self.name, self.sfx, self.dtype, self.scaled = name, sfx, dtype, scaled
+        self.distill_bwd = "gags_decoder_head_distill_bwd" + sfx
+
+    def fn(self, base):
+        return getattr(_lib.load(), base + self.sfx)
+
+    def weights(self, params):
+        return _pack_weights(params[0::2], params[1::2], self)
+
+    def first_activation(self, p, xp, k):
+        a0 = torch.empty(p, k, dtype=self.dtype, device=xp.device)
+        check(self.fn("gags_decoder_pack_input")(p, xp.shape[1], k, ptr(xp), ptr(a0), _st()), "gags_decoder_pack_input")
+        return a0
+
+    def layer(self, p, w, b, a1, a2=None, **kw):
+        return _layer(p, w, b, a1, a2, tier=self, **kw)
+
+    def logits(self, p, w, b, a1, a2=None):
+        return _layer(p, w, b, a1, a2, relu=False, f32=True, tier=self)
+
+    def wgrad(self, p, dz, a1, a2, w, shape, scale):
+        return _wgrad(p, dz, a1, a2, *w.shape, tier=self, shape=shape, scale=scale)
+
+    def cotangent_scale(self, g, div=1.0):
+        if not self.scaled:
+            return None, None
+        return _pow2_scale(torch.linalg.vector_norm(g.reshape(-1), float("inf")), div=div)  # (max |g| without an |g| temporary)
+
+    def head_bwd(self, p, c, head, logits, g, layout):
+        dz = torch.empty(p, logits.shape[1], dtype=self.dtype, device=g.device)
+        check(self.fn("gags_decoder_head_bwd")(p, c, logits.shape[1], head, ptr(logits), ptr(g), ptr(dz), layout, _st()),
+              "gags_decoder_head_bwd")
+        return dz
+
+    def input_grad(self, gin, h, w, c_in):
+        gx = torch.empty(h, w, c_in, device=gin.device)
+        check(self.fn("gags_decoder_unpack_grad")(h * w, c_in, gin.shape[1], ptr(gin), ptr(gx), _st()), "gags_decoder_unpack_grad")
+        return gx.permute(2, 0, 1)
+
+
+_TIERS = {"exact": _SplitTier("exact", 3), "bf16x2": _SplitTier("bf16x2", 2),
+          "bf16": _HalfTier("bf16", "", torch.bfloat16, False), "f16": _HalfTier("f16", "_h16", torch.float16, True)}
+_BF16, _F16 = _TIERS["bf16"], _TIERS["f16"]  # the 16-bit tiers by the names the bit-identity tests pass to _chain_forward
+
+
+def _tier(precision):
+    if precision not in _TIERS:
+        raise ValueError("precision must be 'exact' (fp32-equivalent, the default), 'bf16x2' (two-term split: 16 significand "
+                         "bits, tighter than the TF32 the reference's convs run in), 'f16' (IEEE half operands: TF32's own "
+                         "11-bit significand, fp32 accumulation, power-of-two gradient scaling) or 'bf16' (8 bits, fast opt-in)")
+    return _TIERS[precision]
+
+
 def _pad32(n):
     return (n + 31) // 32 * 32
 
@@ -96,43 +188,43 @@ def _pixel_major(x):
     return xp.reshape(h * w, c), h, w
 
 
-def _layer(n_pix, w, b, a1, a2=None, relu=True, f32=False, mask_src=None, residual=None, premask=False, mode=_BF16):
+def _layer(n_pix, w, b, a1, a2=None, relu=True, f32=False, mask_src=None, residual=None, premask=False, tier=_BF16):
     """One GEMM layer (gags_decoder_layer).  Returns y (16-bit, or fp32 with f32=True) and, with premask=True, also the
     16-bit value before the mask."""
     n, k = w.shape
     dev = w.device
-    y = None if f32 else torch.empty(n_pix, n, dtype=mode.dtype, device=dev)
+    y = None if f32 else torch.empty(n_pix, n, dtype=tier.dtype, device=dev)
     yf = torch.empty(n_pix, n, device=dev) if f32 else None
-    ypre = torch.empty(n_pix, n, dtype=mode.dtype, device=dev) if premask else None
-    check(mode.fn("gags_decoder_layer")(n_pix, n, k, ptr(a1), ptr(a2), ptr(w), ptr(b), int(relu), ptr(mask_src),
+    ypre = torch.empty(n_pix, n, dtype=tier.dtype, device=dev) if premask else None
+    check(tier.fn("gags_decoder_layer")(n_pix, n, k, ptr(a1), ptr(a2), ptr(w), ptr(b), int(relu), ptr(mask_src),
                                         ptr(residual), ptr(y), ptr(ypre), ptr(yf), _st()), "gags_decoder_layer")
     out = yf if f32 else y
     return (out, ypre) if premask else out
 
 
-def _wgrad(n_pix, dz, a1, a2, n, k, mode=_BF16, shape=None, scale=None):
+def _wgrad(n_pix, dz, a1, a2, n, k, tier=_BF16, shape=None, scale=None):
     """Weight and bias gradient of one layer from the padded operands.  shape = the parameter's own (co, ci, ...): the gradient
     is written in that shape (gags_decoder_wgrad_out: no slice copy afterwards); scale: a device scalar every sum is multiplied
     by (the f16 tier's power of two)."""
     co, ci = (n, k) if shape is None else (shape[0], shape[1])
     dw = torch.empty((co, ci) if shape is None else shape, device=dz.device)
     db = torch.empty(co, device=dz.device)
-    nb = mode.fn("gags_decoder_wgrad_scratch_bytes")(n_pix, n, k)
+    nb = tier.fn("gags_decoder_wgrad_scratch_bytes")(n_pix, n, k)
     scratch = torch.empty(max(nb, 4), dtype=torch.uint8, device=dz.device)  # partial matrices per pixel chunk
-    check(mode.fn("gags_decoder_wgrad_out")(n_pix, n, k, ptr(dz), ptr(a1), ptr(a2), ptr(dw), ptr(db), co, ci, ptr(scale),
+    check(tier.fn("gags_decoder_wgrad_out")(n_pix, n, k, ptr(dz), ptr(a1), ptr(a2), ptr(dw), ptr(db), co, ci, ptr(scale),
                                             ptr(scratch), nb, _st()), "gags_decoder_wgrad_out")
     return dw, db
 
 
-_PACK_CACHE = {}  # (id of the first weight) -> (versions, packed): decoders whose parameters did not change are not repacked
+_PACK_CACHE = {}  # (id of the first weight, tier) -> (versions, packed): decoders whose parameters did not change are not repacked
 
 
-def _pack_weights(weights, biases, mode=_BF16):
-    """bf16 [N_pad, K_pad] weights and fp32 [N_pad] biases, every dimension zero-padded to a multiple of 32; each packed
+def _pack_weights(weights, biases, tier=_BF16):
+    """16-bit [N_pad, K_pad] weights and fp32 [N_pad] biases, every dimension zero-padded to a multiple of 32; each packed
     weight also carries its transpose (for the input-gradient GEMMs) and both in MFMA-fragment order (for the fused
     kernels) as attributes -- one gags_decoder_pack_layers launch for the whole decoder, and none while the parameters' version
     counters stand still (frozen decoders, the second use within one iteration's backward)."""
-    key = (id(weights[0]), mode.name)
+    key = (id(weights[0]), tier.name)
     vers = tuple((t.data_ptr(), t._version) for t in list(weights) + list(biases))
     hit = _PACK_CACHE.get(key)
     # (the weak references tell a parameter from a later one that got the same id, address and version counter)
@@ -143,10 +235,10 @@ def _pack_weights(weights, biases, mode=_BF16):
         co, ci = wt.shape[:2]
         n, k = _pad32(co), _pad32(ci)
         dev = wt.device
-        w = torch.empty(n, k, device=dev, dtype=mode.dtype)
-        w_t = torch.empty(k, n, device=dev, dtype=mode.dtype)
-        wf = torch.empty(n // 32, k // 16, 2, 32, 8, device=dev, dtype=mode.dtype)
-        wtf = torch.empty(k // 32, n // 16, 2, 32, 8, device=dev, dtype=mode.dtype)
+        w = torch.empty(n, k, device=dev, dtype=tier.dtype)
+        w_t = torch.empty(k, n, device=dev, dtype=tier.dtype)
+        wf = torch.empty(n // 32, k // 16, 2, 32, 8, device=dev, dtype=tier.dtype)
+        wtf = torch.empty(k // 32, n // 16, 2, 32, 8, device=dev, dtype=tier.dtype)
         b = torch.empty(n, device=dev)
         src = wt.detach().reshape(co, ci)
         srcs.append(src if (src.is_contiguous() and src.dtype == torch.float32) else src.contiguous().float())
@@ -160,7 +252,7 @@ def _pack_weights(weights, biases, mode=_BF16):
         sl = slice(i0, i0 + 12)
         m = len(out[sl])
         ints, ptrs = ctypes.c_int * m, ctypes.c_void_p * m
-        check(mode.fn("gags_decoder_pack_layers")(
+        check(tier.fn("gags_decoder_pack_layers")(
             m, ints(*[d[0] for d in dims[sl]]), ints(*[d[1] for d in dims[sl]]), ptrs(*[t.data_ptr() for t in srcs[sl]]),
             ptrs(*[t.data_ptr() for t in bsrcs[sl]]), ptrs(*[w.data_ptr() for w, _ in out[sl]]),
             ptrs(*[w._gags_t.data_ptr() for w, _ in out[sl]]), ptrs(*[w._gags_frag.data_ptr() for w, _ in out[sl]]),
@@ -216,101 +308,7 @@ def _logits_ld(c_out):
     return c_out if c_out % 32 == 0 else (c_out + 7) // 8 * 8
 
 
-def _chain_forward_exact(x, kind, params, terms=3):
-    """The fp32 chain of a decoder up to its logits (precision="exact": terms = 3; "bf16x2": terms = 2).  Same return tuple
-    as _chain_forward; `wb` holds the fp32 [out, in] weight matrices and biases."""
-    import functools
-    _xl = functools.partial(_xlayer, terms=terms)
-    weights, biases = params[0::2], params[1::2]
-    # private copies (2.4 MB for CNN_decoder), with the transposes the input-gradient GEMMs contract made NOW: for fp32
-    # [co, ci, 1, 1] weights `[:, :, 0, 0].contiguous().float()` is a VIEW of the live parameter, and a backward that runs
-    # after an in-place optimizer step would silently differentiate the new weights (ADVICE r3)
-    wb = []
-    for wt, bs in zip(weights, biases):
-        wm = wt.detach()[:, :, 0, 0].float().clone()
-        wm._gags_t = wm.t().contiguous()
-        wb.append((wm, bs.detach().float().clone()))
-    xp, h, w = _pixel_major(x)
-    p = h * w
-    a0 = xp
-    ld = _logits_ld(wb[-1][0].shape[0])
-    if kind == "decoder":
-        x1 = _xl(p, *wb[0], a0)
-        t1 = _xl(p, *wb[1], x1)
-        x2 = _xl(p, *wb[2], t1)
-        x3 = _xl(p, *wb[3], x1, x2)   # conv(x1 + x2)
-        t4 = _xl(p, *wb[4], x3)
-        x4 = _xl(p, *wb[5], t4)
-        t6 = _xl(p, *wb[6], x3, x4)   # conv(x3 + x4)
-        t7 = _xl(p, *wb[7], t6)
-        logits = _xl(p, *wb[8], t7, relu=False, ldy=ld)
-        acts = [a0, x1, t1, x2, x3, t4, x4, t6, t7]
-    else:
-        acts = [a0]
-        a = a0
-        for i, (wt, b) in enumerate(wb):
-            last = i + 1 == len(wb)
-            a = _xl(p, wt, b, a, relu=not last, ldy=ld if last else None)
-            if not last:
-                acts.append(a)
-        logits = a
-    return logits, acts, wb, h, w, xp.shape[1]
-
-
-def _chain_backward_exact(dz, acts, wb, kind, h, w, c_in, shapes, need_x=True, need_w=None, terms=3):
-    """fp32 backward of the chain from dz [P, c_out] (precision="exact" / "bf16x2")."""
-    p = h * w
-    need_w = need_w or [True] * len(wb)
-    wt = [_transposed(wgt) for wgt, _ in wb]  # [k_in, n_out] (made in the forward): the input-gradient GEMM contracts over n_out
-    dws = [None] * len(wb)
-
-    def wg(i, dz_i, a1, a2=None):
-        if need_w[i]:
-            dws[i] = _xwgrad(p, dz_i, a1, a2, *wb[i][0].shape, terms=terms)
-
-    def dx(i, dz_i, mask_src=None, residual=None, premask=False):
-        return _xlayer(p, wt[i], None, dz_i, relu=False, mask_src=mask_src, residual=residual, premask=premask, terms=terms)
-
-    gin = None
-    if kind == "decoder":
-        a0, x1, t1, x2, x3, t4, x4, t6, t7 = acts
-        wg(8, dz, t7)
-        dz7 = dx(8, dz, mask_src=t7)
-        wg(7, dz7, t6)
-        dz6 = dx(7, dz7, mask_src=t6)
-        wg(6, dz6, x3, x4)
-        dz5, g36 = dx(6, dz6, mask_src=x4, premask=True)
-        wg(5, dz5, t4)
-        dz4 = dx(5, dz5, mask_src=t4)
-        wg(4, dz4, x3)
-        dz3 = dx(4, dz4, mask_src=x3, residual=g36)
-        wg(3, dz3, x1, x2)
-        dz2, g13 = dx(3, dz3, mask_src=x2, premask=True)
-        wg(2, dz2, t1)
-        dz1 = dx(2, dz2, mask_src=t1)
-        wg(1, dz1, x1)
-        dz0 = dx(1, dz1, mask_src=x1, residual=g13)
-        wg(0, dz0, a0)
-        if need_x:
-            gin = dx(0, dz0)
-    else:
-        cur = dz
-        for i in range(len(wb) - 1, -1, -1):
-            wg(i, cur, acts[i])
-            if i > 0 or need_x:
-                cur = dx(i, cur, mask_src=acts[i] if i > 0 else None)
-        gin = cur if need_x else None
-    gx = None if gin is None else gin.view(h, w, c_in).permute(2, 0, 1)
-    grads = []
-    for pair, shp in zip(dws, shapes):
-        if pair is None:
-            grads += [None, None]
-        else:
-            grads += [pair[0].reshape(shp), pair[1]]
-    return gx, grads
-
-
-FUSED = True  # bf16 mode: CNN_decoder's forward (and input-gradient) chain as one kernel each; False: layer by layer
+FUSED = True  # 16-bit tiers: a decoder's forward (and input-gradient) chain as one kernel each; False: layer by layer
 
 
 def _frag_layout(w):
@@ -338,153 +336,110 @@ def _scale_fusable(wb, c_in):
     return c_in <= 32 and [tuple(w.shape) for w, _ in wb] == _SCALE_SHAPES
 
 
-def _chain_forward(x, kind, params, mode=_BF16, head_out=None):
-    """The GEMM chain of a decoder up to its fp32 logits.  Returns (logits [P, ld], activations, packed weights, h, w,
-    c_in).  head_out (a [3, H, W] fp32 tensor): the fused CNN_scale_decoder kernel writes its softmax head there itself and
-    `logits` comes back None (nothing reads them: the head's backward works from its output)."""
-    weights, biases = params[0::2], params[1::2]
-    wb = _pack_weights(weights, biases, mode)
-    xp, h, w = _pixel_major(x)
-    p = h * w
-    a0 = torch.empty(p, wb[0][0].shape[1], dtype=mode.dtype, device=x.device)
-    _layer_m = lambda *a, **k: _layer(*a, mode=mode, **k)  # noqa: E731
-    if kind == "scale" and FUSED and _scale_fusable(wb, xp.shape[1]):
-        # the six layers in one kernel, a wave per 32-pixel tile (csrc/decoder_scale.hip): bit-identical to the chain below
-        dev = x.device
-        acts = [a0] + [torch.empty(p, wgt.shape[0], dtype=mode.dtype, device=dev) for wgt, _ in wb[:5]]
-        logits = torch.empty(p, 32, device=dev) if head_out is None else None
-        arr = ctypes.c_void_p * 6
-        wf = [_frag_layout(wgt) for wgt, _ in wb]
-        masks = torch.empty(p, 11, dtype=torch.int32, device=dev)  # the ReLU decisions as bits, for the fused backward
-        check(mode.fn("gags_scale_decoder_fwd_fused_head")(p, xp.shape[1], ptr(xp), arr(*[t.data_ptr() for t in wf]),
-                                                            arr(*[b.data_ptr() for _, b in wb]), arr(*[t.data_ptr() for t in acts]),
-                                                            ptr(masks), ptr(logits), ptr(head_out), _st()),
-              "gags_scale_decoder_fwd_fused_head")
-        return logits, acts + [masks], wb, h, w, xp.shape[1]
-    fused = kind == "decoder" and FUSED and _fusable(wb, xp.shape[1])
-    if not fused:  # (the fused kernel converts its input tile itself and keeps it as a0)
-        check(mode.fn("gags_decoder_pack_input")(p, xp.shape[1], a0.shape[1], ptr(xp), ptr(a0), _st()), "gags_decoder_pack_input")
-    acts = [a0]
-    if fused:
-        # the nine layers in one kernel, activations resident in LDS (csrc/decoder_fused.hip): bit-identical to the chain below
-        dev = x.device
-        acts = [a0] + [torch.empty(p, 256, dtype=mode.dtype, device=dev) for _ in range(8)]
-        logits = torch.empty(p, wb[8][0].shape[0], device=dev)
-        arr = ctypes.c_void_p * 9
-        wf = [_frag_layout(wgt) for wgt, _ in wb]
-        masks = torch.empty(8, (p + 63) // 64 * 64, 8, dtype=torch.int32, device=dev)  # the ReLU decisions as bits, for the fused
-        # backward: 8 layers x whole 64-pixel groups x 8 words (an opaque buffer: the two kernels' own layout)
-        check(mode.fn("gags_decoder_fwd_fused")(p, xp.shape[1], logits.shape[1], ptr(xp), arr(*[t.data_ptr() for t in wf]),
-                                                 arr(*[b.data_ptr() for _, b in wb]), arr(*[t.data_ptr() for t in acts]),
-                                                 ptr(masks), ptr(logits), _st()), "gags_decoder_fwd_fused")
-        return logits, acts + [masks], wb, h, w, xp.shape[1]
+# The layer wiring of both decoders.  acts[0] is the chain's input and acts[i] the output of layer i - 1; layer i reads
+# acts[i], plus acts[j] where _SKIPS[kind] maps i -> j: CNN_decoder's x3 = conv(x1 + x2) and t6 = conv(x3 + x4).
+_SKIPS = {"decoder": {3: 1, 6: 4}, "scale": {}}
+
+
+def _inputs(acts, skips, i):
+    """(a1, a2) of layer i, which reads their sum."""
+    return (acts[skips[i]], acts[i]) if i in skips else (acts[i], None)
+
+
+def _fused_forward(tier, kind, p, xp, wb, head_out):
+    """The whole chain in one kernel, bit-identical to the layer-by-layer chain: CNN_decoder's nine layers with the
+    activations resident in LDS (csrc/decoder_fused.hip), CNN_scale_decoder's six a wave per 32-pixel tile
+    (csrc/decoder_scale.hip).  The kernel converts its input tile itself and keeps it as a0; CNN_decoder's keeps x1 + x2 and
+    x3 + x4 in place of x2 / x4.  Returns (logits, activations + the ReLU decisions as bits, for the fused backward)."""
+    dev = xp.device
+    acts = [torch.empty(p, wb[0][0].shape[1], dtype=tier.dtype, device=dev)]
+    acts += [torch.empty(p, wgt.shape[0], dtype=tier.dtype, device=dev) for wgt, _ in wb[:-1]]
+    arr = ctypes.c_void_p * len(wb)
+    wf = [_frag_layout(wgt) for wgt, _ in wb]
+    wfs, bs, ats = arr(*[t.data_ptr() for t in wf]), arr(*[b.data_ptr() for _, b in wb]), arr(*[t.data_ptr() for t in acts])
     if kind == "decoder":
-        x1 = _layer_m(p, *wb[0], a0)
-        t1 = _layer_m(p, *wb[1], x1)
-        x2 = _layer_m(p, *wb[2], t1)
-        x3 = _layer_m(p, *wb[3], x1, x2)   # conv(x1 + x2)
-        t4 = _layer_m(p, *wb[4], x3)
-        x4 = _layer_m(p, *wb[5], t4)
-        t6 = _layer_m(p, *wb[6], x3, x4)   # conv(x3 + x4)
-        t7 = _layer_m(p, *wb[7], t6)
-        logits = _layer_m(p, *wb[8], t7, relu=False, f32=True)
-        acts += [x1, t1, x2, x3, t4, x4, t6, t7]
+        logits = torch.empty(p, wb[-1][0].shape[0], device=dev)
+        # 8 layers x whole 64-pixel groups x 8 words (an opaque buffer: the two kernels' own layout)
+        masks = torch.empty(8, (p + 63) // 64 * 64, 8, dtype=torch.int32, device=dev)
+        check(tier.fn("gags_decoder_fwd_fused")(p, xp.shape[1], logits.shape[1], ptr(xp), wfs, bs, ats, ptr(masks), ptr(logits),
+                                                 _st()), "gags_decoder_fwd_fused")
     else:
-        a = a0
-        for i, (wt, b) in enumerate(wb):
-            last = i + 1 == len(wb)
-            a = _layer_m(p, wt, b, a, relu=not last, f32=last)
-            if not last:
-                acts.append(a)
-        logits = a
-    return logits, acts, wb, h, w, xp.shape[1]
+        logits = torch.empty(p, 32, device=dev) if head_out is None else None
+        masks = torch.empty(p, 11, dtype=torch.int32, device=dev)
+        check(tier.fn("gags_scale_decoder_fwd_fused_head")(p, xp.shape[1], ptr(xp), wfs, bs, ats, ptr(masks), ptr(logits),
+                                                            ptr(head_out), _st()), "gags_scale_decoder_fwd_fused_head")
+    return logits, acts + [masks]
 
 
-def _chain_backward(dz, acts, wb, kind, h, w, c_in, shapes, need_x=True, need_w=None, mode=_BF16, scale=None):
-    """From the bf16 gradient of the logits dz [P, ld] back through the chain: (input gradient as a [C_in,H,W] view of
-    [H,W,C_in] memory, weight / bias gradients in parameter order, whether the input gradient already carries `scale`).
-    need_x / need_w: what autograd asked for; scale: a device scalar the parameter gradients (and, in the fused kernel, the
-    input gradient) are multiplied by on their way out."""
+def _chain_forward(x, kind, params, tier, head_out=None):
+    """The GEMM chain of a decoder up to its fp32 logits.  Returns (logits [P, ld], activations, the weights as the tier
+    prepared them, h, w, c_in).  head_out (a [3, H, W] fp32 tensor): the fused CNN_scale_decoder kernel writes its softmax
+    head there itself and `logits` comes back None (nothing reads them: the head's backward works from its output)."""
+    wb = tier.weights(params)
+    xp, h, w = _pixel_major(x)
+    p, c_in = h * w, xp.shape[1]
+    if tier.fused and FUSED and (_fusable if kind == "decoder" else _scale_fusable)(wb, c_in):
+        return (*_fused_forward(tier, kind, p, xp, wb, head_out), wb, h, w, c_in)
+    skips = _SKIPS[kind]
+    acts = [tier.first_activation(p, xp, wb[0][0].shape[1])]
+    for i, (wgt, b) in enumerate(wb[:-1]):
+        acts.append(tier.layer(p, wgt, b, *_inputs(acts, skips, i)))
+    logits = tier.logits(p, *wb[-1], *_inputs(acts, skips, len(wb) - 1))
+    return logits, acts, wb, h, w, c_in
+
+
+def _chain_backward(dz, acts, wb, kind, h, w, c_in, shapes, need_x, need_w, tier, scale=None):
+    """From the gradient of the logits dz [P, ld] back through the chain: (input gradient as a [C_in,H,W] view of
+    [H,W,C_in] memory, weight / bias gradients in parameter order).  need_x / need_w: what autograd asked for; scale: a
+    device scalar every gradient is multiplied by on its way out (the f16 tier's 1 / S)."""
     p = h * w
-    need_w = need_w or [True] * len(wb)
     wt = [_transposed(wgt) for wgt, _ in wb]  # [K_pad, N_pad]: the input-gradient GEMM contracts over N
-    dws = [None] * len(wb)
+    grads = [None] * (2 * len(wb))
 
     def wg(i, dz_i, a1, a2=None):
         if need_w[i]:  # (written in the parameter's shape, times `scale`: nothing left to do per parameter afterwards)
-            dws[i] = _wgrad(p, dz_i, a1, a2, *wb[i][0].shape, mode=mode, shape=shapes[i], scale=scale)
+            grads[2 * i:2 * i + 2] = tier.wgrad(p, dz_i, a1, a2, wb[i][0], shapes[i], scale)
 
-    def dx(i, dz_i, mask_src=None, residual=None, premask=False):
-        return _layer(p, wt[i], None, dz_i, relu=False, mask_src=mask_src, residual=residual, premask=premask, mode=mode)
-
-    if kind == "decoder" and len(acts) == 10:  # the fused forward ran (its bit masks ride along as the tenth entry)
-        # the nine input-gradient GEMMs in one kernel (csrc/decoder_fused.hip), then the weight gradients
-        a0, x1, t1, s12, x3, t4, s34, t6, t7, masks = acts  # (the fused forward keeps x1 + x2 and x3 + x4 in place of x2 / x4)
+    gx = gin = None
+    masks = acts[len(wb)] if len(acts) > len(wb) else None  # the fused forward ran: its ReLU bit masks ride along
+    if masks is not None and (kind == "decoder" or (FUSED and dz.shape[1] == 32)):
+        # the input-gradient GEMMs in one kernel (bit-identical to the loop below), then the weight gradients; every layer
+        # reads the one activation the fused forward kept for it
         dev = dz.device
-        dzs = [torch.empty(p, 256, dtype=mode.dtype, device=dev) for _ in range(8)]
-        gx = torch.empty(h, w, c_in, device=dev) if need_x else None
-        arr = ctypes.c_void_p * 9
-        arr8 = ctypes.c_void_p * 8
+        dzs = [torch.empty(p, wgt.shape[0], dtype=tier.dtype, device=dev) for wgt, _ in wb[:-1]]
         wtf = [_frag_layout(t) for t in wt]
-        check(mode.fn("gags_decoder_bwd_fused_scaled")(p, c_in, dz.shape[1], ptr(dz), arr(*[t.data_ptr() for t in wtf]), ptr(masks),
-                                                        arr8(*[t.data_ptr() for t in dzs]), ptr(gx), ptr(scale), _st()),
-              "gags_decoder_bwd_fused_scaled")
-        scaled_gx = True
-        wg(8, dz, t7); wg(7, dzs[7], t6); wg(6, dzs[6], s34); wg(5, dzs[5], t4); wg(4, dzs[4], x3)
-        wg(3, dzs[3], s12); wg(2, dzs[2], t1); wg(1, dzs[1], x1); wg(0, dzs[0], a0)
-        grads = []
-        for pair in dws:
-            grads += [None, None] if pair is None else [pair[0], pair[1]]
-        return (None if gx is None else gx.permute(2, 0, 1)), grads, scaled_gx
-    if kind == "decoder":
-        a0, x1, t1, x2, x3, t4, x4, t6, t7 = acts
-        wg(8, dz, t7)
-        dz7 = dx(8, dz, mask_src=t7)
-        wg(7, dz7, t6)
-        dz6 = dx(7, dz7, mask_src=t6)
-        wg(6, dz6, x3, x4)
-        dz5, g36 = dx(6, dz6, mask_src=x4, premask=True)     # d(x3 + x4): masked for x4's ReLU, raw for the skip to x3
-        wg(5, dz5, t4)
-        dz4 = dx(5, dz5, mask_src=t4)
-        wg(4, dz4, x3)
-        dz3 = dx(4, dz4, mask_src=x3, residual=g36)           # both paths into x3, then its ReLU
-        wg(3, dz3, x1, x2)
-        dz2, g13 = dx(3, dz3, mask_src=x2, premask=True)
-        wg(2, dz2, t1)
-        dz1 = dx(2, dz2, mask_src=t1)
-        wg(1, dz1, x1)
-        dz0 = dx(1, dz1, mask_src=x1, residual=g13)
-        wg(0, dz0, a0)
-        gin = dx(0, dz0) if need_x else None
-    else:
-        smask = acts[len(wb)] if len(acts) == len(wb) + 1 else None  # the fused forward's ReLU bit masks (csrc/decoder_scale.hip)
-        if smask is not None and FUSED and dz.shape[1] == 32:
-            # the five input-gradient GEMMs in one kernel (bit-identical to the loop below), then the weight gradients
-            dzs = [torch.empty(p, wgt.shape[0], dtype=mode.dtype, device=dz.device) for wgt, _ in wb[:5]]
-            arr6, arr5 = ctypes.c_void_p * 6, ctypes.c_void_p * 5
-            wtf = [None] + [_frag_layout(t) for t in wt[1:]]
-            check(mode.fn("gags_scale_decoder_bwd_fused")(p, ptr(dz), arr6(*[None if t is None else t.data_ptr() for t in wtf]),
-                                                           ptr(smask), arr5(*[t.data_ptr() for t in dzs]), _st()),
-                  "gags_scale_decoder_bwd_fused")
-            for i in range(len(wb) - 1, -1, -1):
-                wg(i, dz if i == 5 else dzs[i], acts[i])
-            gin = dx(0, dzs[0]) if need_x else None
+        arr, arr_dz = ctypes.c_void_p * len(wb), ctypes.c_void_p * len(dzs)
+        if kind == "decoder":  # (the kernel also writes the input gradient, times `scale`)
+            gx = torch.empty(h, w, c_in, device=dev) if need_x else None
+            check(tier.fn("gags_decoder_bwd_fused_scaled")(p, c_in, dz.shape[1], ptr(dz), arr(*[t.data_ptr() for t in wtf]),
+                                                           ptr(masks), arr_dz(*[t.data_ptr() for t in dzs]), ptr(gx), ptr(scale),
+                                                           _st()), "gags_decoder_bwd_fused_scaled")
+            gx = None if gx is None else gx.permute(2, 0, 1)
         else:
-            cur = dz
-            for i in range(len(wb) - 1, -1, -1):
-                wg(i, cur, acts[i])
-                if i > 0 or need_x:
-                    cur = dx(i, cur, mask_src=acts[i] if i > 0 else None)
-            gin = cur if need_x else None
-    gx = None
+            check(tier.fn("gags_scale_decoder_bwd_fused")(p, ptr(dz), arr(None, *[t.data_ptr() for t in wtf[1:]]), ptr(masks),
+                                                          arr_dz(*[t.data_ptr() for t in dzs]), _st()), "gags_scale_decoder_bwd_fused")
+        for i in reversed(range(len(wb))):
+            wg(i, dzs[i] if i < len(dzs) else dz, acts[i])
+        if kind == "scale" and need_x:
+            gin = tier.layer(p, wt[0], None, dzs[0], relu=False)
+    else:
+        skips, skip_grads = _SKIPS[kind], {}
+        cur = dz
+        for i in reversed(range(len(wb))):
+            wg(i, cur, *_inputs(acts, skips, i))
+            if i == 0 and not need_x:
+                break
+            # W_i^T dz_i, plus what a skip carried back to acts[i], masked by acts[i]'s ReLU; a layer that reads a sum hands
+            # the unmasked value on to the skip's source, whose own layer adds it (d(x3 + x4): masked for x4, raw for x3)
+            cur = tier.layer(p, wt[i], None, cur, relu=False, mask_src=acts[i] if i > 0 else None,
+                             residual=skip_grads.pop(i, None), premask=i in skips)
+            if i in skips:
+                cur, skip_grads[skips[i]] = cur
+        gin = cur if need_x else None
     if gin is not None:
-        gx = torch.empty(h, w, c_in, device=dz.device)
-        check(mode.fn("gags_decoder_unpack_grad")(p, c_in, gin.shape[1], ptr(gin), ptr(gx), _st()), "gags_decoder_unpack_grad")
-        gx = gx.permute(2, 0, 1)
-    grads = []
-    for pair in dws:
-        grads += [None, None] if pair is None else [pair[0], pair[1]]
-    return gx, grads, False
+        gx = tier.input_grad(gin, h, w, c_in)
+        gx = gx if scale is None else gx * scale
+    return gx, grads
 
 
 def _needs(ctx, first_param):
@@ -499,17 +454,12 @@ class _DecoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, kind, c_out, precision, *params):
-        exact = precision in ("exact", "bf16x2")  # fp32 tensors, split operands: three terms / two terms
-        terms = 2 if precision == "bf16x2" else 3
-        h16 = _F16 if precision == "f16" else _BF16
+        tier = _tier(precision)
         head_out = None
-        if not exact and kind == "scale" and c_out == 3 and x.dim() == 3:
+        if tier.fused and kind == "scale" and c_out == 3 and x.dim() == 3:
             head_out = torch.empty(3, x.shape[1], x.shape[2], device=x.device)  # (used when the fused kernel serves the shape)
-        logits, acts, wb, h, w, c_in = (_chain_forward_exact(x, kind, params, terms) if exact
-                                        else _chain_forward(x, kind, params, h16, head_out=head_out))
-        p = h * w
-        ctx.kind, ctx.c_out, ctx.hw, ctx.c_in, ctx.exact, ctx.terms = kind, c_out, (h, w), c_in, exact, terms
-        ctx.wb, ctx.h16 = wb, h16
+        logits, acts, wb, h, w, c_in = _chain_forward(x, kind, params, tier, head_out)
+        ctx.tier, ctx.kind, ctx.c_out, ctx.hw, ctx.c_in, ctx.wb = tier, kind, c_out, (h, w), c_in, wb
         ctx.shapes = [tuple(t.shape) for t in params[0::2]]
         ctx.from_output = logits is None
         if logits is None:  # the fused scale decoder wrote its softmax head itself; the backward starts from this output
@@ -518,59 +468,34 @@ class _DecoderFn(torch.autograd.Function):
         # CNN_decoder's [C,H,W] output is a permuted view of PIXEL-major memory (like render()'s own output): the head
         # writes rows, the losses read rows, the reference's next step (.permute(1,2,0)) is free.  The 3-channel scale
         # map stays channel-major (its consumers index it by plane).
+        p = h * w
         pm = kind == "decoder" and c_out % 4 == 0 and logits.shape[1] <= 512 and logits.shape[1] % 32 == 0
         out = torch.empty((h, w, c_out) if pm else (c_out, h, w), device=x.device)
         check(_lib.load().gags_decoder_head(p, c_out, logits.shape[1], 0 if kind == "decoder" else 1, ptr(logits), ptr(out),
                                             1 if pm else 0, _st()), "gags_decoder_head")
         if pm:
             out = out.permute(2, 0, 1)
-        ctx.kind, ctx.c_out, ctx.hw, ctx.c_in, ctx.exact, ctx.terms = kind, c_out, (h, w), c_in, exact, terms
-        ctx.wb, ctx.h16 = wb, h16
-        ctx.shapes = [tuple(t.shape) for t in params[0::2]]
         ctx.save_for_backward(logits, *acts)
         return out
 
     @staticmethod
     def backward(ctx, g):
         logits, *acts = ctx.saved_tensors
-        wb, (h, w), kind = ctx.wb, ctx.hw, ctx.kind
+        tier, (h, w), c = ctx.tier, ctx.hw, ctx.c_out
         p = h * w
-        lib = _lib.load()
-        if ctx.from_output:  # `logits` is the softmax output y [3, H, W]: dz = y (g - <y, g>) (gags_softmax_head_bwd_y)
-            y, h16, inv = logits, ctx.h16, None
-            g = g if (g.is_contiguous() and g.dtype == torch.float32) else g.contiguous().float()
-            if h16 is _F16:
-                s, inv = _pow2_scale(torch.linalg.vector_norm(g.reshape(-1), float("inf")))
-                g = g * s
-            dz = torch.empty(p, 32, dtype=h16.dtype, device=g.device)
-            check(h16.fn("gags_softmax_head_bwd_y")(p, ctx.c_out, 32, ptr(y), ptr(g), ptr(dz), _st()), "gags_softmax_head_bwd_y")
-            need_x, need_w = _needs(ctx, 4)
-            gx, grads, done = _chain_backward(dz, acts, wb, kind, h, w, ctx.c_in, ctx.shapes, need_x, need_w, mode=h16, scale=inv)
-            if inv is not None and not done:
-                gx = None if gx is None else gx * inv
-            return (gx, None, None, None, *grads)
         gp = g.permute(1, 2, 0)
-        pm = (g.dtype == torch.float32 and gp.is_contiguous() and not g.is_contiguous() and ctx.c_out % 4 == 0
+        pm = (not ctx.from_output and g.dtype == torch.float32 and gp.is_contiguous() and not g.is_contiguous() and c % 4 == 0
               and logits.shape[1] <= 512)  # the cotangent came back in the output's own pixel-major layout
         g = gp if pm else (g if (g.is_contiguous() and g.dtype == torch.float32) else g.contiguous().float())
-        need_x, need_w = _needs(ctx, 4)
-        mode = 0 if kind == "decoder" else 1
-        if ctx.exact:
-            dz = torch.empty(p, ctx.c_out, device=g.device)
-            check(lib.gags_decoder_head_bwd_exact(p, ctx.c_out, logits.shape[1], mode, ptr(logits), ptr(g), 1 if pm else 0,
-                                                  ptr(dz), ctx.c_out, _st()), "gags_decoder_head_bwd_exact")
-            gx, grads = _chain_backward_exact(dz, acts, wb, kind, h, w, ctx.c_in, ctx.shapes, need_x, need_w, ctx.terms)
+        s, inv = tier.cotangent_scale(g)  # f16: scaled into half's range by a power of two (exact), the results scaled back
+        g = g if s is None else g * s
+        if ctx.from_output:  # `logits` is the softmax output y [3, H, W]: dz = y (g - <y, g>) (gags_softmax_head_bwd_y)
+            dz = torch.empty(p, 32, dtype=tier.dtype, device=g.device)
+            check(tier.fn("gags_softmax_head_bwd_y")(p, c, 32, ptr(logits), ptr(g), ptr(dz), _st()), "gags_softmax_head_bwd_y")
         else:
-            h16, inv = ctx.h16, None
-            if h16 is _F16:  # the cotangent scaled into half's range by a power of two (exact), the results scaled back
-                s, inv = _pow2_scale(torch.linalg.vector_norm(g.reshape(-1), float("inf")))  # (max |g| without an |g| temporary)
-                g = g * s
-            dz = torch.empty(p, logits.shape[1], dtype=h16.dtype, device=g.device)
-            check(h16.fn("gags_decoder_head_bwd")(p, ctx.c_out, logits.shape[1], mode, ptr(logits), ptr(g), ptr(dz),
-                                                  1 if pm else 0, _st()), "gags_decoder_head_bwd")
-            gx, grads, done = _chain_backward(dz, acts, wb, kind, h, w, ctx.c_in, ctx.shapes, need_x, need_w, mode=h16, scale=inv)
-            if inv is not None and not done:  # (the parameter gradients left their sums already multiplied)
-                gx = None if gx is None else gx * inv
+            dz = tier.head_bwd(p, c, 0 if ctx.kind == "decoder" else 1, logits, g, 1 if pm else 0)
+        need_x, need_w = _needs(ctx, 4)
+        gx, grads = _chain_backward(dz, acts, ctx.wb, ctx.kind, h, w, ctx.c_in, ctx.shapes, need_x, need_w, tier, inv)
         return (gx, None, None, None, *grads)
 
 
@@ -582,10 +507,8 @@ class _DecoderDistillFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, img_embed, seg_map, scale_map, c_out, precision, *params):
         from .losses import _f
-        ctx.terms = {"exact": 3, "bf16x2": 2}.get(precision, 0)  # 0: the 16-bit tensor modes
-        ctx.h16 = _F16 if precision == "f16" else _BF16
-        logits, acts, wb, h, w, c_in = (_chain_forward_exact(x, "decoder", params, ctx.terms) if ctx.terms
-                                        else _chain_forward(x, "decoder", params, ctx.h16))
+        tier = _tier(precision)
+        logits, acts, wb, h, w, c_in = _chain_forward(x, "decoder", params, tier)
         e, seg, sc = _f(img_embed), _f(seg_map), _f(scale_map)
         if e.shape[1] != c_out or tuple(sc.shape) != (3, h, w) or seg.dim() != 3 or seg.shape[0] != 4:
             raise ValueError(f"embeddings {tuple(e.shape)}, seg_map {tuple(seg.shape)}, scale_map {tuple(sc.shape)} "
@@ -595,7 +518,7 @@ class _DecoderDistillFn(torch.autograd.Function):
         check(_lib.load().gags_decoder_head_distill_fwd(c_out, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0],
                                                         ptr(logits), ptr(e), ptr(seg), ptr(sc), ptr(l1), ptr(mask), _st()),
               "gags_decoder_head_distill_fwd")
-        ctx.c_out, ctx.hw, ctx.c_in, ctx.wb = c_out, (h, w), c_in, wb
+        ctx.tier, ctx.c_out, ctx.hw, ctx.c_in, ctx.wb = tier, c_out, (h, w), c_in, wb
         ctx.shapes = [tuple(t.shape) for t in params[0::2]]
         ctx.save_for_backward(logits, e, seg, sc, *acts)
         ctx.mark_non_differentiable(mask)
@@ -605,33 +528,19 @@ class _DecoderDistillFn(torch.autograd.Function):
     def backward(ctx, v_map, _v_mask):
         from .losses import _f
         logits, e, seg, sc, *acts = ctx.saved_tensors
-        (h, w), c = ctx.hw, ctx.c_out
+        tier, (h, w), c = ctx.tier, ctx.hw, ctx.c_out
+        vm = _f(v_map)
         vs = torch.empty(3, h, w, device=logits.device)
+        # the logits' gradient in the tier's type (fp32 in the fp32-tensor tiers).  f16: it is about v_map / (c |logits|),
+        # so the kernel multiplies it by a power of two chosen on the device from max |v_map| / c (half has 5 exponent
+        # bits), the chain's results are scaled back; the scale map's gradient is fp32
+        s, inv = tier.cotangent_scale(vm, div=c)
+        dz = torch.empty(h * w, logits.shape[1], dtype=tier.dtype, device=logits.device)
+        check(getattr(_lib.load(), tier.distill_bwd)(c, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0], ptr(logits),
+                                                     ptr(e), ptr(seg), ptr(sc), ptr(vm), ptr(dz), *([] if s is None else [ptr(s)]),
+                                                     ptr(vs), _st()), tier.distill_bwd)
         need_x, need_w = _needs(ctx, 6)
-        if ctx.terms:  # fp32-tensor tiers: the logits' gradient stays fp32
-            dz = torch.empty(h * w, logits.shape[1], device=logits.device)
-            check(_lib.load().gags_decoder_head_distill_bwd_f32(c, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0],
-                                                                ptr(logits), ptr(e), ptr(seg), ptr(sc), ptr(_f(v_map)), ptr(dz),
-                                                                ptr(vs), _st()), "gags_decoder_head_distill_bwd_f32")
-            gx, grads = _chain_backward_exact(dz, acts, ctx.wb, "decoder", h, w, ctx.c_in, ctx.shapes, need_x, need_w, ctx.terms)
-        elif ctx.h16 is _F16:
-            # the logits' gradient is about v_map / (c |logits|): scaled by a power of two chosen on the device from
-            # max |v_map| / c (half has 5 exponent bits), the chain's results scaled back; the scale map's gradient is fp32
-            vm = _f(v_map)
-            s, inv = _pow2_scale(torch.linalg.vector_norm(vm.reshape(-1), float("inf")), div=c)
-            dz = torch.empty(h * w, logits.shape[1], dtype=torch.float16, device=logits.device)
-            check(_lib.load().gags_decoder_head_distill_bwd_h16(c, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0],
-                                                                ptr(logits), ptr(e), ptr(seg), ptr(sc), ptr(vm), ptr(dz), ptr(s),
-                                                                ptr(vs), _st()), "gags_decoder_head_distill_bwd_h16")
-            gx, grads, done = _chain_backward(dz, acts, ctx.wb, "decoder", h, w, ctx.c_in, ctx.shapes, need_x, need_w, mode=_F16,
-                                              scale=inv)
-            gx = gx if (gx is None or done) else gx * inv
-        else:
-            dz = torch.empty(h * w, logits.shape[1], dtype=torch.bfloat16, device=logits.device)
-            check(_lib.load().gags_decoder_head_distill_bwd(c, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0],
-                                                            ptr(logits), ptr(e), ptr(seg), ptr(sc), ptr(_f(v_map)), ptr(dz), ptr(vs),
-                                                            _st()), "gags_decoder_head_distill_bwd")
-            gx, grads, _ = _chain_backward(dz, acts, ctx.wb, "decoder", h, w, ctx.c_in, ctx.shapes, need_x, need_w)
+        gx, grads = _chain_backward(dz, acts, ctx.wb, "decoder", h, w, ctx.c_in, ctx.shapes, need_x, need_w, tier, inv)
         return (gx, None, None, vs, None, None, *grads)
 
 
@@ -642,10 +551,7 @@ class _Stack(nn.Module):
 
     def __init__(self, dims_in, dims_out, precision="exact"):
         super().__init__()
-        if precision not in ("exact", "bf16x2", "f16", "bf16"):
-            raise ValueError("precision must be 'exact' (fp32-equivalent, the default), 'bf16x2' (two-term split: 16 significand "
-                             "bits, tighter than the TF32 the reference's convs run in), 'f16' (IEEE half operands: TF32's own "
-                             "11-bit significand, fp32 accumulation, power-of-two gradient scaling) or 'bf16' (8 bits, fast opt-in)")
+        _tier(precision)
         self.precision = precision
         layers = []
         for i, (ci, co) in enumerate(zip(dims_in, dims_out)):

@@ -101,6 +101,23 @@ def test_frozen_activations_are_cached_and_invalidated():
     assert torch.allclose(m.get_rotation.norm(dim=1), torch.ones(n))
 
 
+def test_unknown_decoder_precision_is_refused_before_any_launch():
+    """`precision` may be changed after construction: both decoder Functions refuse a value that names no tier (with the
+    constructor's message) before anything reaches the library, instead of running it in bf16."""
+    import pytest
+    from gags_amd import decoders as D
+    with pytest.raises(ValueError, match="precision must be"):
+        D.CNN_decoder(16, 512, "fp8")
+    dec = D.CNN_decoder(16, 512, "bf16")
+    dec.precision = "fp8"
+    params = [t for m in dec.convs() for t in (m.weight, m.bias)]
+    x = torch.zeros(16, 2, 3)
+    with pytest.raises(ValueError, match="precision must be"):
+        D._DecoderFn.apply(x, dec.kind, dec.output_dim, dec.precision, *params)
+    with pytest.raises(ValueError, match="precision must be"):
+        D._DecoderDistillFn.apply(x, torch.zeros(5, 512), torch.zeros(4, 2, 3), torch.zeros(3, 2, 3), 512, dec.precision, *params)
+
+
 def test_bench_dump_keeps_small_arrays_whole_and_samples_the_same_rows_of_large_ones(tmp_path, monkeypatch):
     """bench.py --dump-outputs: float32 files (row sums float64); an array above its cap is written as a seeded sample of its
     rows, in their order, the same on every call."""

@@ -17,7 +17,7 @@ H, W = 1080, 1920
 dec = D.CNN_decoder(16, 512, "f16").to(dev)
 params = [t for cv in dec.convs() for t in (cv.weight, cv.bias)]
 x = torch.randn(H, W, 16, device=dev).permute(2, 0, 1)
-mode = D._F16
+tier = D._F16
 
 
 def timed(fn, n=6):
@@ -33,9 +33,9 @@ def timed(fn, n=6):
     return e0.elapsed_time(e1) / n
 
 
-logits, acts, wb, h, w, c_in = D._chain_forward(x, "decoder", params, mode)
-fwd = timed(lambda: D._chain_forward(x, "decoder", params, mode))
+logits, acts, wb, h, w, c_in = D._chain_forward(x, "decoder", params, tier)
+fwd = timed(lambda: D._chain_forward(x, "decoder", params, tier))
 dz = (torch.randn(H * W, 512, device=dev) * 1e-3).to(torch.float16)
 shapes = [tuple(t.shape) for t in params[0::2]]
-bwd = timed(lambda: D._chain_backward(dz, acts, wb, "decoder", h, w, c_in, shapes, True, [False] * 9, mode=mode))
+bwd = timed(lambda: D._chain_backward(dz, acts, wb, "decoder", h, w, c_in, shapes, True, [False] * 9, tier))
 print(f"{os.path.basename(L.LIB_PATH)}: chain forward {fwd:.3f} ms, input-gradient chain {bwd:.3f} ms")
