@@ -140,6 +140,10 @@ SIGNATURES = {
     "gags_relevancy": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gags_relevancy_activate_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "gags_relevancy_activate": (_i32, [_i32, _i32, _i32, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gags_point_relevancy_mask_scratch_bytes": (_i64, [_i32, _i64]),
+    "gags_point_relevancy_mask": (_i32, [_i32, _i64, _vp, _f32, _vp, _vp, _vp, _i64, _vp]),
+    "gags_point_mask_smooth_scratch_bytes": (_i64, [_i32, _i64]),
+    "gags_point_mask_smooth": (_i32, [_i32, _i64, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

@@ -231,6 +231,14 @@ int gags_sort_pairs_u32(int64_t n, int nbits, const uint32_t *keys_in, const int
     return sort_pairs_t<uint32_t>(n, 0, nbits, keys_in, vals_in, keys_out, vals_out, scratch, scratch_bytes, st);
 }
 
+// internal: 64-bit keys on any bit range, used by the point-cloud neighbour vote (csrc/pointquery.hip)
+int64_t gags_sort_u64_scratch_bytes(int64_t n) { return sort_scratch_bytes_t<uint64_t>(n); }
+int gags_sort_pairs_u64(int64_t n, int first_bit, int nbits, const uint64_t *keys_in, const int32_t *vals_in,
+                        uint64_t *keys_out, int32_t *vals_out, void *scratch, int64_t scratch_bytes, hipStream_t st)
+{
+    return sort_pairs_t<uint64_t>(n, first_bit, nbits, keys_in, vals_in, keys_out, vals_out, scratch, scratch_bytes, st);
+}
+
 extern "C" int64_t gags_sort_scratch_bytes(int64_t n_isects) { return sort_scratch_bytes_t<uint64_t>(n_isects); }
 
 extern "C" int gags_sort_pairs(int64_t n, int tile_bits, int depth_sorted, const int64_t *keys_in,

@@ -1,5 +1,5 @@
 /*
- * gags_next.h -- C ABI of the kernels either side of the rasterizer, same
+ * gags_next.h -- C ABI of the kernels either side of the rasterizer (N5), same
  * library (libgags_hip.so) and conventions as gags_raster.h: extern "C", device pointers, caller-owned memory,
  * `stream` = hipStream_t as void*, return GAGS_OK or a negative GAGS_E* code.  fp32 unless noted.
  *
@@ -277,6 +277,29 @@ int64_t gags_relevancy_activate_scratch_bytes(int n_phrases, int h, int w);
 int gags_relevancy_activate(int n_phrases, int h, int w, const float *valid_map, float thresh, int box, int smooth_scale,
                             float *avg, float *blended, float *output, unsigned char *mask_pred,
                             unsigned char *mask_smooth, float *stats, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---- N5: 3-D open-vocabulary query on the Gaussians (compute_relvancy.py:273-394 `pcd_relvancy`, --pcd_mode) ------- */
+
+/* compute_relvancy.py:363-367 for every phrase k of probs[n_phrases, n, 2] (gags_relevancy's output over the n Gaussians;
+ * column 0 is the relevancy r), in the reference's fp32 order:
+ *   normalized[k, i] = clip(((r_i - min r) / ((max r - min r) + 1e-9)) * 2 - 1, 0, 1)
+ *   mask[k, i]       = normalized[k, i] > rel_thresh                          uint8
+ * min / max stay on the device.  n == 0 or n_phrases == 0: nothing to do.  scratch: the _scratch_bytes() bytes. */
+int64_t gags_point_relevancy_mask_scratch_bytes(int n_phrases, int64_t n);
+int gags_point_relevancy_mask(int n_phrases, int64_t n, const float *probs, float rel_thresh, float *normalized,
+                              unsigned char *mask, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* utils/pcd_utils.py:204-219 smooth_pcd_mask for n_masks masks mask[n_masks, n] (uint8, nonzero = set) over the points
+ * xyz[n, 3] at once.  For every mask k and point i:
+ *   c = #{ j : mask[k, j] and ((dx*dx + dy*dy) + dz*dz) <= radius*radius }   in IEEE float64 from the float32
+ *       coordinates, no FMA (the point itself included: scipy's KDTree.query_ball_point rule)
+ *   out[k, i] = c > threshold || (mask[k, i] && c >= 10)                      (10 is the reference's own constant)
+ * counts[k, i] = min(c, max(threshold + 1, 10)) when counts is not NULL (no count is needed past that).  No atomics on the
+ * results: bit-reproducible.  Requires n_masks * n < 2^31, n_masks <= 65534, radius finite and > 0, threshold >= 0.
+ * scratch: the _scratch_bytes() bytes (0 when nothing runs). */
+int64_t gags_point_mask_smooth_scratch_bytes(int n_masks, int64_t n);
+int gags_point_mask_smooth(int n_masks, int64_t n, const float *xyz, const unsigned char *mask, double radius, int threshold,
+                           unsigned char *out, int32_t *counts, void *scratch, int64_t scratch_bytes, void *stream);
 
 
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
