@@ -144,6 +144,9 @@ SIGNATURES = {
     "gags_point_relevancy_mask": (_i32, [_i32, _i64, _vp, _f32, _vp, _vp, _vp, _i64, _vp]),
     "gags_point_mask_smooth_scratch_bytes": (_i64, [_i32, _i64]),
     "gags_point_mask_smooth": (_i32, [_i32, _i64, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "gags_depthsample_scratch_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "gags_depthsample_map": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gags_depthsample_scatter": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

@@ -1,0 +1,224 @@
+// N6 (include/gags_next.h): depth_SAM.py -- the point-to-pixel min-depth mapping of the GAS stage -- on the GPU.
+//
+// For every Gaussian centre and every training camera one decision (ds_decide, steps 1-5 of the rule in gags_next.h, all
+// fp32 with no FMA and IEEE division): project, round half to even, keep what lands inside the image and agrees with the
+// rendered depth there.  Every kernel calls that one function, so a decision is bit-identical wherever it is made.
+//
+// (a) map pass: one thread per point, the cameras in chunks whose depth maps fit the 256 MiB Infinity Cache together (16
+//     maps at 1080p); the thread keeps the running min of the rendered depth D_c[v, u] over the cameras that see it in a
+//     register and writes min_depth once per chunk (a read-modify-write by the owning thread: no atomics).  Optionally the
+//     dense mapping [N, C, 2] (v, u) and visible [N, C] that preprocess.py --pcd_mindepth_mode reads.
+// (b) scatter pass: one thread per (point, camera) of a chunk re-derives the decision and takes the integer max of its
+//     point index into the camera's winner map (scratch, -1 = none); a per-pixel finalise writes
+//     samples = winner >= 0 ? min_depth[winner] : 0.  The max is order-independent: bit-reproducible, and the highest
+//     point index wins a pixel several points land on (the reference's single-threaded index_put_).
+// Offsets into the dense outputs and the [C, H, W] maps are 64-bit.  Every depth read and every map write sits behind
+// the inside test of ds_decide.
+#include <algorithm>
+#include <cmath>
+#include "common.h"
+#include "gags_next.h"
+
+namespace {
+
+constexpr int CAM_FLOATS = 16;                      // rows 0..2 of the world-to-camera matrix, fx, fy, cx, cy
+constexpr int MAX_CHUNK = 64;                       // cameras per launch (LDS: 64 x 64 B)
+constexpr int64_t CACHE_BUDGET = 128ll << 20;       // depth maps (and winner maps) per chunk: 16 at 1920 x 1080
+
+struct Pix {
+    int v, u;
+    float d;  // D_c[v, u]
+};
+
+// Steps 1-5 of the rule: true when the point is inside and agrees with the rendered depth; then p holds (v, u) and the
+// depth read there.  No depth is read unless the pixel is inside.
+__device__ __forceinline__ bool ds_decide(const float *__restrict__ cam, float x, float y, float z, int w, int h, float cut,
+                                          float vis_thresh, const float *__restrict__ depth, Pix &p)
+{
+    float xc = cam[0] * x;
+    xc = xc + cam[1] * y;
+    xc = xc + cam[2] * z;
+    xc = xc + cam[3];
+    float yc = cam[4] * x;
+    yc = yc + cam[5] * y;
+    yc = yc + cam[6] * z;
+    yc = yc + cam[7];
+    float zc = cam[8] * x;
+    zc = zc + cam[9] * y;
+    zc = zc + cam[10] * z;
+    zc = zc + cam[11];
+    float u = xc * cam[12];
+    u = u / zc;
+    u = u + cam[14];
+    float v = yc * cam[13];
+    v = v / zc;
+    v = v + cam[15];
+    const float ur = __builtin_rintf(u), vr = __builtin_rintf(v);  // half to even (torch.round)
+    // in float, before any conversion: NaN fails every comparison, and so does anything past the int32 range
+    const bool inside = ur >= cut && ur < (float)w - cut && vr >= cut && vr < (float)h - cut;
+    if (!inside) return false;
+    p.u = (int)ur;
+    p.v = (int)vr;
+    p.d = depth[(int64_t)p.v * w + p.u];
+    return fabsf(p.d - zc) <= vis_thresh * p.d;
+}
+
+// cam[c] = {M[0, 0..3], M[1, 0..3], M[2, 0..3], fx, fy, cx, cy} from viewmats [C, 4, 4] and Ks [C, 3, 3]
+__global__ void pack_cams_kernel(int n_cams, const float *__restrict__ viewmats, const float *__restrict__ Ks,
+                                 float *__restrict__ cams)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= n_cams) return;
+    float *o = cams + (int64_t)c * CAM_FLOATS;
+    for (int k = 0; k < 12; ++k) o[k] = viewmats[(int64_t)c * 16 + k];
+    const float *K = Ks + (int64_t)c * 9;
+    o[12] = K[0];
+    o[13] = K[4];
+    o[14] = K[2];
+    o[15] = K[5];
+}
+
+__global__ __launch_bounds__(256) void map_kernel(int64_t n, int n_cams, int c0, int nc, int w, int h, float cut,
+                                                  float vis_thresh, const float *__restrict__ xyz,
+                                                  const float *__restrict__ cams, const float *__restrict__ depths,
+                                                  float *__restrict__ min_depth, int2 *__restrict__ mapping,
+                                                  unsigned char *__restrict__ visible)
+{
+    __shared__ float lcam[MAX_CHUNK * CAM_FLOATS];
+    for (int k = threadIdx.x; k < nc * CAM_FLOATS; k += 256) lcam[k] = cams[(int64_t)c0 * CAM_FLOATS + k];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[i * 3 + 0], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
+    const int64_t hw = (int64_t)h * w;
+    float m = c0 == 0 ? INFINITY : min_depth[i];
+    for (int cc = 0; cc < nc; ++cc) {
+        const int64_t c = c0 + cc;
+        Pix p;
+        const bool vis = ds_decide(lcam + cc * CAM_FLOATS, x, y, z, w, h, cut, vis_thresh, depths + c * hw, p);
+        if (vis) m = p.d < m ? p.d : m;
+        if (mapping) mapping[i * n_cams + c] = vis ? make_int2(p.v, p.u) : make_int2(0, 0);
+        if (visible) visible[i * n_cams + c] = vis ? 1 : 0;
+    }
+    min_depth[i] = m;
+}
+
+// winner[cc][v, u] = max point index that camera c0 + cc sees at (v, u); blockIdx.y = cc
+__global__ __launch_bounds__(256) void scatter_kernel(int64_t n, int c0, int w, int h, float cut, float vis_thresh,
+                                                      const float *__restrict__ xyz, const float *__restrict__ cams,
+                                                      const float *__restrict__ depths, int *__restrict__ winner)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int cc = blockIdx.y;
+    const int64_t c = c0 + cc, hw = (int64_t)h * w;
+    Pix p;
+    if (ds_decide(cams + c * CAM_FLOATS, xyz[i * 3 + 0], xyz[i * 3 + 1], xyz[i * 3 + 2], w, h, cut, vis_thresh,
+                  depths + c * hw, p))
+        atomicMax(winner + cc * hw + (int64_t)p.v * w + p.u, (int)i);
+}
+
+__global__ __launch_bounds__(256) void finalise_kernel(int c0, int64_t hw, const int *__restrict__ winner,
+                                                       const float *__restrict__ min_depth, float *__restrict__ samples)
+{
+    const int64_t px = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (px >= hw) return;
+    const int cc = blockIdx.y;
+    const int wi = winner[cc * hw + px];
+    samples[(c0 + cc) * hw + px] = wi >= 0 ? min_depth[wi] : 0.f;
+}
+
+inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
+
+// cameras per launch: their depth maps (and the scatter's winner maps) within CACHE_BUDGET, at least 1
+inline int chunk_cams(int n_cams, int h, int w)
+{
+    const int64_t per = (int64_t)h * w * 4;
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_cams, (int64_t)MAX_CHUNK, CACHE_BUDGET / per}));
+}
+
+bool bad_sizes(int64_t n, int n_cams, int h, int w, int cut_bound)
+{
+    // h, w < 2^24: exact as floats, so the inside test in float bounds every index
+    return n < 0 || n >= INT32_MAX || n_cams < 1 || h < 1 || w < 1 || h >= (1 << 24) || w >= (1 << 24) ||
+           (int64_t)h * w > INT32_MAX || cut_bound < 0;
+}
+
+struct Layout {
+    int64_t cams, winner, total;
+};
+
+Layout layout(int n_cams, int h, int w)
+{
+    Layout L;
+    L.cams = 0;
+    L.winner = al256((int64_t)n_cams * CAM_FLOATS * 4);
+    L.total = L.winner + al256((int64_t)chunk_cams(n_cams, h, w) * h * w * 4);
+    return L;
+}
+
+}  // namespace
+
+extern "C" int64_t gags_depthsample_scratch_bytes(int64_t n, int n_cams, int h, int w)
+{
+    if (bad_sizes(n, n_cams, h, w, 0) || n == 0) return 0;
+    return layout(n_cams, h, w).total;
+}
+
+extern "C" int gags_depthsample_map(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats,
+                                    const float *Ks, const float *depths, float vis_thresh, int cut_bound,
+                                    float *min_depth, int32_t *mapping, unsigned char *visible, void *scratch,
+                                    int64_t scratch_bytes, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (bad_sizes(n, n_cams, h, w, cut_bound)) return GAGS_EINVAL;
+    if (n == 0) return GAGS_OK;
+    if (!xyz || !viewmats || !Ks || !depths || !min_depth || !scratch) return GAGS_EINVAL;
+    const Layout L = layout(n_cams, h, w);
+    if (scratch_bytes < L.total) return GAGS_ESCRATCH;
+    hipStream_t st = (hipStream_t)stream;
+    float *cams = (float *)((char *)scratch + L.cams);
+    hipLaunchKernelGGL(pack_cams_kernel, dim3((n_cams + 63) / 64), dim3(64), 0, st, n_cams, viewmats, Ks, cams);
+    const int chunk = chunk_cams(n_cams, h, w);
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    for (int c0 = 0; c0 < n_cams; c0 += chunk) {
+        const int nc = std::min(chunk, n_cams - c0);
+        hipLaunchKernelGGL(map_kernel, dim3(nb), dim3(256), 0, st, n, n_cams, c0, nc, w, h, (float)cut_bound, vis_thresh,
+                           xyz, cams, depths, min_depth, (int2 *)mapping, visible);
+    }
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}
+
+extern "C" int gags_depthsample_scatter(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats,
+                                        const float *Ks, const float *depths, float vis_thresh, int cut_bound,
+                                        const float *min_depth, float *samples, void *scratch, int64_t scratch_bytes,
+                                        void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (bad_sizes(n, n_cams, h, w, cut_bound)) return GAGS_EINVAL;
+    if (!samples) return GAGS_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t hw = (int64_t)h * w;
+    if (n == 0) {  // no point: every map is zero
+        if (hipMemsetAsync(samples, 0, (size_t)(n_cams * hw * 4), st) != hipSuccess) return GAGS_ELAUNCH;
+        return GAGS_OK;
+    }
+    if (!xyz || !viewmats || !Ks || !depths || !min_depth || !scratch) return GAGS_EINVAL;
+    const Layout L = layout(n_cams, h, w);
+    if (scratch_bytes < L.total) return GAGS_ESCRATCH;
+    float *cams = (float *)((char *)scratch + L.cams);
+    int *winner = (int *)((char *)scratch + L.winner);
+    hipLaunchKernelGGL(pack_cams_kernel, dim3((n_cams + 63) / 64), dim3(64), 0, st, n_cams, viewmats, Ks, cams);
+    const int chunk = chunk_cams(n_cams, h, w);
+    const unsigned nb = (unsigned)((n + 255) / 256), nbp = (unsigned)((hw + 255) / 256);
+    for (int c0 = 0; c0 < n_cams; c0 += chunk) {
+        const int nc = std::min(chunk, n_cams - c0);
+        if (hipMemsetAsync(winner, 0xff, (size_t)(nc * hw * 4), st) != hipSuccess) return GAGS_ELAUNCH;
+        hipLaunchKernelGGL(scatter_kernel, dim3(nb, nc), dim3(256), 0, st, n, c0, w, h, (float)cut_bound, vis_thresh, xyz,
+                           cams, depths, winner);
+        hipLaunchKernelGGL(finalise_kernel, dim3(nbp, nc), dim3(256), 0, st, c0, hw, winner, min_depth, samples);
+    }
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}

@@ -302,6 +302,31 @@ int gags_point_mask_smooth(int n_masks, int64_t n, const float *xyz, const unsig
                            unsigned char *out, int32_t *counts, void *scratch, int64_t scratch_bytes, void *stream);
 
 
+/* ---- N6: depth_SAM.py, the point-to-pixel min-depth mapping of the GAS stage ---------------------------------------------
+ * n points xyz[n, 3], n_cams cameras: viewmats[C, 4, 4] row-major world-to-camera (world_view_transform.T), Ks[C, 3, 3]
+ * ([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), rendered depths[C, h, w] (channel 3 of render(..., render_mode="RGB+ED")).  For
+ * point i and camera c, all fp32, no FMA, IEEE division (depth_SAM.py:34-77 compute_mapping):
+ *   1. (xc, yc, zc) = rows 0..2 of M (x, y, z, 1) as ((M[r,0] x + M[r,1] y) + M[r,2] z) + M[r,3]
+ *   2. u = (xc fx) / zc + cx,  v = (yc fy) / zc + cy
+ *   3. ui = rint(u), vi = rint(v), half to even (torch.round)
+ *   4. inside <=> cut_bound <= ui < w - cut_bound and cut_bound <= vi < h - cut_bound, compared in float (NaN, +-inf and
+ *      anything past the int32 range are outside)
+ *   5. d = depths[c, vi, ui]; visible <=> inside and |d - zc| <= vis_thresh d
+ * mapping[i, c] = (vi, ui), visible[i, c] = 1 when visible, else (0, 0) and 0;  min_depth[i] = min over the cameras that see
+ * i of d (+inf when none);  samples[c, v, u] = min_depth[j] for the HIGHEST index j visible in c at (v, u), else 0.
+ * Requires n < 2^31 - 1, n_cams >= 1, 1 <= h, w < 2^24, h w < 2^31, cut_bound >= 0; offsets into the outputs are 64-bit.  Bit-
+ * reproducible (the scatter's only atomic is an integer max of the point index).  scratch: the _scratch_bytes() bytes,
+ * 0 when n == 0. */
+int64_t gags_depthsample_scratch_bytes(int64_t n, int n_cams, int h, int w);
+/* min_depth[n]; mapping[n, n_cams, 2] int32 and visible[n, n_cams] uint8 are optional (NULL: not written) */
+int gags_depthsample_map(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats, const float *Ks,
+                         const float *depths, float vis_thresh, int cut_bound, float *min_depth, int32_t *mapping,
+                         unsigned char *visible, void *scratch, int64_t scratch_bytes, void *stream);
+/* samples[n_cams, h, w] from min_depth[n] (gags_depthsample_map's, same arguments); n == 0: all zero */
+int gags_depthsample_scatter(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats, const float *Ks,
+                             const float *depths, float vis_thresh, int cut_bound, const float *min_depth, float *samples,
+                             void *scratch, int64_t scratch_bytes, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
