@@ -97,6 +97,12 @@ def reduce_feature_grad(grad, mode="rs_ag", average=False, bucket_bytes=BUCKET_B
         raise ValueError(mode)
     if average:
         flat.div_(ws)
+    # c10d collectives write their tensors without moving torch's version counter (all_reduce, reduce_scatter_tensor into
+    # a slice under GAGS_DIST_INPLACE=1; all_gather_into_tensor and copy_ happen to move it).  `grad` now holds other ranks'
+    # rows: whoever trusts "unchanged since I handed it out" on the counter -- the persistent gradient buffer of the staged
+    # backward (rasterization._KeptGrad), OverlappedGradReducer's adoption check -- is told here, whatever the branch above
+    from .rasterization import grad_written
+    grad_written(grad)
     return grad
 
 
@@ -519,6 +525,9 @@ class OverlappedGradReducer:
         elif ws > 1 and not self.loopback:
             if cuda:
                 torch.cuda.current_stream().wait_stream(self.comm)
+            # (the plain in-place reduction: reduce_feature_grad marks the gradient as written -- grad_written().  The
+            # branches above are the designed exception: under the wire hook the reduce kernel flags the exchanged rows itself,
+            # _unpack_rows writes only those, and the all-rows fallback has called forget_all_kept())
             reduce_feature_grad(param_grad, mode=self.mode, bucket_bytes=self.bucket_bytes)
         if cuda:
             torch.cuda.current_stream().wait_stream(self.comm)

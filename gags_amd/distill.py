@@ -31,7 +31,9 @@ def distillation_loss(feature_map, seg_map, img_embed, cnn_decoder, cnn_scale_de
     terms = {"l1", "ce", "regionvar" (None before scale_regulation_iteration), "scale_map", "seg_map_trained"}.
     fused_head: None = use CNN_decoder.distill_l1 (head fused into the loss) whenever the decoder offers it."""
     scale_map = cnn_scale_decoder(feature_map.detach())                                  # train.py:149
-    seg_map_trained = L.get_trained_seg(seg_map, scale_map)                              # :152
+    # (the ids of seg_map index img_embed: its row count bounds them whatever was written into the map since the last
+    # iteration, by whatever route -- no readback, nothing remembered per tensor)
+    seg_map_trained = L.get_trained_seg(seg_map, scale_map, n_seg=img_embed.shape[0])    # :152
     late = iteration >= scale_regulation_iteration
     regionvar = None
     if late:                                                                             # :153

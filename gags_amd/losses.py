@@ -45,7 +45,12 @@ def _n_seg(seg_map):
     readback per segmentation map, not one per iteration (a host sync in the middle of an iteration drains the queue: the
     dozens of small launches behind it then run at the host's pace -- ~0.5 ms each time at 1080p): a view's SAM map does not
     change between iterations, so the answer is kept per tensor (identity, address and version counter), and
-    get_trained_seg hands the bound of its source map on to the map it makes (`_gags_n_seg`)."""
+    get_trained_seg hands the bound of its source map on to the map it makes (`_gags_n_seg`).
+    The version counter only sees torch's own in-place operators: a map refilled through raw pointers (a kernel, DLPack, a
+    c10d collective) keeps the old bound, and ids above it are skipped.  The composed iteration does not depend on that:
+    distill.distillation_loss passes the bound it knows without looking at the data (the embedding table's row count) to
+    get_trained_seg(n_seg=...), no readback at all; a caller of the single losses who refills a map that way calls
+    forget_n_seg()."""
     hint = getattr(seg_map, "_gags_n_seg", None)
     if hint is not None:
         return hint
@@ -58,6 +63,14 @@ def _n_seg(seg_map):
         _NSEG_CACHE.clear()
     _NSEG_CACHE[key] = (weakref.ref(seg_map), seg_map.data_ptr(), seg_map._version, n)
     return n
+
+
+def forget_n_seg(seg_map=None):
+    """Drop the remembered bound of `seg_map` (None: of every map): the next loss on it reads the bound back again."""
+    if seg_map is None:
+        _NSEG_CACHE.clear()
+    else:
+        _NSEG_CACHE.pop(id(seg_map), None)
 
 
 def l1_loss(network_output, gt):
@@ -237,13 +250,15 @@ def scale_region_regulation_loss(scale_map, seg_map, scale_bal_idx=1, mix_seg=Fa
     return _RegionVar.apply(scale_map, seg_map)
 
 
-def get_trained_seg(seg_map, scale_map):
-    """seg_map [4,H,W], scale_map [3,H,W] -> [H,W]: the segment id of the level the 5x5-smoothed scale map prefers."""
+def get_trained_seg(seg_map, scale_map, n_seg=None):
+    """seg_map [4,H,W], scale_map [3,H,W] -> [H,W]: the segment id of the level the 5x5-smoothed scale map prefers.
+    n_seg: a bound above every id of seg_map that the caller KNOWS (the ids index the view's embedding table: its row count),
+    handed on to the losses that read the result; None: _n_seg's readback, remembered per tensor."""
     seg, sc = _f(seg_map), _f(scale_map.detach())
     _, h, w = seg.shape
     out = torch.empty(h, w, device=seg.device)
     check(_lib.load().gags_trained_seg(h, w, ptr(seg), ptr(sc), ptr(out), _st()), "gags_trained_seg")
-    out._gags_n_seg = _n_seg(seg_map)  # (every id of the result is an id of seg_map)
+    out._gags_n_seg = _n_seg(seg_map) if n_seg is None else max(int(n_seg), 1)  # (every id of the result is an id of seg_map)
     return out
 
 

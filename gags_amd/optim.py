@@ -51,4 +51,7 @@ class FeatureAdam(torch.optim.Optimizer):
                                                   _lib.ptr(st["exp_avg_sq"]), float(group["lr"]), float(b1), float(b2),
                                                   float(group["eps"]), int(st["step"].item()), stream),
                                "gags_adam_step")
+                # the kernel wrote `p` through its raw pointer: move the version counter as torch's own optimizers do, for
+                # everything keyed on it (decoders._pack_weights' cache of packed weights, autograd's saved-tensor checks)
+                torch.autograd.graph.increment_version(p)
         return loss

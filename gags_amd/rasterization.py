@@ -139,6 +139,12 @@ class RasterContext:
         if self._kept_fails.get(key, 0) >= 3:
             return None
         ent = self._kept.pop(key, None)
+        if ent is not None and ent.released() and not ent.untouched():
+            # written since it was handed out (an in-place collective, an optimizer's clipping, grad_written()) and released
+            # again: its rows are no longer "zero except last step's", but nobody else holds the storage -- start over from a
+            # clean buffer (one fill, what a fresh torch.zeros would cost, without the allocation) and do not count the step
+            # towards the switch-off: a loop that reduces its gradient in place every step keeps the one buffer
+            ent.wipe()
         if ent is not None and not ent.untouched():
             self._kept_fails[key] = self._kept_fails.get(key, 0) + 1  # the holder keeps that storage; a new one below
             ent = None
@@ -184,6 +190,17 @@ class RasterContext:
         return self._pinned[key]
 
 
+def grad_written(grad):
+    """Tell the library that `grad` -- a gradient this package's backward produced, e.g. `pc._semantic_feature.grad` -- was
+    written by something torch's version counter does not see: a c10d collective (`dist.all_reduce(p.grad)` leaves
+    `_version` alone), a DLPack consumer, a kernel launched on its data_ptr().  The persistent gradient buffer
+    (_KeptGrad) then starts the next step from zeros instead of trusting that only last step's flagged rows are non-zero.
+    Every writer inside this package calls it itself (gags_amd/dist.py: reduce_feature_grad); torch's own in-place operators
+    need nothing.  Returns `grad`.  (memory model; GAGS_KEEP_GRAD=0 turns the buffer off altogether.)"""
+    torch.autograd.graph.increment_version(grad)
+    return grad
+
+
 _TLS = threading.local()
 
 
@@ -212,9 +229,13 @@ class _KeptGrad:
     reduce stage only writes the rows that have partial rows now and re-zeroes the rows that had some in the previous step
     (two flag arrays, gags_raster_bwd_colors_staged_keep).  The buffer is only reused when NOBODY else still refers to its
     storage (reference count back at its baseline: the previous step's .grad was released, e.g. zero_grad(set_to_none=True)
-    or `.grad = None`) and nobody wrote to it in place through torch (version counter unchanged; the kernels write through raw
-    pointers and never bump it).  Otherwise the holder keeps the old storage and this step runs on a new buffer; after three
-    such steps in a row the mechanism switches itself off for the shape (a loop that accumulates into a live .grad)."""
+    or `.grad = None`) and nobody wrote to it in place (version counter unchanged: torch's in-place operators move it, this
+    package's own writers of a gradient -- dist.reduce_feature_grad -- move it through grad_written(), and a caller whose own
+    collective or kernel writes a gradient must call grad_written() too: c10d collectives and raw pointers leave the counter
+    alone; the staged backward's kernels are the one writer that does not, on purpose).  A buffer that was written and then
+    released is wiped and used again; one that is still held stays with its holder and this step runs on a new buffer, and
+    after three such steps in a row the mechanism switches itself off for the shape (a loop that accumulates into a live
+    .grad)."""
 
     def __init__(self, n, d, dtype, dev):
         self.buf = torch.zeros(n, d, dtype=dtype, device=dev)
@@ -223,8 +244,17 @@ class _KeptGrad:
         self.base = _storage_refs(self.buf)
         self.version = self.buf._version
 
+    def released(self):
+        return _storage_refs(self.buf) <= self.base
+
     def untouched(self):
-        return _storage_refs(self.buf) <= self.base and self.buf._version == self.version
+        return self.released() and self.buf._version == self.version
+
+    def wipe(self):
+        """Back to the state of a new buffer, in place (only when released(): nobody else reads this storage)."""
+        self.buf.zero_()
+        self.flags.zero_()
+        self.version = self.buf._version
 
     def hand_out(self):
         prev, cur = self.flags[self.cur], self.flags[1 - self.cur]
@@ -572,6 +602,14 @@ class _Rasterize(torch.autograd.Function):
             try:
                 scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             except torch.OutOfMemoryError:
+                # the kept gradient buffers (_KeptGrad: up to KEEP_GRAD_SHAPES x [N, D]) are the memory this context can give
+                # back: released, then one more attempt
+                (rctx if rctx is not None else default_context()).forget_all_kept()
+                try:
+                    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                except torch.OutOfMemoryError:
+                    scratch = None
+            if scratch is None:
                 # slot space (1 KB per intersection) does not fit even after the caching allocator gave its blocks
                 # back: scratch-free kernels, which read an fp32 table only.  Said out loud: they are several times slower
                 # (single-kernel forward, atomic backward) and the caller should know why
@@ -756,11 +794,13 @@ class _EarlyRowmap:
         return self._rows
 
     def __del__(self):
-        # a forward that was never differentiated: its pinned word goes back to the pool (a later user's copy is enqueued behind
-        # this one's on the same stream, and is read behind its own event)
+        # a forward that was never differentiated: its pinned word goes back to the pool only when the copy into it has
+        # landed (the event has completed).  While the copy may still be in flight the word is dropped instead: handed to the
+        # next forward -- possibly on another stream -- it could be overwritten by THIS forward's count after that one's arrived
         try:
             if self.host is not None:
-                self.rctx.give_pinned(self.dev, self.host)
+                if self.ev.query():
+                    self.rctx.give_pinned(self.dev, self.host)
                 self.host = None
         except Exception:
             pass

@@ -351,3 +351,67 @@ def test_geometry_gradients_reduce_as_one_packed_block_two_ranks():
         p.join(timeout=60)
         assert p.exitcode == 0
     assert all(ok for _, ok in res)
+
+
+def _kept_backward(ctx, n, d, rows, values):
+    """What the staged colours-only backward does with the persistent gradient buffer (rasterization._KeptGrad), on the host:
+    the rows this view has are written, the rows flagged by the previous step and absent now are zeroed, no other row is
+    touched, the flags are recorded for the next step -- all through `.data`, as the kernels write through raw pointers."""
+    alias, prev, cur = ctx.kept_grad(n, d, torch.float32, torch.device("cpu"))
+    hit = torch.zeros(n, dtype=torch.bool)
+    hit[rows] = True
+    alias.data[(prev != 0) & ~hit] = 0
+    alias.data[rows] = values
+    cur.data.copy_(hit.to(torch.uint8))
+    return alias
+
+
+def _two_step_worker(rank, world, port, mode, bucket_bytes, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from gags_amd.dist import reduce_feature_grad
+    from gags_amd.rasterization import RasterContext
+    n, d = 1037, 7  # (7259 elements: odd, so the reduce-scatter buckets leave a tail for the plain all-reduce)
+    ctx = RasterContext()
+    assert ctx.keep_grad_buffer
+    ok, ptrs = [], set()
+    for step in range(3):
+        local = []
+        for r in range(world):  # rows and values of every rank's view this step: different rows every step and rank
+            g = torch.Generator().manual_seed(1000 * step + r)
+            rows = torch.randperm(n, generator=g)[:200]
+            local.append((rows, torch.randn(200, d, generator=g)))
+        expect = torch.zeros(n, d)
+        for rows, values in local:
+            expect[rows] += values
+        grad = _kept_backward(ctx, n, d, *local[rank])
+        ptrs.add(grad.data_ptr())
+        reduce_feature_grad(grad, mode=mode, bucket_bytes=bucket_bytes)
+        ok.append(bool(torch.allclose(grad, expect, rtol=1e-6, atol=1e-6)))
+        del grad  # (zero_grad(set_to_none=True): the buffer's only other holder lets go)
+    q.put((rank, ok, len(ptrs), dict(ctx._kept_fails)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("mode,bucket_bytes", [("allreduce", 4096), ("rs_ag", 4096), ("rs_ag", 256 << 20)])
+def test_reduction_into_the_kept_buffer_over_three_steps(mode, bucket_bytes):
+    """reduce_feature_grad writes the other ranks' rows into the very buffer the next backward reuses, and c10d's
+    collectives do not move torch's version counter: the reduction itself must tell the buffer (rasterization.grad_written),
+    or rows of step 1's other rank are summed again in step 2.  Host tensors and a host restatement of the keep kernel's
+    protocol (gloo cannot reduce-scatter device tensors); both bucketed forms of rs_ag and its ragged tail, and allreduce.
+    The buffer stays in use (wiped, not replaced) and no step counts towards the switch-off."""
+    world, port = 2, _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_two_step_worker, args=(r, world, port, mode, bucket_bytes, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=120) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, ok, n_ptrs, fails in res:
+        assert ok == [True, True, True], (rank, ok)
+        assert n_ptrs == 1 and all(v == 0 for v in fails.values()), (rank, n_ptrs, fails)

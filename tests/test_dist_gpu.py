@@ -23,19 +23,24 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _setup():
+# the views of a three-step run: every rank changes its view from step to step (step s, rank r renders STEP_VIEWS[s][r]);
+# the first step is the single-step test's
+STEP_VIEWS = ((2, 3), (5, 0), (7, 2))
+
+
+def _setup(views=STEP_VIEWS[0]):
     from gags_amd import synthetic as syn
     dev = torch.device("cuda", 0)
     pc = syn.make_model(N, D, W, H, seed=3, device=dev, gen_device=dev, scale0=syn.SCALE0 * 6.0)
     pc.training_setup()
-    cams = [syn.make_camera(W, H, view=v + 2, device=dev) for v in range(VIEWS)]
+    cams = [syn.make_camera(W, H, view=v, device=dev) for v in views]
     G = [syn.make_cotangent(D, H, W, seed=10 + v, device=dev) for v in range(VIEWS)]
     return dev, pc, cams, G
 
 
-def _single_process_grad():
+def _single_process_grad(views=STEP_VIEWS[0]):
     from gags_amd.gaussian_renderer import render
-    dev, pc, cams, G = _setup()
+    dev, pc, cams, G = _setup(views)
     bg = torch.zeros(3, device=dev)
     pc._semantic_feature.grad = None
     for v in range(VIEWS):
@@ -43,10 +48,11 @@ def _single_process_grad():
     return pc._semantic_feature.grad.detach().cpu().numpy()
 
 
-def _worker(rank, world, port, mode, out_dir):
+def _worker(rank, world, port, mode, out_dir, steps=1):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    from gags_amd import synthetic as syn
     from gags_amd.dist import channel_shard, distributed_step
     from gags_amd.gaussian_renderer import render
     dev, pc, cams, G = _setup()
@@ -57,21 +63,30 @@ def _worker(rank, world, port, mode, out_dir):
         cots = [g[c0:c1].permute(1, 2, 0).contiguous().permute(2, 0, 1) for g in G]
         distributed_step(render, cams, pc, bg, cots, mode="channel")
     else:
-        distributed_step(render, cams, pc, bg, G, mode="allreduce")  # gloo has no reduce-scatter for GPU tensors
+        for s in range(steps):
+            if s > 0:  # (as zero_grad(set_to_none=True) between steps; the parameters stay: each step stands for itself)
+                pc._semantic_feature.grad = None
+                cams = [syn.make_camera(W, H, view=v, device=dev) for v in STEP_VIEWS[s]]
+            distributed_step(render, cams, pc, bg, G, mode="allreduce")  # gloo has no reduce-scatter for GPU tensors
+            torch.cuda.synchronize()
+            if steps > 1:
+                np.save(os.path.join(out_dir, f"grad_{mode}_{rank}_s{s}.npy"), pc._semantic_feature.grad.detach().cpu().numpy())
     np.save(os.path.join(out_dir, f"grad_{mode}_{rank}.npy"), pc._semantic_feature.grad.detach().cpu().numpy())
     dist.barrier()
     dist.destroy_process_group()
 
 
-def _run(mode, tmp_path):
+def _run(mode, tmp_path, steps=1):
     world, port = 2, _free_port()
     ctx = mp.get_context("spawn")
-    procs = [ctx.Process(target=_worker, args=(r, world, port, mode, str(tmp_path))) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, mode, str(tmp_path), steps)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
         p.join(timeout=300)
         assert p.exitcode == 0
+    if steps > 1:
+        return [[np.load(tmp_path / f"grad_{mode}_{r}_s{s}.npy") for r in range(world)] for s in range(steps)]
     return [np.load(tmp_path / f"grad_{mode}_{r}.npy") for r in range(world)]
 
 
@@ -82,6 +97,21 @@ def test_view_sharded_step_equals_single_process_sum(tmp_path):
     # each view's gradient is bit-reproducible; only the order of the final sum over views may differ
     assert np.linalg.norm(g0.astype(np.float64) - ref) <= 1e-6 * np.linalg.norm(ref)
     assert np.abs(ref).max() > 0
+
+
+def test_view_sharded_steps_with_changing_views_each_equal_the_single_process_sum(tmp_path):
+    """Three steps in one process group, `.grad = None` between them, every rank on another view each step: the in-place
+    all-reduce writes the other rank's rows into the tensor autograd adopted -- the staged backward's persistent buffer --
+    and the next step's backward rewrites or re-zeroes only the rows of ITS OWN last view.  Every step must satisfy the
+    single-step statement: rows of an earlier step's other rank must not be summed again."""
+    per_step = _run("view", tmp_path, steps=len(STEP_VIEWS))
+    for s, (g0, g1) in enumerate(per_step):
+        ref = _single_process_grad(STEP_VIEWS[s])
+        np.testing.assert_array_equal(g0, g1, err_msg=f"step {s}")
+        err = np.linalg.norm(g0.astype(np.float64) - ref)
+        print(f"step {s}: |reduced - single-process sum| = {err:.3e} of {np.linalg.norm(ref):.3e}")
+        assert err <= 1e-6 * np.linalg.norm(ref), (s, err, np.linalg.norm(ref))
+        assert np.abs(ref).max() > 0
 
 
 def test_channel_sharded_step_is_bit_identical_and_exchange_free(tmp_path):
@@ -165,6 +195,85 @@ def test_overlapped_union_row_exchange_with_the_real_backward(tmp_path):
             np.testing.assert_array_equal(np.load(tmp_path / f"{tag}_{r}.npy"), ref)   # two addends per element: exact
         assert used == 1 and rows == union and 0 < union < N
         assert union < padded < N and rows_last == -1   # (the over-capacity step re-sent ALL rows: rows_exchanged is None)
+
+
+ALT_VIEWS = ((2, 3), (6, 0), (2, 3))  # step s, rank r: the camera alternates, so the rows of the union change every step
+
+
+def _overlap_alternating_worker(rank, world, port, out_dir):
+    """_overlap_step_worker with a second camera per rank to alternate with, exact counts (no capacity-sized blocks): three
+    steps through the wire hook -- the reduce kernel flags the exchanged rows of the persistent buffer itself, finish() writes
+    only those -- with the union's rows changing from step to step."""
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from gags_amd import synthetic as syn
+    from gags_amd.dist import OverlappedGradReducer
+    from gags_amd.gaussian_renderer import render
+    dev = torch.device("cuda", 0)
+    d = 256
+    pc = syn.make_model(N, d, W, H, seed=3, device=dev, gen_device=dev, scale0=syn.SCALE0 * 6.0)
+    pc.training_setup()
+    G = syn.make_cotangent(d, H, W, seed=10 + rank, device=dev)
+    bg = torch.zeros(3, device=dev)
+    red = OverlappedGradReducer(mode="allreduce", rows="union")
+    meta = []
+    for s, views in enumerate(ALT_VIEWS):
+        cam = syn.make_camera(W, H, view=views[rank], device=dev)
+        pc._semantic_feature.grad = None
+        loss = (render(cam, pc, None, bg, feature_mode=True)["render"] * G).sum()
+        with red:
+            loss.backward()
+        used = red.finish(pc._semantic_feature.grad)
+        torch.cuda.synchronize()
+        meta += [int(used), int(red.assigned), red.rows_exchanged or -1]
+        np.save(os.path.join(out_dir, f"alt_{s}_{rank}.npy"), pc._semantic_feature.grad.detach().cpu().numpy())
+    np.save(os.path.join(out_dir, f"alt_meta_{rank}.npy"), np.array(meta))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_overlapped_exchange_over_steps_whose_rows_change(tmp_path):
+    """Beside test_overlapped_union_row_exchange_with_the_real_backward (one camera per rank: the rows never change, so rows
+    left over from an earlier step could not show): each rank alternates between two cameras.  Every step's gradient is the
+    exact sum of that step's two views (two addends per element), the union is that step's own, and the exchange ran through
+    the overlapped path with the gradient adopted."""
+    from gags_amd import synthetic as syn
+    from gags_amd.gaussian_renderer import render
+    from gags_amd.rasterization import RasterContext
+    dev = torch.device("cuda", 0)
+    d = 256
+    pc = syn.make_model(N, d, W, H, seed=3, device=dev, gen_device=dev, scale0=syn.SCALE0 * 6.0)
+    pc.training_setup()
+    bg = torch.zeros(3, device=dev)
+    plain = RasterContext()
+    plain.keep_grad_buffer = False
+    refs, unions = [], []
+    for views in ALT_VIEWS:
+        per_view = []
+        for r, v in enumerate(views):
+            pc._semantic_feature.grad = None
+            G = syn.make_cotangent(d, H, W, seed=10 + r, device=dev)
+            (render(syn.make_camera(W, H, view=v, device=dev), pc, None, bg, feature_mode=True, context=plain)["render"] * G).sum().backward()
+            per_view.append(pc._semantic_feature.grad.detach().clone())
+        refs.append((per_view[0] + per_view[1]).cpu().numpy())
+        unions.append(int(((per_view[0] != 0).any(1) | (per_view[1] != 0).any(1)).sum()))
+    pc._semantic_feature.grad = None
+    assert not np.array_equal(refs[0] != 0, refs[1] != 0)  # the steps touch different rows
+    world, port = 2, _free_port()
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_overlap_alternating_worker, args=(r, world, port, str(tmp_path))) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=300)
+        assert p.exitcode == 0
+    for r in range(world):
+        meta = np.load(tmp_path / f"alt_meta_{r}.npy").reshape(len(ALT_VIEWS), 3)
+        for s in range(len(ALT_VIEWS)):
+            np.testing.assert_array_equal(np.load(tmp_path / f"alt_{s}_{r}.npy"), refs[s], err_msg=f"rank {r} step {s}")
+            used, assigned, rows = meta[s]
+            assert used == 1 and assigned == 1 and rows == unions[s] and 0 < unions[s] < N, (r, s, meta[s], unions[s])
 
 
 def _early_unpack_worker(rank, world, port, out_dir):

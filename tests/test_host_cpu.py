@@ -149,3 +149,43 @@ def test_bench_dump_keeps_small_arrays_whole_and_samples_the_same_rows_of_large_
     rows = z[0]["feature_grad"]  # twice the cap: 1200 // 8 = 150 rows
     assert rows.shape == (150, d) and np.all(np.diff(rows[:, 0]) > 0)
     np.testing.assert_array_equal(rows, grad.numpy()[rows[:, 0].astype(np.int64)])
+
+
+def test_an_unused_row_map_recycles_its_pinned_word_only_when_the_copy_has_landed():
+    """rasterization._EarlyRowmap (a forward enqueues the backward's row map and sends its count to a pinned word): a forward
+    that is never differentiated returns the word to the context's pool from __del__ -- but only when the event behind the
+    copy has completed.  A word whose copy may still be in flight is dropped: handed to the next forward it could be
+    overwritten by the older count after the newer one arrived.  rows() waits for the event first and recycles.  Plain Python
+    policy: stub event and tensor objects, no device."""
+    from gags_amd.rasterization import RasterContext, _EarlyRowmap
+
+    class Event:
+        def __init__(self, done):
+            self.done, self.synced = done, 0
+
+        def query(self):
+            return self.done
+
+        def synchronize(self):
+            self.synced += 1
+            self.done = True
+
+    class Dev:
+        index = 0
+
+    ctx = RasterContext()
+    pool = ctx._pinned_pool.setdefault(0, [])
+    landed, in_flight, used = [7], [8], [9]
+    e = _EarlyRowmap(None, None, None, landed, Event(True), ctx, Dev())
+    del e
+    assert pool == [landed]
+    e = _EarlyRowmap(None, None, None, in_flight, Event(False), ctx, Dev())
+    del e
+    assert pool == [landed], "a pinned word was recycled while the copy into it may be in flight"
+    ev = Event(False)
+    e = _EarlyRowmap(None, None, None, used, ev, ctx, Dev())
+    assert e.rows() == 9 and ev.synced == 1 and e.rows() == 9 and ev.synced == 1
+    assert pool == [landed, used]
+    del e
+    assert pool == [landed, used]  # (returned once)
+    assert ctx.take_pinned(Dev()) is used and ctx.take_pinned(Dev()) is landed and pool == []
