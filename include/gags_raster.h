@@ -85,7 +85,10 @@ int gags_project_fwd(int n, const float *means, const float *quats, const float 
                      int32_t *tiles_per_gauss, void *stream);
 
 /* K5: inclusive prefix sum of tiles_per_gauss -> cum[N]; the grand total (n_isects) is
- * also written to total[0], or -1 when it does not fit an int32 (the caller must refuse the view).
+ * also written to total[0], or -1 when it does not fit an int32 (the caller must refuse the view; the entries of cum
+ * behind the wrap are then unspecified).  Every entry must lie in [0, 2^20): the 2048 entries one workgroup sums then fit an
+ * int32, which is what the overflow check builds on (a tile count is at most the grid's: 2^20 tiles is 16 384 x 16 384
+ * pixels).  in == cum is allowed, total may be NULL, n = 0 writes total[0] = 0 and nothing else.
  * scratch: gags_scan_scratch_bytes(n) bytes. */
 int64_t gags_scan_scratch_bytes(int n);
 int gags_cumsum_i32(int n, const int32_t *in, int32_t *cum, int32_t *total,
