@@ -57,15 +57,7 @@ SIGNATURES = {
     "gags_blended_mask": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "gags_bwd_staged_scratch_bytes": (_i64, [_i64, _i32, _i32]),
     "gags_raster_bwd_colors_staged": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                             _i64, _vp, _i32, _vp]),
-    "gags_raster_bwd_colors_staged_range": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                                   _i64, _vp, _i32, _i32, _i32, _vp]),
-    "gags_raster_bwd_colors_staged_cap": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                                 _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
-    "gags_raster_bwd_colors_staged_wire": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                                  _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gags_raster_bwd_colors_staged_keep": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                                  _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+                                             _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_raster_list_need": (_i32, [_i32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
     "gags_trim_lists": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_trim_last_ids": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -161,14 +153,20 @@ GAGS_FEAT_F16 = 32  # forward: colors is an fp16 table (include/gags_raster.h)
 GAGS_BWD_F32MFMA = 64  # python-side: staged backward contracts with v_mfma_f32_32x32x2_f32 (round 1-2's kernel) instead of the
 #                        default fp32-equivalent split operands on the 16-bit matrix cores (csrc/raster_bwd_mfma.hip)
 GAGS_BWD_BLOCKWAVES = 4096  # python-side: the staged backward's rows kernel in round 4's shape (a wave per 8x8 pixel block, rows
-#                             merged in LDS: stage bit 512) instead of the default (a wave per 32 channels, rows merged in the accumulators)
+#                             merged in LDS: GAGS_STAGED_BLOCKWAVES) instead of the default (a wave per 32 channels, rows merged in the accumulators)
 GAGS_BWD_EXACT_WEIGHTS = 8192  # python-side: the default rows kernel with the weights as THREE fp16 terms (exact) and five product terms
-#                                (stage bit 1024) instead of two terms / three product terms: 1.60e-7 instead of 1.68e-7 of float64, 1.33x the time
+#                                (GAGS_STAGED_EXACT_WEIGHTS) instead of two terms / three product terms: 1.60e-7 instead of 1.68e-7 of float64, 1.33x the time
 GAGS_BWD_F16SPLIT = 0   # (round 2's opt-in flag: that kernel, made exact, is the default now)
 GAGS_FWD_F16MFMA = 128  # python-side: fp16 feature table + D % 128 == 0: feature pass on the 16-bit matrix cores (opt-in; C flag 64)
 GAGS_FWD_EXACT = 2048  # fp32 table, D >= 128: feature pass on v_mfma_f32_32x32x2_f32, bit-identical to the sequential fmaf chain (the
 #                        oracle); default: 16-bit matrix cores on operands split into three bf16 terms (include/gags_raster.h)
 GAGS_FWD_FUSED = 8  # python-side: single-kernel matrix-core forward (no scratch) instead of weights + features
+# `stage` of gags_raster_bwd_colors_staged (include/gags_raster.h; tests/test_abi_cpu.py compares the two): which of the three
+# stages a call runs, OR-ed with the bits that select a rows kernel, the output dtype and how v_colors / the scratch are used
+GAGS_STAGE_ALL, GAGS_STAGE_ROWS, GAGS_STAGE_SORT, GAGS_STAGE_REDUCE, GAGS_STAGE_MASK = 0, 1, 2, 3, 15
+GAGS_STAGED_F32MFMA, GAGS_STAGED_OUT_F16, GAGS_STAGED_PREZEROED = 32, 64, 128
+GAGS_STAGED_RANGE_SCRATCH, GAGS_STAGED_BLOCKWAVES, GAGS_STAGED_EXACT_WEIGHTS = 256, 512, 1024
+GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instructions (what GAGS_BWD_F32MFMA asks of that kernel)
 
 _lib = None
 

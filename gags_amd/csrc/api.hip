@@ -299,7 +299,7 @@ extern "C" int gags_raster_bwd_geom(int d, int n, int width, int height, const f
                                        (const int32_t *)(fs + L.gid), (const int32_t *)(fs + L.sidx),
                                        (const float *)(fs + L.tbuf), scratch, scratch_bytes, v_geo,
                                        (flags & GAGS_RECS_BY_GAUSSIAN) ? 1 : 0, row_base, n_rows,
-                                       (const int32_t *)(fs + L.hit), flatten_ids, (flags & 32) ? 1 : 0,
+                                       (const int32_t *)(fs + L.hit), flatten_ids, (flags & GAGS_GEOM_F32MFMA) ? 1 : 0,
                                        (hipStream_t)stream);
 }
 
@@ -318,15 +318,19 @@ extern "C" int gags_blended_mask(int64_t n_isects, int width, int height, int n,
                                     (hipStream_t)stream);
 }
 
-namespace {
-int staged_entry(int d, int n, int width, int height, const int32_t *isect_offsets, int64_t n_isects,
-                 const float *v_render_colors, const int32_t *blk_rows, const int32_t *rowmap, int64_t rows,
-                 const void *fwd_scratch, int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes, float *v_colors,
-                 int stage, int ch_begin, int ch_count, const int32_t *rows_dev, const int32_t *wire_pos, float *wire,
-                 const uint8_t *keep_prev, uint8_t *keep_cur, void *stream)
+extern "C" int gags_raster_bwd_colors_staged(int d, int n, int width, int height, const int32_t *isect_offsets,
+                                             int64_t n_isects, const float *v_render_colors, const int32_t *blk_rows,
+                                             const int32_t *rowmap, int64_t rows, const void *fwd_scratch,
+                                             int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes,
+                                             float *v_colors, int stage, int ch_begin, int ch_count,
+                                             const int32_t *rows_dev, const int32_t *wire_pos, float *wire,
+                                             const uint8_t *keep_prev, uint8_t *keep_cur, void *stream)
 {
+    if ((wire != nullptr) != (wire_pos != nullptr) || (wire && (stage & GAGS_STAGED_OUT_F16))) return GAGS_EINVAL;  // (the block is fp32)
+    if ((keep_prev != nullptr) != (keep_cur != nullptr) || (keep_cur && (keep_prev == keep_cur || (stage & GAGS_STAGED_PREZEROED))))
+        return GAGS_EINVAL;
     if (d <= 0 || width <= 0 || height <= 0 || n < 0 || !isects_ok(n_isects, width, height) || rows < 0 ||
-        rows >= (1ll << 31) || stage < 0 || (stage & 15) > 3)
+        rows >= (1ll << 31) || stage < 0 || (stage & GAGS_STAGE_MASK) > GAGS_STAGE_REDUCE)
         return GAGS_EINVAL;
     if (n == 0) return GAGS_OK;
     if (!isect_offsets || !blk_rows || !rowmap || !fwd_scratch || !scratch || !v_colors || !v_render_colors)
@@ -340,68 +344,4 @@ int staged_entry(int d, int n, int width, int height, const int32_t *isect_offse
                                          rowmap, rows, (const float *)(fs + L.wt), (const int32_t *)(fs + L.gid),
                                          rowmap + rowmap_slot_off(n_isects), scratch, scratch_bytes, v_colors, stage,
                                          ch_begin, ch_count, rows_dev, wire_pos, wire, keep_prev, keep_cur, (hipStream_t)stream);
-}
-}  // namespace
-
-extern "C" int gags_raster_bwd_colors_staged_cap(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                                 int64_t n_isects, const float *v_render_colors, const int32_t *blk_rows,
-                                                 const int32_t *rowmap, int64_t rows, const void *fwd_scratch,
-                                                 int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes,
-                                                 float *v_colors, int stage, int ch_begin, int ch_count,
-                                                 const int32_t *rows_dev, void *stream)
-{
-    return staged_entry(d, n, width, height, isect_offsets, n_isects, v_render_colors, blk_rows, rowmap, rows, fwd_scratch,
-                        fwd_scratch_bytes, scratch, scratch_bytes, v_colors, stage, ch_begin, ch_count, rows_dev, nullptr, nullptr,
-                        nullptr, nullptr, stream);
-}
-
-extern "C" int gags_raster_bwd_colors_staged_wire(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                                  int64_t n_isects, const float *v_render_colors, const int32_t *blk_rows,
-                                                  const int32_t *rowmap, int64_t rows, const void *fwd_scratch,
-                                                  int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes,
-                                                  float *v_colors, int stage, int ch_begin, int ch_count,
-                                                  const int32_t *wire_pos, float *wire, const uint8_t *keep_prev,
-                                                  uint8_t *keep_cur, void *stream)
-{
-    if ((wire != nullptr) != (wire_pos != nullptr) || (wire && (stage & 64))) return GAGS_EINVAL;  // (the block is fp32)
-    if ((keep_prev != nullptr) != (keep_cur != nullptr) || (keep_cur && (keep_prev == keep_cur || (stage & 128)))) return GAGS_EINVAL;
-    return staged_entry(d, n, width, height, isect_offsets, n_isects, v_render_colors, blk_rows, rowmap, rows, fwd_scratch,
-                        fwd_scratch_bytes, scratch, scratch_bytes, v_colors, stage, ch_begin, ch_count, nullptr, wire_pos, wire,
-                        keep_prev, keep_cur, stream);
-}
-
-extern "C" int gags_raster_bwd_colors_staged_keep(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                                  int64_t n_isects, const float *v_render_colors, const int32_t *blk_rows,
-                                                  const int32_t *rowmap, int64_t rows, const void *fwd_scratch,
-                                                  int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes,
-                                                  float *v_colors, int stage, int ch_begin, int ch_count,
-                                                  const uint8_t *keep_prev, uint8_t *keep_cur, void *stream)
-{
-    if (!keep_prev || !keep_cur || keep_prev == keep_cur || (stage & 128)) return GAGS_EINVAL;
-    return staged_entry(d, n, width, height, isect_offsets, n_isects, v_render_colors, blk_rows, rowmap, rows, fwd_scratch,
-                        fwd_scratch_bytes, scratch, scratch_bytes, v_colors, stage, ch_begin, ch_count, nullptr, nullptr, nullptr,
-                        keep_prev, keep_cur, stream);
-}
-
-extern "C" int gags_raster_bwd_colors_staged_range(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                                   int64_t n_isects, const float *v_render_colors,
-                                                   const int32_t *blk_rows, const int32_t *rowmap, int64_t rows,
-                                                   const void *fwd_scratch, int64_t fwd_scratch_bytes, void *scratch,
-                                                   int64_t scratch_bytes, float *v_colors, int stage, int ch_begin,
-                                                   int ch_count, void *stream)
-{
-    return gags_raster_bwd_colors_staged_cap(d, n, width, height, isect_offsets, n_isects, v_render_colors, blk_rows, rowmap, rows,
-                                             fwd_scratch, fwd_scratch_bytes, scratch, scratch_bytes, v_colors, stage, ch_begin,
-                                             ch_count, nullptr, stream);
-}
-
-extern "C" int gags_raster_bwd_colors_staged(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                             int64_t n_isects, const float *v_render_colors, const int32_t *blk_rows,
-                                             const int32_t *rowmap, int64_t rows, const void *fwd_scratch,
-                                             int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes,
-                                             float *v_colors, int stage, void *stream)
-{
-    return gags_raster_bwd_colors_staged_range(d, n, width, height, isect_offsets, n_isects, v_render_colors, blk_rows,
-                                               rowmap, rows, fwd_scratch, fwd_scratch_bytes, scratch, scratch_bytes,
-                                               v_colors, stage, 0, d, stream);
 }

@@ -851,11 +851,12 @@ int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, con
                                   const int32_t *rows_dev, const int32_t *wire_pos, float *wire, const uint8_t *keep_prev,
                                   uint8_t *keep_cur, hipStream_t st)
 {
-    // stage: 0 = everything; 1 = rows, 2 = sort + segment offsets, 3 = reduce (per-kernel timing)
+    // stage: GAGS_STAGE_ALL = everything; _ROWS, _SORT (+ segment offsets), _REDUCE = one of them (per-kernel timing)
     GAGS_CLEAR_ERR();
-    const int stage = stage_flags & 15;
+    const int stage = stage_flags & GAGS_STAGE_MASK;
     if (!gags_mfma_width(d) || d > 1024) return 1;
-    const bool sA = stage == 0 || stage == 1, sS = stage == 0 || stage == 2, sR = stage == 0 || stage == 3;
+    const bool sA = stage == GAGS_STAGE_ALL || stage == GAGS_STAGE_ROWS, sS = stage == GAGS_STAGE_ALL || stage == GAGS_STAGE_SORT,
+               sR = stage == GAGS_STAGE_ALL || stage == GAGS_STAGE_REDUCE;
     const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
     const int n_tiles = tile_w * tile_h;
     // channel range of this call (a by-view step exchanges the gradient range by range while the next range is computed,
@@ -863,10 +864,10 @@ int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, con
     if (ch_count <= 0 || ch_begin < 0 || ch_begin + ch_count > d || ch_begin % 32 != 0 ||
         (ch_count % 32 != 0 && ch_begin + ch_count != d))
         return GAGS_EINVAL;
-    // stage bit 256: the scratch holds partial rows of THIS call's channel range only ([rows, ch_count rounded up to 4]
+    // GAGS_STAGED_RANGE_SCRATCH: the scratch holds partial rows of THIS call's channel range only ([rows, ch_count rounded up to 4]
     // instead of [rows, d]; sized with gags_bwd_staged_scratch_bytes(rows, n, that width)): a wide gradient is then produced
     // range by range through a scratch a quarter (an eighth ...) the size -- what lets heavy views fit (C5H: 80 M rows)
-    const bool narrow = (stage_flags & 256) != 0;
+    const bool narrow = (stage_flags & GAGS_STAGED_RANGE_SCRATCH) != 0;
     const int pp = narrow ? ((ch_count + 3) & ~3) : d;
     const StagedLayout L = staged_layout(rows > 0 ? rows : 1, n_gauss, pp);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
@@ -884,9 +885,9 @@ int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, con
             const int ce = ch_begin + ch_count;
             if (ce - c >= 128) {
                 const int nsl = (ce - c) / 128;
-                if (stage_flags & 32) GAGS_ROWS_LAUNCH(raster_bwd_rows<4>, c, nsl);  // GAGS_BWD_F32MFMA: the fp32 matrix instructions
-                else if (stage_flags & 512) GAGS_ROWS_LAUNCH(raster_bwd_rows_f16, c, nsl);  // round 4's shape: a wave per pixel block, rows merged in LDS
-                else if (stage_flags & 1024) GAGS_ROWS_LAUNCH((raster_bwd_rows_cw<3, 5>), c, nsl);  // weights as three terms (exact), five product terms
+                if (stage_flags & GAGS_STAGED_F32MFMA) GAGS_ROWS_LAUNCH(raster_bwd_rows<4>, c, nsl);  // the fp32 matrix instructions
+                else if (stage_flags & GAGS_STAGED_BLOCKWAVES) GAGS_ROWS_LAUNCH(raster_bwd_rows_f16, c, nsl);  // round 4's shape: a wave per pixel block, rows merged in LDS
+                else if (stage_flags & GAGS_STAGED_EXACT_WEIGHTS) GAGS_ROWS_LAUNCH((raster_bwd_rows_cw<3, 5>), c, nsl);  // weights as three terms (exact), five product terms
                 else if (rows_scale_per_block()) GAGS_ROWS_LAUNCH((raster_bwd_rows_cw<2, 3>), c, nsl);  // (GAGS_BWD_ROWSCALE=1: round 5's scale per (row, block))
                 else GAGS_ROWS_LAUNCH((raster_bwd_rows_cw<2, 3, true>), c, nsl);  // default: 16-bit matrix cores, a wave per 32 channels, three product terms, one weight scale
                 c += 128 * nsl;
@@ -914,23 +915,26 @@ int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, con
         hipLaunchKernelGGL(seg_fill_kernel, dim3((n_gauss + 1 + 255) / 256), dim3(256), 0, st, n_gauss, seg);
     }
     if (sR) {
-        const bool half = (stage_flags & 64) != 0;  // v_colors is an fp16 tensor
-        const int sparse = (stage_flags & 128) ? 1 : 0;  // v_colors arrives zero-filled: rows of Gaussians that blended nothing are skipped
+        const bool half = (stage_flags & GAGS_STAGED_OUT_F16) != 0;  // v_colors is an fp16 tensor
+        const int sparse = (stage_flags & GAGS_STAGED_PREZEROED) ? 1 : 0;  // v_colors arrives zero-filled: rows of Gaussians that blended nothing are skipped
         const int c4 = ch_count & ~3, c1 = ch_count & 3;  // float4 lanes + the 1-3 channels an odd width leaves over
         if (wire && (c1 != 0 || !wire_pos)) return GAGS_EINVAL;  // the wire block is [rows, ch_count], ch_count % 4 == 0
         const bool ride = c4 >= 16 && c1 > 0;  // the 1-3 leftover channels ride along with the float4 columns' launch
+        // one launch of the reduce kernel over channels [c0, c0 + cw): the fp16- or the fp32-output instantiation
+        auto reduce = [&](auto *k_f16, auto *k_f32, dim3 grid, int c0, int cw, int tail) {
+            hipLaunchKernelGGL(half ? k_f16 : k_f32, grid, dim3(256), 0, st, n_gauss, d, c0, cw, seg, idx_s, prow, pp,
+                               (void *)v_colors, sparse, wire_pos, wire, keep_prev, keep_cur, tail);
+        };
         if (c4 > 0) {
             const int gpb = 256 / (c4 >> 2);
             const dim3 grid((n_gauss + gpb * REDUCE_ITER - 1) / (gpb * REDUCE_ITER));
             const int tail = ride ? c1 : 0;
-            if (half) hipLaunchKernelGGL((reduce_rows_kernel<true, 4>), grid, dim3(256), 0, st, n_gauss, d, ch_begin, c4, seg, idx_s, prow, pp, (void *)v_colors, sparse, wire_pos, wire, keep_prev, keep_cur, tail);
-            else hipLaunchKernelGGL((reduce_rows_kernel<false, 4>), grid, dim3(256), 0, st, n_gauss, d, ch_begin, c4, seg, idx_s, prow, pp, (void *)v_colors, sparse, wire_pos, wire, keep_prev, keep_cur, tail);
+            reduce((reduce_rows_kernel<true, 4>), (reduce_rows_kernel<false, 4>), grid, ch_begin, c4, tail);
         }
         if (c1 > 0 && !ride) {
             const int gpb = 256 / c1;
             const dim3 grid((n_gauss + gpb * REDUCE_ITER - 1) / (gpb * REDUCE_ITER));
-            if (half) hipLaunchKernelGGL((reduce_rows_kernel<true, 1>), grid, dim3(256), 0, st, n_gauss, d, ch_begin + c4, c1, seg, idx_s, prow, pp, (void *)v_colors, sparse, wire_pos, wire, keep_prev, keep_cur, 0);
-            else hipLaunchKernelGGL((reduce_rows_kernel<false, 1>), grid, dim3(256), 0, st, n_gauss, d, ch_begin + c4, c1, seg, idx_s, prow, pp, (void *)v_colors, sparse, wire_pos, wire, keep_prev, keep_cur, 0);
+            reduce((reduce_rows_kernel<true, 1>), (reduce_rows_kernel<false, 1>), grid, ch_begin + c4, c1, 0);
         }
     }
     GAGS_CHECK_LAUNCH();

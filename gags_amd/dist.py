@@ -409,7 +409,7 @@ class OverlappedGradReducer:
     def wire_for_range(self, c0, c1):
         """RasterContext.grad_wire_hook: called by the staged backward BEFORE the reduce stage of range [c0, c1).  Returns
         (pos int32 [N], wire fp32 [|union|, c1 - c0]) -- the reduce kernel then writes the rows the ranks exchange straight
-        into `wire` (gags_raster_bwd_colors_staged_wire), next to the gradient itself: no pack kernel re-reads the range --
+        into `wire` (gags_raster_bwd_colors_staged: wire_pos / wire), next to the gradient itself: no pack kernel re-reads the range --
         or None when the exchange packs for itself (all rows, the bf16 wire, host tensors).  The calling (compute) stream is
         made to wait for the union's index list, which the exchange stream builds from the all-reduced mask; the host waits
         for its COUNT here (it sizes the block) while the range's rows kernel is already queued."""

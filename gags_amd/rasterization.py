@@ -20,6 +20,7 @@ PyTorch supplies device memory, streams and autograd plumbing; all arithmetic is
 import ctypes
 import os
 import threading
+from typing import Any, NamedTuple
 
 import torch
 
@@ -55,6 +56,17 @@ EARLY_ROWMAP = os.environ.get("GAGS_EARLY_ROWMAP", "1") != "0"
 CAPACITY_MODE = os.environ.get("GAGS_CAPACITY_MODE", "0") == "1"
 
 
+def _tiles(width, height):
+    """(tile_w, tile_h, number of tiles) of a width x height view."""
+    tile_w, tile_h = (width + TILE - 1) // TILE, (height + TILE - 1) // TILE
+    return tile_w, tile_h, tile_w * tile_h
+
+
+def _dev_key(dev):
+    """The device's index as a dictionary key (a bare "cuda" is the current device)."""
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
 class RasterContext:
     """Everything `rasterization(...)` remembers or is told between calls -- SURVEY 8b asks for a boundary that is
     "re-entrant per stream, no global state": the C library has none, and the Python layer keeps its own in an object the
@@ -73,7 +85,7 @@ class RasterContext:
         With grad_wire_hook set, the backward asks it before the reduce stage of every range,
             grad_wire_hook(ch_begin, ch_end) -> (pos int32 [N], wire fp32 [rows, ch_end - ch_begin]) or None,
         and the reduce kernel writes row pos[g] of `wire` for every Gaussian with pos[g] >= 0 next to the gradient itself
-        (gags_raster_bwd_colors_staged_wire); grad_range_hook then gets `wire` as a fourth argument.  grad_range_channels: an
+        (gags_raster_bwd_colors_staged: wire_pos, wire); grad_range_hook then gets `wire` as a fourth argument.  grad_range_channels: an
         int or a tuple of range widths (see GRAD_RANGE_CHANNELS).
     capacity_mode, cap_isects, cap_rows
         Capacity mode (OFF by default): the two counts a view produces on the device -- tile intersections, partial
@@ -88,7 +100,7 @@ class RasterContext:
         switch for callers whose host is the bottleneck.
     overlap_zero_fill
         Experiment, OFF: zero-fill the colour gradient on a second stream during the forward's binning and let the reduce
-        stage write only the rows that exist (stage bit 128; 73 % of the Gaussians blend nothing at C3).  Measured at C3:
+        stage write only the rows that exist (GAGS_STAGED_PREZEROED; 73 % of the Gaussians blend nothing at C3).  Measured at C3:
         reduce 1.27 -> 0.95 ms, but the fill kernel takes the CUs from whatever it runs beside -- under the rows kernel that
         kernel slowed by 0.38 ms, under the binning kernels the step grew by 1.7 ms.  The C-ABI flag stays for callers
         that own a zeroed buffer anyway.
@@ -160,31 +172,31 @@ class RasterContext:
         return ent.hand_out()
 
     def side_stream(self, dev):
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        key = _dev_key(dev)
         if key not in self._side:
             self._side[key] = torch.cuda.Stream(device=dev)
         return self._side[key]
 
     def take_pinned(self, dev):
         """A pinned int32 of the caller's own (returned with give_pinned): counts of several forwards may be in flight."""
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        key = _dev_key(dev)
         pool = self._pinned_pool.setdefault(key, [])
         return pool.pop() if pool else torch.empty(1, dtype=torch.int32).pin_memory()
 
     def give_pinned(self, dev, t):
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        key = _dev_key(dev)
         pool = self._pinned_pool.setdefault(key, [])
         if len(pool) < 8:
             pool.append(t)
 
     def pinned_i64(self, dev):
-        key = ("i64", dev.index if dev.index is not None else torch.cuda.current_device())
+        key = ("i64", _dev_key(dev))
         if key not in self._pinned:
             self._pinned[key] = torch.empty(1, dtype=torch.int64).pin_memory()
         return self._pinned[key]
 
     def pinned_i32(self, dev):
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        key = _dev_key(dev)
         if key not in self._pinned:
             self._pinned[key] = torch.empty(1, dtype=torch.int32).pin_memory()
         return self._pinned[key]
@@ -227,7 +239,7 @@ class _KeptGrad:
     those zeros are 2.2 GB of HBM writes.  Here the context keeps ONE zero-initialised buffer per (N, D, dtype), every
     backward hands autograd a fresh alias of it (own TensorImpl, same storage: autograd adopts it without a copy) and the
     reduce stage only writes the rows that have partial rows now and re-zeroes the rows that had some in the previous step
-    (two flag arrays, gags_raster_bwd_colors_staged_keep).  The buffer is only reused when NOBODY else still refers to its
+    (two flag arrays: keep_prev / keep_cur of gags_raster_bwd_colors_staged).  The buffer is only reused when NOBODY else still refers to its
     storage (reference count back at its baseline: the previous step's .grad was released, e.g. zero_grad(set_to_none=True)
     or `.grad = None`) and nobody wrote to it in place (version counter unchanged: torch's in-place operators move it, this
     package's own writers of a gradient -- dist.reduce_feature_grad -- move it through grad_written(), and a caller whose own
@@ -440,6 +452,16 @@ class _SH(torch.autograd.Function):
         return v_coeffs, v_means, None, None, None
 
 
+class Binning(NamedTuple):
+    """tile_binning's result, in the order its callers unpack it (see there)."""
+    isect_ids: Any
+    flatten_ids: Any
+    isect_offsets: Any
+    n_isects: Any
+    packed: Any
+    offsets_full: Any
+
+
 def tile_binning(means2d, radii, depths, tiles_per_gauss, width, height, conics=None, opacities=None, cap=None, records=None,
                  context=None):
     """K5-K8 (+K8b) on device.  Returns (isect_ids sorted int64, flatten_ids sorted int32, isect_offsets [th,tw] int32,
@@ -452,8 +474,7 @@ def tile_binning(means2d, radii, depths, tiles_per_gauss, width, height, conics=
     st = _stream()
     dev = means2d.device
     n = radii.shape[0]
-    tile_w, tile_h = (width + TILE - 1) // TILE, (height + TILE - 1) // TILE
-    n_tiles = tile_w * tile_h
+    tile_w, tile_h, n_tiles = _tiles(width, height)
     tile_bits = max(1, n_tiles.bit_length())  # (room for the sentinel tile id n_tiles of the capacity mode)
     cum = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)
@@ -513,7 +534,7 @@ def tile_binning(means2d, radii, depths, tiles_per_gauss, width, height, conics=
     # `offsets` has n_tiles + 1 entries, the last one = the intersection count (gags_tile_offsets): the raster kernels read
     # isect_offsets[tile + 1] as a tile's end.  Callers get gsplat's [tile_h, tile_w] view AND the buffer itself.
     off_view = offsets[:n_tiles].view(tile_h, tile_w)
-    return ids_s[:size], flat_s[:size], off_view, count, packed, offsets
+    return Binning(ids_s[:size], flat_s[:size], off_view, count, packed, offsets)
 
 
 def _trim_lists(lib, n, width, height, offsets_full, flatten_ids, n_isects, packed):
@@ -525,7 +546,7 @@ def _trim_lists(lib, n, width, height, offsets_full, flatten_ids, n_isects, pack
     (gags_trim_last_ids translates a copy back).  One more 4-byte readback (the trimmed count sizes the id list)."""
     st = _stream()
     dev = flatten_ids.device
-    n_tiles = ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
+    n_tiles = _tiles(width, height)[2]
     need = torch.empty(n_tiles, dtype=torch.int32, device=dev)
     with profiler.stage("list_need"):
         check(lib.gags_raster_list_need(n, width, height, ptr(offsets_full), ptr(flatten_ids), n_isects, ptr(packed),
@@ -584,7 +605,7 @@ class _Rasterize(torch.autograd.Function):
         backgrounds = None if backgrounds is None else _c(backgrounds)
         n, d = colors.shape
         dev = colors.device
-        n_tiles = ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
+        n_tiles = _tiles(width, height)[2]
         offsets = _offsets_with_count(offsets, n_tiles, flatten_ids.shape[0] if n_isects is None else n_isects)
         n_isects = flatten_ids.shape[0]  # (capacity mode: the buffers' size; the kernels take the count from `offsets`)
         out = torch.empty(height, width, d, device=dev)
@@ -649,7 +670,7 @@ class _Rasterize(torch.autograd.Function):
         if (split and n_isects > 0 and rctx_.early_rowmap and needs[2] and not need_geom and _mfma_width(d)
                 and d <= 1024 and not (flags & _lib.GAGS_BWD_ATOMIC) and not rctx_.capacity_mode):
             with profiler.stage("bwd_rowcount"):
-                early = _early_rowmap(lib, rctx_, offsets, blk_rows, scratch, n_isects, width, height, dev)
+                early = _early_rowmap(lib, rctx_, _FwdState(offsets, n_isects, blk_rows, scratch, flatten_ids, n, d, width, height))
         # wide-D geometry gradients on the matrix cores (gags_raster_bwd_geom) also consume the forward's scratch
         geom_mfma = split and need_geom and _geom_mfma_width(d) and not (flags & _lib.GAGS_BWD_ATOMIC)
         staged = (split and _mfma_width(d) and d <= 1024 and (needs[2] or geom_mfma)
@@ -674,6 +695,7 @@ class _Rasterize(torch.autograd.Function):
         n, d = colors.shape
         dev = colors.device
         n_isects = flatten_ids.shape[0]
+        fwd = _FwdState(offsets, n_isects, blk_rows, fwd_scratch, flatten_ids, n, d, width, height)
         need_geom = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[3]
         v_out = torch.zeros(height, width, d, device=dev) if v_out is None else _c(v_out)
         v_alphas = None if v_alphas is None else _c(v_alphas)
@@ -683,17 +705,13 @@ class _Rasterize(torch.autograd.Function):
         if not need_geom and blk_rows is not None:
             # an fp16 table gets its gradient in fp16 straight from the reduce kernel (fp32 sums, rounded once): no fp32
             # tensor + cast pass (autograd wants the table's dtype; an fp32 master sits behind a .half() cast)
-            v_colors = _backward_staged(lib, ctx.rctx, offsets, n_isects, blk_rows, fwd_scratch, v_out, n, d, width, height,
-                                        (32 if (flags & _lib.GAGS_BWD_F32MFMA) else 0) | (64 if ctx.half else 0) | (512 if (flags & _lib.GAGS_BWD_BLOCKWAVES) else 0) | (1024 if (flags & _lib.GAGS_BWD_EXACT_WEIGHTS) else 0),
-                                        flatten_ids, ctx.prezero, early=ctx.early)
+            v_colors = _backward_staged(lib, ctx.rctx, fwd, v_out, _stage_bits(flags, ctx.half), ctx.prezero, early=ctx.early)
             return None, None, v_colors, None, v_bg, None, None, None, None, None, None, None, None, None, None
         if need_geom and blk_rows is not None and ctx.geom_mfma:
             # wide D: colours through the staged backward, geometry through the matrix-core dot pass + scalar pass
             v_colors = None
             if ctx.needs_input_grad[2]:
-                v_colors = _backward_staged(lib, ctx.rctx, offsets, n_isects, blk_rows, fwd_scratch, v_out, n, d, width, height,
-                                            (32 if (flags & _lib.GAGS_BWD_F32MFMA) else 0) | (64 if ctx.half else 0) | (512 if (flags & _lib.GAGS_BWD_BLOCKWAVES) else 0) | (1024 if (flags & _lib.GAGS_BWD_EXACT_WEIGHTS) else 0),
-                                            flatten_ids)
+                v_colors = _backward_staged(lib, ctx.rctx, fwd, v_out, _stage_bits(flags, ctx.half))
             if ctx.half:  # the geometry kernels read an fp32 table: widen the halves (exact) for this backward
                 colors = colors.float()
             # compact numbering of the per-slot rows: one small prefix sum and a 4-byte readback instead of sorting the
@@ -712,7 +730,8 @@ class _Rasterize(torch.autograd.Function):
                                                ptr(packed), ptr(v_out), ptr(v_alphas), ptr(blk_rows), ptr(fwd_scratch),
                                                fwd_scratch.numel(), ptr(gscratch), nb, ptr(v_geo), ptr(flatten_ids),
                                                ptr(row_base), n_rows,
-                                               _lib.GAGS_RECS_BY_GAUSSIAN | (32 if (flags & _lib.GAGS_BWD_F32MFMA) else 0),
+                                               _lib.GAGS_RECS_BY_GAUSSIAN
+                                               | (_lib.GAGS_GEOM_F32MFMA if (flags & _lib.GAGS_BWD_F32MFMA) else 0),
                                                _stream()),
                       "gags_raster_bwd_geom")
             v_con, v_m2d, v_opac = v_geo[:, 0:3].contiguous(), v_geo[:, 3:5].contiguous(), v_geo[:, 5].contiguous()
@@ -806,14 +825,48 @@ class _EarlyRowmap:
             pass
 
 
-def _early_rowmap(lib, rctx, offsets, blk_rows, fwd_scratch, n_isects, width, height, dev):
-    ne = lib.gags_bwd_rowmap_elems(n_isects, width, height)
+class _FwdState(NamedTuple):
+    """What a split forward hands the staged backward of its view (read by name: tools/ wrap _backward_staged)."""
+    offsets: Any      # n_tiles + 1 int32 entries, the last one = the intersection count
+    n_isects: int     # entries of the id lists (capacity mode: the buffers' size)
+    blk_rows: Any     # the forward's slot counts, four per tile
+    fwd_scratch: Any  # the forward's scratch: weight tiles, hit flags
+    flatten_ids: Any
+    n: int
+    d: int
+    width: int
+    height: int
+
+
+_STAGE_NAMES = {_lib.GAGS_STAGE_ROWS: "bwd_rows", _lib.GAGS_STAGE_SORT: "bwd_sort", _lib.GAGS_STAGE_REDUCE: "bwd_reduce"}
+
+
+def _stage_bits(raster_flags, half):
+    """The public raster_flags' choice of a rows kernel, and `half` = the gradient of an fp16 table, as bits of the `stage`
+    argument of gags_raster_bwd_colors_staged."""
+    return ((_lib.GAGS_STAGED_F32MFMA if (raster_flags & _lib.GAGS_BWD_F32MFMA) else 0)
+            | (_lib.GAGS_STAGED_OUT_F16 if half else 0)
+            | (_lib.GAGS_STAGED_BLOCKWAVES if (raster_flags & _lib.GAGS_BWD_BLOCKWAVES) else 0)
+            | (_lib.GAGS_STAGED_EXACT_WEIGHTS if (raster_flags & _lib.GAGS_BWD_EXACT_WEIGHTS) else 0))
+
+
+def _rowmap(lib, fwd):
+    """The view's partial gradient rows numbered on the device (gags_bwd_rowmap, enqueued on the current stream; the one place
+    that knows that call).  Returns (rowmap, total = the row count, int32 [1] on the device, the scan's scratch)."""
+    dev = fwd.blk_rows.device
+    ne = lib.gags_bwd_rowmap_elems(fwd.n_isects, fwd.width, fwd.height)
     trow = torch.empty(ne, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)
-    sb = lib.gags_bwd_rowmap_scratch_bytes(n_isects)
+    sb = lib.gags_bwd_rowmap_scratch_bytes(fwd.n_isects)
     stmp = torch.empty(max(sb, 4), dtype=torch.uint8, device=dev)
-    check(lib.gags_bwd_rowmap(n_isects, width, height, ptr(offsets), ptr(blk_rows), ptr(fwd_scratch), fwd_scratch.numel(),
-                              ptr(trow), ne, ptr(total), ptr(stmp), sb, _stream()), "gags_bwd_rowmap")
+    check(lib.gags_bwd_rowmap(fwd.n_isects, fwd.width, fwd.height, ptr(fwd.offsets), ptr(fwd.blk_rows), ptr(fwd.fwd_scratch),
+                              fwd.fwd_scratch.numel(), ptr(trow), ne, ptr(total), ptr(stmp), sb, _stream()), "gags_bwd_rowmap")
+    return trow, total, stmp
+
+
+def _early_rowmap(lib, rctx, fwd):
+    trow, total, stmp = _rowmap(lib, fwd)
+    dev = total.device
     host = rctx.take_pinned(dev)
     host.copy_(total, non_blocking=True)
     ev = torch.cuda.Event()
@@ -821,142 +874,160 @@ def _early_rowmap(lib, rctx, offsets, blk_rows, fwd_scratch, n_isects, width, he
     return _EarlyRowmap(trow, total, stmp, host, ev, rctx, dev)
 
 
-def _backward_staged(lib, rctx, offsets, n_isects, blk_rows, fwd_scratch, v_out, n, d, width, height, xflag=0,
-                     flatten_ids=None, prezero=None, exact_rows=False, early=None):
-    """Colours-only backward without atomics: hit flags of the forward -> prefix sum (one row per (tile, Gaussian)
-    pair that blended anything) -> one 4-byte readback (total rows) -> merged partial rows -> sort by Gaussian ->
-    segmented sum."""
-    dev = v_out.device
-    st = _stream()
-    if rctx.grad_rows_hook is not None and rctx.grad_range_hook is not None and flatten_ids is not None:
-        mask = torch.empty(n, dtype=torch.uint8, device=dev)
-        check(lib.gags_blended_mask(n_isects, width, height, n, ptr(flatten_ids), ptr(fwd_scratch), fwd_scratch.numel(),
-                                    ptr(mask), st), "gags_blended_mask")
-        rctx.grad_rows_hook(mask)  # before the readback below: the ranks agree on the union while the backward starts
-    hook = rctx.grad_range_hook
-    ranges = _channel_ranges(d, rctx.grad_range_channels) if hook is not None else None
-    cap_key = (n, width, height, dev.index)
-    pending = None
+def _row_count(lib, rctx, fwd, early, capacity):
+    """(rowmap, total, rows, pending): the row map and the row count the backward sizes its scratch by, one of three ways.
+    early (an _EarlyRowmap): the forward enqueued the row map behind its own kernels and its count has reached the host
+    meanwhile: no prefix sum, no readback, no drained queue here.  capacity (the count remembered from earlier views; see
+    RasterContext.capacity_mode): `rows` is a capacity and the count stays on the device until the backward is enqueued --
+    `pending` is its _DeferredCount.  Neither: one 4-byte readback."""
     if early is not None:
-        # the forward enqueued the row map behind its own kernels and its count has reached the host meanwhile: no prefix sum,
-        # no readback, no drained queue here
-        trow, total, rows = early.trow, early.total, early.rows()
-    else:
-        ne = lib.gags_bwd_rowmap_elems(n_isects, width, height)
-        trow = torch.empty(ne, dtype=torch.int32, device=dev)
-        total = torch.empty(1, dtype=torch.int32, device=dev)
-        sb = lib.gags_bwd_rowmap_scratch_bytes(n_isects)
-        stmp = torch.empty(max(sb, 4), dtype=torch.uint8, device=dev)
-    if early is None:
-        with profiler.stage("bwd_rowcount"):
-            check(lib.gags_bwd_rowmap(n_isects, width, height, ptr(offsets), ptr(blk_rows), ptr(fwd_scratch),
-                                      fwd_scratch.numel(), ptr(trow), ne, ptr(total), ptr(stmp), sb, st), "gags_bwd_rowmap")
-            if rctx.capacity_mode and hook is None and cap_key in rctx.cap_rows and not exact_rows:
-                # capacity mode (see RasterContext): the row count stays on the device until the backward is enqueued
-                rows = min(max(n_isects, 1), int(rctx.cap_rows[cap_key] * CAP_MARGIN) + 1024)
-                pending = _DeferredCount(total, rctx)
-            else:
-                host = ctypes.c_int32(0)
-                check(lib.gags_read_i32(ptr(total), ctypes.byref(host), st), "gags_read_i32")
-                rows = int(host.value)
-    # a heavy view's partial rows ([rows, D] fp32) can outgrow the device (C5H: 80 M rows x 2 KB): beyond PROW_MAX_BYTES the
-    # gradient is produced one 128-channel range at a time through a [rows, 128] scratch (stage bit 256)
-    narrow = (hook is None and pending is None and d % 128 == 0 and d > 128 and rows * d * 4 > PROW_MAX_BYTES)
-    nbytes = lib.gags_bwd_staged_scratch_bytes(rows, n, 128 if narrow else d)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    v_dtype = torch.float16 if (xflag & 64) else torch.float32
-    # the persistent buffer (rows of Gaussians that blend nothing are never written again): not under the exchange hooks (the
-    # ranks' sum lands in rows this view did not write), the capacity mode or the zero-fill experiment
-    # ... under the exchange hooks only when the reduce stage writes the exchanged block itself: its rows -- where finish()
-    # writes the ranks' sum -- then count as written (gags_raster_bwd_colors_staged_wire)
-    wire_hook = rctx.grad_wire_hook if (hook is not None and ranges is not None and not (xflag & 64)) else None
-    kept = None
-    if pending is None and prezero is None and (hook is None or (wire_hook is not None and rctx.grad_rows_hook is not None)):
-        kept = rctx.kept_grad(n, d, v_dtype, dev)
-    v_colors = kept[0] if kept is not None else torch.empty(n, d, device=dev, dtype=v_dtype)
-    rows_dev = ptr(total) if pending is not None else None
+        return early.trow, early.total, early.rows(), None
+    with profiler.stage("bwd_rowcount"):
+        trow, total, _ = _rowmap(lib, fwd)
+        if capacity is not None:
+            return trow, total, min(max(fwd.n_isects, 1), int(capacity * CAP_MARGIN) + 1024), _DeferredCount(total, rctx)
+        host = ctypes.c_int32(0)
+        check(lib.gags_read_i32(ptr(total), ctypes.byref(host), _stream()), "gags_read_i32")
+        return trow, total, int(host.value), None
 
-    def keep_or_range(stage, c0, cw):
-        """One staged call for channels [c0, c0 + cw): through the persistent buffer's entry when the call holds the reduce stage."""
-        if kept is not None and (stage & 15) in (0, 3):
-            check(lib.gags_raster_bwd_colors_staged_keep(
-                d, n, width, height, ptr(offsets), n_isects, ptr(v_out), ptr(blk_rows), ptr(trow), rows, ptr(fwd_scratch),
-                fwd_scratch.numel(), ptr(scratch), nbytes, ptr(v_colors), stage, c0, cw, ptr(kept[1]), ptr(kept[2]), st),
-                "gags_raster_bwd_colors_staged_keep")
-        else:
-            check(lib.gags_raster_bwd_colors_staged_cap(
-                d, n, width, height, ptr(offsets), n_isects, ptr(v_out), ptr(blk_rows), ptr(trow), rows, ptr(fwd_scratch),
-                fwd_scratch.numel(), ptr(scratch), nbytes, ptr(v_colors), stage, c0, cw, rows_dev, st),
-                "gags_raster_bwd_colors_staged_cap")
 
-    def run(stage):
-        keep_or_range(stage | xflag, 0, d)
-
-    if prezero is not None and hook is None:
+def _grad_buffer(rctx, fwd, bits, dev, hook, wire_hook, pending, prezero):
+    """(v_colors, kept, bits): the tensor the reduce stage writes.  In this order:
+    prezero = (buffer, event) of a zero-fill the forward started (RasterContext.overlap_zero_fill), outside the exchange hooks:
+    that buffer, and the reduce stage writes only the rows that exist (GAGS_STAGED_PREZEROED);
+    else the context's persistent buffer (kept = _KeptGrad.hand_out(): an alias and two flag arrays; rows of Gaussians that blend
+    nothing are never written again): not with a zero-fill, not in capacity mode (`pending`), and under the exchange hooks
+    (the ranks' sum lands in rows this view did not write) only when the reduce stage writes the exchanged block itself: its
+    rows -- where finish() writes the ranks' sum -- then count as written (wire_pos / wire of the staged entry);
+    else a fresh tensor, written in full."""
+    v_dtype = torch.float16 if (bits & _lib.GAGS_STAGED_OUT_F16) else torch.float32
+    if prezero is not None:
         # the forward started a zero-fill of this tensor on a second stream while the binning kernels (small, latency-bound:
         # the memory system idles) ran; the reduce stage then writes only the rows that exist -- 73 % of the Gaussians
         # blend nothing at C3: 3.07 GB -> 0.83 GB written here.  (Filled under the rows kernel instead, the fill slowed
         # that kernel by as much as the reduce stage gained.)
         buf, ev = prezero
-        if buf.shape == v_colors.shape and buf.dtype == v_colors.dtype:
+        if hook is None and buf.shape == (fwd.n, fwd.d) and buf.dtype == v_dtype:
             torch.cuda.current_stream().wait_event(ev)
-            v_colors = buf
-            xflag |= 128
-    if narrow:
-        for c0 in range(0, d, 128):
-            for stage in ((1, 2, 3) if c0 == 0 else (1, 3)):
-                with profiler.stage(("bwd_rows", "bwd_sort", "bwd_reduce")[stage - 1]):
-                    keep_or_range(stage | xflag | 256, c0, 128)
-    elif hook is not None and ranges is not None:
-        alias = v_colors.detach()  # own TensorImpl, same storage: autograd may still adopt v_colors without a copy
-        # the partial rows are produced for `grad_rows_group` channels per launch: every rows launch streams the view's weight
-        # tiles from HBM once for all of its 128-channel slices (they share them through L2), so wider groups re-read them less
-        # often -- and deliver their first range later; the reduce stage and the exchange keep the narrower range either way
-        group = max(int(rctx.grad_rows_group), 1)
-        rows_done = 0
-        for c0, c1 in ranges:
-            if c1 > rows_done:
-                g1 = rows_done
-                while g1 < c1 or (g1 - rows_done < group and g1 < d):
-                    g1 = next(b for a, b in ranges if a == g1)
-                for stage in ((1, 2) if rows_done == 0 else (1,)):
-                    with profiler.stage(("bwd_rows", "bwd_sort")[stage - 1]):
-                        check(lib.gags_raster_bwd_colors_staged_range(
-                            d, n, width, height, ptr(offsets), n_isects, ptr(v_out), ptr(blk_rows), ptr(trow), rows,
-                            ptr(fwd_scratch), fwd_scratch.numel(), ptr(scratch), nbytes, ptr(v_colors), stage | xflag, rows_done,
-                            g1 - rows_done, st), "gags_raster_bwd_colors_staged_range")
-                rows_done = g1
-            # the rows the ranks exchange leave from the reduce kernel itself (no pack pass over the range afterwards)
-            w = wire_hook(c0, c1) if wire_hook is not None else None
-            if w is None and kept is not None:
-                # the exchange packs for itself after all (bf16 wire, all rows): its sum may land in rows the flags do not
-                # cover.  This step's reduce writes every row; the buffer is not kept
-                rctx.forget_kept(n, d, v_dtype, dev)
-                kept = None
-            with profiler.stage("bwd_reduce"):
-                check(lib.gags_raster_bwd_colors_staged_wire(
-                    d, n, width, height, ptr(offsets), n_isects, ptr(v_out), ptr(blk_rows), ptr(trow), rows,
-                    ptr(fwd_scratch), fwd_scratch.numel(), ptr(scratch), nbytes, ptr(v_colors), 3 | xflag, c0, c1 - c0,
-                    ptr(w[0]) if w else None, ptr(w[1]) if w else None, ptr(kept[1]) if kept else None,
-                    ptr(kept[2]) if kept else None, st), "gags_raster_bwd_colors_staged_wire")
-            if w is not None:
-                hook(alias, c0, c1, w[1])
-            else:
-                hook(alias, c0, c1)
-    elif profiler.ENABLED:  # one event pair per kernel (group), for the roofline line of bench.py
-        for stage, name in enumerate(("bwd_rows", "bwd_sort", "bwd_reduce"), start=1):
+            return buf, None, bits | _lib.GAGS_STAGED_PREZEROED
+    elif pending is None and (hook is None or (wire_hook is not None and rctx.grad_rows_hook is not None)):
+        kept = rctx.kept_grad(fwd.n, fwd.d, v_dtype, dev)
+        if kept is not None:
+            return kept[0], kept, bits
+    return torch.empty(fwd.n, fwd.d, device=dev, dtype=v_dtype), None, bits
+
+
+def _bind_staged(lib, fwd, v_out, trow, rows, scratch, v_colors):
+    """gags_raster_bwd_colors_staged with everything bound that does not vary within one backward.  What remains per call:
+    stage (with its bits), the channel range [c0, c0 + cw), rows_dev (capacity mode: the true row count on the device),
+    wire = (pos, block) of the exchange, keep = the persistent buffer's hand-out -- its flag arrays travel only with a call
+    that holds the reduce stage."""
+    fixed = (fwd.d, fwd.n, fwd.width, fwd.height, ptr(fwd.offsets), fwd.n_isects, ptr(v_out), ptr(fwd.blk_rows), ptr(trow), rows,
+             ptr(fwd.fwd_scratch), fwd.fwd_scratch.numel(), ptr(scratch), scratch.numel(), ptr(v_colors))
+    st = _stream()
+    with_reduce = (_lib.GAGS_STAGE_ALL, _lib.GAGS_STAGE_REDUCE)
+
+    def call(stage, c0, cw, rows_dev=None, wire=None, keep=None):
+        if keep is not None and (stage & _lib.GAGS_STAGE_MASK) not in with_reduce:
+            keep = None
+        check(lib.gags_raster_bwd_colors_staged(
+            *fixed, stage, c0, cw, rows_dev, ptr(wire[0]) if wire else None, ptr(wire[1]) if wire else None,
+            ptr(keep[1]) if keep else None, ptr(keep[2]) if keep else None, st), "gags_raster_bwd_colors_staged")
+
+    return call
+
+
+def _run_whole(call, bits, d, rows_dev, kept, hook, v_colors):
+    """The whole view, all channels: one call, or one per stage under the profiler (one event pair per kernel (group), for the
+    roofline line of bench.py).  An exchange hook whose ranges do not divide this width gets the gradient in one piece."""
+    if profiler.ENABLED:
+        for stage, name in _STAGE_NAMES.items():
             with profiler.stage(name):
-                run(stage)
+                call(stage | bits, 0, d, rows_dev, None, kept)
     else:
-        run(0)
-        if hook is not None:
-            hook(v_colors.detach(), 0, d)
+        call(_lib.GAGS_STAGE_ALL | bits, 0, d, rows_dev, None, kept)
+    if hook is not None:
+        hook(v_colors.detach(), 0, d)
+
+
+def _run_range_scratch(call, bits, d, kept):
+    """A heavy view (PROW_MAX_BYTES): the gradient one 128-channel range at a time through a [rows, 128] scratch."""
+    for c0 in range(0, d, 128):
+        for stage in ((_lib.GAGS_STAGE_ROWS, _lib.GAGS_STAGE_SORT, _lib.GAGS_STAGE_REDUCE) if c0 == 0
+                      else (_lib.GAGS_STAGE_ROWS, _lib.GAGS_STAGE_REDUCE)):
+            with profiler.stage(_STAGE_NAMES[stage]):
+                call(stage | bits | _lib.GAGS_STAGED_RANGE_SCRATCH, c0, 128, None, None, kept)
+
+
+def _run_ranged(call, rctx, fwd, bits, ranges, hook, wire_hook, kept, v_colors):
+    """Under the exchange hooks: rows for `grad_rows_group` channels per launch (the sort with the first), then per range the
+    reduce stage -- which also writes the exchanged block when the wire hook hands one out -- and the range hook."""
+    alias = v_colors.detach()  # own TensorImpl, same storage: autograd may still adopt v_colors without a copy
+    # the partial rows are produced for `grad_rows_group` channels per launch: every rows launch streams the view's weight
+    # tiles from HBM once for all of its 128-channel slices (they share them through L2), so wider groups re-read them less
+    # often -- and deliver their first range later; the reduce stage and the exchange keep the narrower range either way
+    group = max(int(rctx.grad_rows_group), 1)
+    rows_done = 0
+    for c0, c1 in ranges:
+        if c1 > rows_done:
+            g1 = rows_done
+            while g1 < c1 or (g1 - rows_done < group and g1 < fwd.d):
+                g1 = next(b for a, b in ranges if a == g1)
+            for stage in ((_lib.GAGS_STAGE_ROWS, _lib.GAGS_STAGE_SORT) if rows_done == 0 else (_lib.GAGS_STAGE_ROWS,)):
+                with profiler.stage(_STAGE_NAMES[stage]):
+                    call(stage | bits, rows_done, g1 - rows_done)
+            rows_done = g1
+        # the rows the ranks exchange leave from the reduce kernel itself (no pack pass over the range afterwards)
+        w = wire_hook(c0, c1) if wire_hook is not None else None
+        if w is None and kept is not None:
+            # the exchange packs for itself after all (bf16 wire, all rows): its sum may land in rows the flags do not
+            # cover.  This step's reduce writes every row; the buffer is not kept
+            rctx.forget_kept(fwd.n, fwd.d, v_colors.dtype, v_colors.device)
+            kept = None
+        with profiler.stage("bwd_reduce"):
+            call(_lib.GAGS_STAGE_REDUCE | bits, c0, c1 - c0, None, w, kept)
+        if w is not None:
+            hook(alias, c0, c1, w[1])
+        else:
+            hook(alias, c0, c1)
+
+
+def _backward_staged(lib, rctx, fwd, v_out, stage_bits=0, prezero=None, exact_rows=False, early=None):
+    """Colours-only backward without atomics: hit flags of the forward -> prefix sum (one row per (tile, Gaussian)
+    pair that blended anything) -> the total of rows (_row_count) -> merged partial rows -> sort by Gaussian ->
+    segmented sum.  fwd: the forward's _FwdState; stage_bits: _stage_bits(); prezero, early: what the forward prepared
+    (a zero-filled gradient, the row map); exact_rows: the re-run of a capacity-mode backward whose capacity was too small."""
+    dev = v_out.device
+    n, d = fwd.n, fwd.d
+    hook = rctx.grad_range_hook
+    if rctx.grad_rows_hook is not None and hook is not None:
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        check(lib.gags_blended_mask(fwd.n_isects, fwd.width, fwd.height, n, ptr(fwd.flatten_ids), ptr(fwd.fwd_scratch),
+                                    fwd.fwd_scratch.numel(), ptr(mask), _stream()), "gags_blended_mask")
+        rctx.grad_rows_hook(mask)  # before the readback below: the ranks agree on the union while the backward starts
+    ranges = _channel_ranges(d, rctx.grad_range_channels) if hook is not None else None
+    cap_key = (n, fwd.width, fwd.height, dev.index)
+    capacity = rctx.cap_rows.get(cap_key) if (rctx.capacity_mode and hook is None and not exact_rows) else None
+    trow, total, rows, pending = _row_count(lib, rctx, fwd, early, capacity)
+    # a heavy view's partial rows ([rows, D] fp32) can outgrow the device (C5H: 80 M rows x 2 KB): beyond PROW_MAX_BYTES the
+    # gradient is produced one 128-channel range at a time through a [rows, 128] scratch (GAGS_STAGED_RANGE_SCRATCH)
+    narrow = (hook is None and pending is None and d % 128 == 0 and d > 128 and rows * d * 4 > PROW_MAX_BYTES)
+    nbytes = lib.gags_bwd_staged_scratch_bytes(rows, n, 128 if narrow else d)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    wire_hook = rctx.grad_wire_hook if (ranges is not None and not (stage_bits & _lib.GAGS_STAGED_OUT_F16)) else None
+    v_colors, kept, bits = _grad_buffer(rctx, fwd, stage_bits, dev, hook, wire_hook, pending, prezero)
+    call = _bind_staged(lib, fwd, v_out, trow, rows, scratch, v_colors)
+    if narrow:
+        _run_range_scratch(call, bits, d, kept)
+    elif ranges is not None:
+        _run_ranged(call, rctx, fwd, bits, ranges, hook, wire_hook, kept, v_colors)
+    else:
+        _run_whole(call, bits, d, ptr(total) if pending is not None else None, kept, hook, v_colors)
     if pending is not None:
         true_rows = pending.get()
         if true_rows > rows:  # more rows than the remembered capacity (none was stored out of bounds): again, exact
             rctx.cap_rows[cap_key] = true_rows
-            return _backward_staged(lib, rctx, offsets, n_isects, blk_rows, fwd_scratch, v_out, n, d, width, height, xflag & ~128,
-                                    flatten_ids, None, exact_rows=True)
+            return _backward_staged(lib, rctx, fwd, v_out, stage_bits, None, exact_rows=True)
         rows = true_rows
     if hook is None and rctx.capacity_mode:
         rctx.cap_rows[cap_key] = max(rows, int(0.97 * rctx.cap_rows.get(cap_key, 0)))
@@ -1061,44 +1132,44 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         with torch.no_grad(), profiler.stage("binning"):
             b = tile_binning(means2d, radii, depths, tiles, width, height, conics if wide else None,
                              _c(opacities) if wide else None, cap, records=records if wide else None, context=rctx)
-        offs, flat = b[5], b[1]
+        offs, flat = b.offsets_full, b.flatten_ids
         # heavy views: the lists cut to what their tiles read (_trim_lists) -- the raster passes, their scratch and the backward
         # work on the cut lists; callers still get the full ones in `info`
         trimmed = None
         n_full = flat.shape[0]
-        if (cap is None and wide and b[4] is not None and n_full > 0 and rctx.trim_lists is not False
+        if (cap is None and wide and b.packed is not None and n_full > 0 and rctx.trim_lists is not False
                 and not (raster_flags & (_lib.GAGS_FWD_NO_MFMA | _lib.GAGS_FWD_FUSED))):
             lib_ = _lib.load()
             if rctx.trim_lists or lib_.gags_raster_fwd_scratch_bytes(n_full, width, height) > TRIM_AUTO_BYTES:
                 with torch.no_grad():
-                    trimmed = _trim_lists(lib_, n, width, height, offs, flat, n_full, b[4])
+                    trimmed = _trim_lists(lib_, n, width, height, offs, flat, n_full, b.packed)
                 offs, flat = trimmed[0], trimmed[1]
         # any width in ONE rasterization: 513 = 512 CLIP channels + 1 (BASELINE.json configs[4] "512-d feat + granularity")
         # is four 128-channel slices and one lane of a narrow slice on the same matrix-core kernels, into one output tensor
-        r = _Rasterize.apply(means2d, conics, cols, opacities, bg, offs, flat, b[4], width, height, int(raster_flags), prezero,
+        r = _Rasterize.apply(means2d, conics, cols, opacities, bg, offs, flat, b.packed, width, height, int(raster_flags), prezero,
                              rctx, None, torch.is_grad_enabled())
         if trimmed is not None:
             # last_ids are sorted indices: a COPY goes back to the full lists' numbering for the caller (the autograd node keeps
             # its own, which matches the lists it saved)
             with torch.no_grad():
                 last_user = r[2].clone()
-                check(_lib.load().gags_trim_last_ids(width, height, ptr(b[5]), ptr(offs), ptr(r[1]), ptr(last_user), _stream()),
+                check(_lib.load().gags_trim_last_ids(width, height, ptr(b.offsets_full), ptr(offs), ptr(r[1]), ptr(last_user), _stream()),
                       "gags_trim_last_ids")
             profiler.note("isects_trimmed", trimmed[2])
             r = (r[0], r[1], last_user, trimmed[2])
         else:
             r = (r[0], r[1], r[2], None)
-        return b[:5], r
+        return b, r
 
     cap = None
     if rctx.capacity_mode and cap_key in rctx.cap_isects:
         cap = min(MAX_ISECTS - 1, int(rctx.cap_isects[cap_key] * CAP_MARGIN) + 4096)
-    (isect_ids, flatten_ids, isect_offsets, n_isects, packed), (out, alphas, last_ids, n_trimmed) = run(cap)
+    (isect_ids, flatten_ids, isect_offsets, n_isects, packed, _), (out, alphas, last_ids, n_trimmed) = run(cap)
     if cap is not None:
         n_true = n_isects.get()  # (the scan that produced it finished long ago: everything above is already enqueued)
-        _check_isects(n_true, ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE))
+        _check_isects(n_true, _tiles(width, height)[2])
         if n_true > cap:  # more intersections than the remembered capacity: nothing was written out of bounds; run again, exact
-            (isect_ids, flatten_ids, isect_offsets, n_isects, packed), (out, alphas, last_ids, n_trimmed) = run(None)
+            (isect_ids, flatten_ids, isect_offsets, n_isects, packed, _), (out, alphas, last_ids, n_trimmed) = run(None)
         else:
             n_isects = n_true
             isect_ids, flatten_ids = isect_ids[:n_true], flatten_ids[:n_true]
@@ -1111,7 +1182,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             check(_lib.load().gags_ed_normalize(height * width, out.shape[-1], ptr(out), ptr(alphas), _stream()),
                   "gags_ed_normalize")
 
-    tile_w, tile_h = (width + TILE - 1) // TILE, (height + TILE - 1) // TILE
+    tile_w, tile_h, _ = _tiles(width, height)
     info = {
         "camera_ids": None, "gaussian_ids": None,
         "radii": radii[None], "means2d": means2d_c, "depths": depths[None], "conics": conics[None],

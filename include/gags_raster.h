@@ -222,29 +222,7 @@ int gags_raster_bwd(int d, int width, int height, const float *means2d, const fl
  * row count `rows` (read it with gags_read_i32).  rowmap: gags_bwd_rowmap_elems(...) int32;
  * scratch: gags_bwd_rowmap_scratch_bytes(n_isects) bytes.
  *
- * blk_rows (as gags_raster_fwd wrote it: four int32 per tile) must be 16-byte aligned: a tile's four counts are one load.
- * gags_raster_bwd_colors_staged: per tile the four pixel blocks' partial rows are merged on chip and stored
- * once per (tile, Gaussian), the rows are sorted by Gaussian and reduced; v_colors[N,D] is written in full
- * (no zero-fill needed).  scratch: gags_bwd_staged_scratch_bytes(rows, n, d) bytes.
- * stage: low 4 bits 0 = all, 1..3 = rows, sort, reduce (per-kernel timing, overlap of the zero-fill below).
- * The rows' contraction (128-channel slices) runs on the 16-bit matrix cores with fp32-equivalent split operands (fp16
- * terms after exact power-of-two scalings -- per (tile, channel) for the cotangent; for the weights, which lie in [2^-21.3, 1),
- * the constant 2^15 since round 6 --, fp32 accumulation; see the bits below for the number of terms); atomic-free and
- * bit-reproducible.  Shape since round 5: a wave per 32 channels of the slice, the four pixel blocks'
- * contributions to a tile row meet in its accumulators (csrc/raster_bwd_rows_cw.h).  bit 5 (32): the fp32 matrix
- * instructions instead (rounds 1-2's kernel).  bit 9 (512): round 4's shape (a wave per pixel block, rows merged in LDS;
- * weights as three terms, five product terms).  The default shape multiplies THREE product terms of two-term operands (one
- * fp32-level rounding per operand, the second-order term dropped: <= 3 * 2^-24 per product; 1.68e-7 of float64 against the fp32
- * matrix instructions' 1.90e-7); bit 10 (1024): the default shape with exact three-term weights and five product terms.
- * bit 6 (64): v_colors points to an fp16 [N,D] tensor (the gradient of an fp16 feature table in the table's dtype;
- * sums are formed in fp32 and rounded once).
- * bit 7 (128): v_colors arrives ZERO-FILLED and the reduce stage skips the Gaussians that blended nothing (73 % at C3)
- * instead of writing their rows of zeros -- the caller fills it on a second stream while the rows stage runs.
- * bit 8 (256), with gags_raster_bwd_colors_staged_range / _cap: the scratch holds the partial rows of THIS call's channel
- * range only -- [rows, ch_count] instead of [rows, D]; size it with gags_bwd_staged_scratch_bytes(rows, n, ch_count) -- so
- * that a wide gradient can be produced range by range (stages 1, 2, 3 for the first range, 1 and 3 for the others)
- * through a quarter of the memory: a heavy view's rows (80 M x 2 KB at D = 512) need not exist at once.
- * Returns 1 when D is not eligible. */
+ * The backward itself: gags_raster_bwd_colors_staged below. */
 int64_t gags_bwd_rowmap_elems(int64_t n_isects, int width, int height);
 int64_t gags_bwd_rowmap_scratch_bytes(int64_t n_isects);
 int gags_bwd_rowmap(int64_t n_isects, int width, int height, const int32_t *isect_offsets, const int32_t *blk_rows,
@@ -256,7 +234,7 @@ int gags_bwd_rowmap(int64_t n_isects, int width, int height, const int32_t *isec
  * matrix cores: by default the 16-bit ones with split operands (feature rows and cotangent as two fp16 terms each after
  * exact power-of-two scalings -- one per Gaussian row, one per 8x8 block -- and three product terms: as close to float64 as
  * fp32 matrix arithmetic), with
- * flags bit 5 (32) the fp32 matrix instructions (rounds 1-2's kernel); the per-pair chain uses the forward's own weights (T = weight / alpha: front-to-back quantities,
+ * flags bit GAGS_GEOM_F32MFMA the fp32 matrix instructions (rounds 1-2's kernel); the per-pair chain uses the forward's own weights (T = weight / alpha: front-to-back quantities,
  * not 1 - render_alpha rebuilt back to front).  Together with gags_raster_bwd_colors_staged this replaces
  * gags_raster_bwd when geometry needs grad at wide D (gsplat's rasterize_to_pixels backward [EXT]).
  * backgrounds / v_render_alphas may be NULL.  row_base (optional, [tile_h*tile_w*4] int32 = exclusive prefix sum of
@@ -267,6 +245,7 @@ int gags_bwd_rowmap(int64_t n_isects, int width, int height, const int32_t *isec
  * like the rows (256 B per blended slot and 256-channel pass: 2.3 GB at C3, D = 512), without it they live in a copy of
  * the forward's sparse slot space (~1.1 KB per tile intersection and pass); + 1.5 KB per Gaussian for the split table.
  * Returns 1 when D is not eligible. */
+#define GAGS_GEOM_F32MFMA 32 /* gags_raster_bwd_geom's `flags`, next to GAGS_RECS_BY_GAUSSIAN */
 int64_t gags_raster_bwd_geom_scratch_bytes(int64_t n_isects, int width, int height, int n, int d, int64_t n_rows);
 int gags_raster_bwd_geom(int d, int n, int width, int height, const float *colors, const float *backgrounds,
                          const int32_t *isect_offsets, int64_t n_isects, const void *packed,
@@ -280,59 +259,86 @@ int gags_raster_bwd_geom(int d, int n, int width, int height, const float *color
  * exchanges only the union of these rows over the ranks (gags_amd/dist.py; SURVEY 8e "gradients are sparse in rows"). */
 int gags_blended_mask(int64_t n_isects, int width, int height, int n, const int32_t *flatten_ids,
                       const void *fwd_scratch, int64_t fwd_scratch_bytes, unsigned char *mask, void *stream);
+/* K10, staged flavour, the backward itself: per tile the four pixel blocks' partial rows are merged on chip and stored once
+ * per (tile, Gaussian) ("rows"), the rows are sorted by Gaussian ("sort") and summed per Gaussian ("reduce").  No atomics,
+ * bit-reproducible.  The rows' contraction (128-channel slices) runs on the 16-bit matrix cores with fp32-equivalent split
+ * operands (fp16 terms after exact power-of-two scalings -- per (tile, channel) for the cotangent; for the weights, which lie
+ * in [2^-21.3, 1), the constant 2^15 since round 6 --, fp32 accumulation; see the bits below for the number of terms).  Shape
+ * since round 5: a wave per 32 channels of the slice, the four pixel blocks' contributions to a tile row meet in its
+ * accumulators (csrc/raster_bwd_rows_cw.h); it multiplies THREE product terms of two-term operands (one fp32-level rounding
+ * per operand, the second-order term dropped: <= 3 * 2^-24 per product; 1.68e-7 of float64 against the fp32 matrix
+ * instructions' 1.90e-7).  Returns 1 when D is not eligible (16 <= D <= 1024, any such D); GAGS_ESCRATCH when a scratch is too
+ * small.  One entry; a trailing pointer that is NULL switches its feature off.  By argument:
+ *
+ * blk_rows, fwd_scratch
+ *     as a split gags_raster_fwd left them.  blk_rows (four int32 per tile) must be 16-byte aligned: a tile's four counts
+ *     are one load.
+ * rowmap, rows
+ *     gags_bwd_rowmap's map and the row count it left in total[0].
+ * scratch
+ *     gags_bwd_staged_scratch_bytes(rows, n, d) bytes; the same scratch for every call of a view.
+ * v_colors
+ *     [N,D], written in full (no zero-fill needed) unless a bit or pointer below says otherwise.
+ * stage
+ *     (stage & GAGS_STAGE_MASK): GAGS_STAGE_ALL, or one of GAGS_STAGE_ROWS / _SORT / _REDUCE (per-kernel timing, range by
+ *     range production, overlap of the zero-fill below), OR-ed with any of
+ *     GAGS_STAGED_F32MFMA        rows on the fp32 matrix instructions instead (rounds 1-2's kernel).
+ *     GAGS_STAGED_BLOCKWAVES     rows in round 4's shape (a wave per pixel block, rows merged in LDS; weights as three terms,
+ *                                five product terms).
+ *     GAGS_STAGED_EXACT_WEIGHTS  the default shape with exact three-term weights and five product terms.
+ *     GAGS_STAGED_OUT_F16        v_colors points to an fp16 [N,D] tensor (the gradient of an fp16 feature table in the
+ *                                table's dtype; sums are formed in fp32 and rounded once).
+ *     GAGS_STAGED_PREZEROED      v_colors arrives ZERO-FILLED and the reduce stage skips the Gaussians that blended nothing
+ *                                (73 % at C3) instead of writing their rows of zeros -- the caller fills it on a second
+ *                                stream while the rows stage runs.
+ *     GAGS_STAGED_RANGE_SCRATCH  the scratch holds the partial rows of THIS call's channel range only -- [rows, ch_count]
+ *                                instead of [rows, D]; size it with gags_bwd_staged_scratch_bytes(rows, n, ch_count) -- so
+ *                                that a wide gradient can be produced range by range (stages rows, sort, reduce for the
+ *                                first range, rows and reduce for the others) through a quarter of the memory: a heavy
+ *                                view's rows (80 M x 2 KB at D = 512) need not exist at once.
+ * ch_begin, ch_count
+ *     channels [ch_begin, ch_begin + ch_count) only (whole 128- / 64- / 32-channel slices, as D % 128 / 64 allows; the last
+ *     range may end at D): v_colors[:, ch_begin : ch_begin + ch_count] is written; (0, d) = everything.  A multi-GPU by-view
+ *     step calls range after range -- stages rows, sort, reduce for the range that starts at 0 (it writes the row ->
+ *     Gaussian keys the sort needs), rows and reduce for the others -- and exchanges each range while the next is computed
+ *     (gags_amd/dist.py).
+ * rows_dev
+ *     `rows` is a CAPACITY and the true row count lives on the device (rows_dev = gags_bwd_rowmap's total; NULL: rows is
+ *     exact): rows past the capacity are dropped, the keys between the count and the capacity become sentinels.  Read the
+ *     count afterwards; if it exceeds the capacity run the backward again.
+ * wire_pos, wire (both or neither; not with GAGS_STAGED_OUT_F16: the block is fp32)
+ *     the reduce stage ALSO writes the rows a by-view multi-GPU step exchanges (gags_amd/dist.py):
+ *     wire[wire_pos[g], :] = the range's gradient row of Gaussian g for every g with wire_pos[g] >= 0 -- wire is a dense
+ *     fp32 [union rows, ch_count] block (ch_count % 4 == 0), wire_pos the inverse of the union's row list
+ *     (gags_compact_mask_pos).  Every row of the block is written (a union row this view did not touch gets zeros), so the
+ *     block needs no clearing and no pack kernel re-reads the gradient.  v_colors is written as always.
+ * keep_prev, keep_cur (both or neither, two different arrays of n bytes; not with GAGS_STAGED_PREZEROED)
+ *     v_colors is a PERSISTENT gradient buffer (round 6) the caller keeps between steps, all zeros except the rows the
+ *     previous call wrote -- keep_prev[g] != 0 (all zeros for a freshly zeroed buffer).  The reduce stage writes the rows
+ *     that have partial rows now, re-zeroes the rows that had some last time and none now, touches nothing else (the rows of
+ *     Gaussians that blend nothing -- 73 % at C3, 2.2 GB of zeros per step -- are never written again), and leaves
+ *     keep_cur[g] for the next call.  Same values as without, bit for bit.  With wire: a row counts as written when it has
+ *     partial rows OR lies in the exchanged block (the caller writes the ranks' sum there).  The caller must know that
+ *     nobody else wrote the buffer in between (gags_amd/rasterization.py checks the storage's reference count and version
+ *     counter and passes NULL otherwise). */
+#define GAGS_STAGE_ALL 0
+#define GAGS_STAGE_ROWS 1
+#define GAGS_STAGE_SORT 2
+#define GAGS_STAGE_REDUCE 3
+#define GAGS_STAGE_MASK 15
+#define GAGS_STAGED_F32MFMA 32
+#define GAGS_STAGED_OUT_F16 64
+#define GAGS_STAGED_PREZEROED 128
+#define GAGS_STAGED_RANGE_SCRATCH 256
+#define GAGS_STAGED_BLOCKWAVES 512
+#define GAGS_STAGED_EXACT_WEIGHTS 1024
 int64_t gags_bwd_staged_scratch_bytes(int64_t rows, int n, int d);
-int gags_raster_bwd_colors_staged(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                  int64_t n_isects, const float *v_render_colors,
-                                  const int32_t *blk_rows, const int32_t *rowmap, int64_t rows,
-                                  const void *fwd_scratch, int64_t fwd_scratch_bytes,
-                                  void *scratch, int64_t scratch_bytes, float *v_colors, int stage,
+int gags_raster_bwd_colors_staged(int d, int n, int width, int height, const int32_t *isect_offsets, int64_t n_isects,
+                                  const float *v_render_colors, const int32_t *blk_rows, const int32_t *rowmap, int64_t rows,
+                                  const void *fwd_scratch, int64_t fwd_scratch_bytes, void *scratch, int64_t scratch_bytes,
+                                  float *v_colors, int stage, int ch_begin, int ch_count, const int32_t *rows_dev,
+                                  const int32_t *wire_pos, float *wire, const uint8_t *keep_prev, uint8_t *keep_cur,
                                   void *stream);
-/* The same for channels [ch_begin, ch_begin + ch_count) only (whole 128- / 64- / 32-channel slices, as D % 128 / 64
- * allows; the last range may end at D): v_colors[:, ch_begin : ch_begin + ch_count] is written.  A multi-GPU by-view
- * step calls it range after range -- stage 1, 2, 3 for the range that starts at 0 (it writes the row -> Gaussian
- * keys the sort needs), stage 1 and 3 for the others -- and exchanges each range while the next is computed
- * (gags_amd/dist.py).  Same scratch for every range of a view. */
-int gags_raster_bwd_colors_staged_range(int d, int n, int width, int height, const int32_t *isect_offsets,
-                                        int64_t n_isects, const float *v_render_colors,
-                                        const int32_t *blk_rows, const int32_t *rowmap, int64_t rows,
-                                        const void *fwd_scratch, int64_t fwd_scratch_bytes,
-                                        void *scratch, int64_t scratch_bytes, float *v_colors, int stage,
-                                        int ch_begin, int ch_count, void *stream);
-/* The same with `rows` as a CAPACITY and the true row count on the device (rows_dev = gags_bwd_rowmap's total; NULL:
- * rows is exact): rows past the capacity are dropped, the keys between the count and the capacity become sentinels.  Read
- * the count afterwards; if it exceeds the capacity run the backward again. */
-int gags_raster_bwd_colors_staged_cap(int d, int n, int width, int height, const int32_t *isect_offsets, int64_t n_isects,
-                                      const float *v_render_colors, const int32_t *blk_rows, const int32_t *rowmap,
-                                      int64_t rows, const void *fwd_scratch, int64_t fwd_scratch_bytes, void *scratch,
-                                      int64_t scratch_bytes, float *v_colors, int stage, int ch_begin, int ch_count,
-                                      const int32_t *rows_dev, void *stream);
-
-/* gags_raster_bwd_colors_staged_range whose reduce stage ALSO writes the rows a by-view multi-GPU step exchanges
- * (gags_amd/dist.py): wire[wire_pos[g], :] = the range's gradient row of Gaussian g for every g with
- * wire_pos[g] >= 0 -- wire is a dense fp32 [union rows, ch_count] block (ch_count % 4 == 0), wire_pos the inverse of the
- * union's row list (gags_compact_mask_pos).  Every row of the block is written (a union row this view did not touch gets
- * zeros), so the block needs no clearing and no pack kernel re-reads the gradient.  v_colors is written as always -- or,
- * with keep_prev / keep_cur (both or neither; see gags_raster_bwd_colors_staged_keep below), as a persistent buffer whose
- * rows count as written when they have partial rows OR lie in the exchanged block (the caller writes the ranks' sum there). */
-int gags_raster_bwd_colors_staged_wire(int d, int n, int width, int height, const int32_t *isect_offsets, int64_t n_isects,
-                                       const float *v_render_colors, const int32_t *blk_rows, const int32_t *rowmap,
-                                       int64_t rows, const void *fwd_scratch, int64_t fwd_scratch_bytes, void *scratch,
-                                       int64_t scratch_bytes, float *v_colors, int stage, int ch_begin, int ch_count,
-                                       const int32_t *wire_pos, float *wire, const uint8_t *keep_prev, uint8_t *keep_cur,
-                                       void *stream);
-
-/* gags_raster_bwd_colors_staged_range into a PERSISTENT gradient buffer (round 6): v_colors is a buffer the caller keeps
- * between steps, all zeros except the rows the previous call wrote -- keep_prev[g] != 0 (n bytes; all zeros for a freshly
- * zeroed buffer).  The reduce stage writes the rows that have partial rows now, re-zeroes the rows that had some last time
- * and none now, touches nothing else (the rows of Gaussians that blend nothing -- 73 % at C3, 2.2 GB of zeros per step --
- * are never written again), and leaves keep_cur[g] (n bytes, another array) for the next call.  Same values as the plain
- * entry, bit for bit.  The caller must know that nobody else wrote the buffer in between (gags_amd/rasterization.py checks
- * the storage's reference count and version counter and falls back to the plain entry otherwise). */
-int gags_raster_bwd_colors_staged_keep(int d, int n, int width, int height, const int32_t *isect_offsets, int64_t n_isects,
-                                       const float *v_render_colors, const int32_t *blk_rows, const int32_t *rowmap,
-                                       int64_t rows, const void *fwd_scratch, int64_t fwd_scratch_bytes, void *scratch,
-                                       int64_t scratch_bytes, float *v_colors, int stage, int ch_begin, int ch_count,
-                                       const uint8_t *keep_prev, uint8_t *keep_cur, void *stream);
 
 /* Diagnostics (roofline model): counts[0] += (pixel,Gaussian) pairs evaluated
  * before each pixel's stop, counts[1] += pairs blended.  counts[2] int64, zeroed by caller. */
@@ -411,8 +417,8 @@ int64_t gags_compact_mask_scratch_bytes(int n);
 int gags_compact_mask(int n, const uint8_t *mask, int64_t cap, int64_t *idx, int32_t *count, void *scratch,
                       int64_t scratch_bytes, void *stream);
 /*   gags_compact_mask_pos: the same, and the inverse on the way: pos[r] (n int32, written in full) = the position of row r
- *                     in idx, -1 for rows that are not set or whose position is >= cap (gags_raster_bwd_colors_staged_wire
- *                     writes the exchanged rows through it). */
+ *                     in idx, -1 for rows that are not set or whose position is >= cap (gags_raster_bwd_colors_staged
+ *                     writes the exchanged rows through it: wire_pos). */
 int gags_compact_mask_pos(int n, const uint8_t *mask, int64_t cap, int64_t *idx, int32_t *pos, int32_t *count, void *scratch,
                           int64_t scratch_bytes, void *stream);
 int gags_pack_rows(int64_t n_rows, const int64_t *idx, const void *grad, int grad_type, int d, int c0, int cw,

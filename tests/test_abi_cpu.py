@@ -87,17 +87,35 @@ def test_argument_validation_returns_codes_without_launching(lib):
     assert lib.gags_compact_mask_pos(-1, None, 0, None, None, None, None, 0, None) == -1
     assert lib.gags_compact_mask_pos(8, None, 1 << 31, None, None, None, None, 0, None) == -1   # capacity past int32 positions
     staged = (128, 8, 16, 16, None, 0, None, None, None, 0, None, 0, None, 0, None, 3, 0, 128)
-    assert lib.gags_raster_bwd_colors_staged_wire(*staged, None, None, None, None, None) == -1
-    assert lib.gags_raster_bwd_colors_staged_keep(*staged, None, None, None) == -1            # both flag arrays are required
+    assert lib.gags_raster_bwd_colors_staged(*staged, None, None, None, None, None, None) == -1
     # the staged backward wants the forward's per-block slot counts 16-byte aligned (one scalar load per tile)
     import ctypes
     buf = (ctypes.c_int32 * 64)()
     base = ctypes.addressof(buf)
     al = base + (-base % 16)
     P = ctypes.c_void_p
-    common = dict(pre=(128, 8, 16, 16, P(al), 0, P(al)), post=(P(al), 0, P(al), 0, P(al), 0, P(al), 3))
-    assert lib.gags_raster_bwd_colors_staged(*common["pre"], P(al + 4), *common["post"], None) == -1
-    assert lib.gags_raster_bwd_colors_staged(*common["pre"], P(al), *common["post"], None) == -3   # (aligned: on to the scratch-size check)
+    from gags_amd import _lib
+    common = dict(pre=(128, 8, 16, 16, P(al), 0, P(al)), post=(P(al), 0, P(al), 0, P(al), 0, P(al)))
+
+    def staged_call(blk_rows=al, stage=_lib.GAGS_STAGE_REDUCE, wire_pos=None, wire=None, keep_prev=None, keep_cur=None):
+        """The one staged entry on otherwise valid dummy pointers and scratch_bytes = 0: a call that passes validation stops at
+        GAGS_ESCRATCH (-3), so a -1 is the rule under test and not a NULL elsewhere."""
+        opt = [None if a is None else P(a) for a in (wire_pos, wire, keep_prev, keep_cur)]
+        return lib.gags_raster_bwd_colors_staged(*common["pre"], P(blk_rows), *common["post"], stage, 0, 128, None, *opt, None)
+    assert staged_call(blk_rows=al + 4) == -1
+    assert staged_call() == -3   # (aligned: on to the scratch-size check)
+    # what used to be decided by WHICH staged entry was called: the optional pointers come in pairs ...
+    assert staged_call(keep_prev=al, keep_cur=al + 16) == -3
+    assert staged_call(keep_prev=al) == -1
+    assert staged_call(keep_cur=al + 16) == -1
+    assert staged_call(keep_prev=al, keep_cur=al) == -1                                               # one array for both
+    assert staged_call(keep_prev=al, keep_cur=al + 16, stage=_lib.GAGS_STAGE_REDUCE | _lib.GAGS_STAGED_PREZEROED) == -1    # a kept buffer is not pre-zeroed
+    assert staged_call(stage=_lib.GAGS_STAGE_REDUCE | _lib.GAGS_STAGED_PREZEROED) == -3
+    assert staged_call(wire_pos=al, wire=al + 16) == -3
+    assert staged_call(wire=al + 16) == -1
+    assert staged_call(wire_pos=al) == -1
+    assert staged_call(wire_pos=al, wire=al + 16, stage=_lib.GAGS_STAGE_REDUCE | _lib.GAGS_STAGED_OUT_F16) == -1           # the wire block is fp32
+    assert staged_call(stage=_lib.GAGS_STAGE_REDUCE | _lib.GAGS_STAGED_OUT_F16) == -3
     assert lib.gags_decoder_layer_split(8, 4, 4, *([None] * 2), 4, *([None] * 2), 1, *([None] * 4), 4, 5, None) == -1   # terms = 5
     assert lib.gags_decoder_wgrad_split(8, 4, 4, None, 4, None, None, 4, None, None, None, 0, 1, None) == -1            # terms = 1
     # round 6, second half: the iteration's entries
@@ -247,6 +265,26 @@ def test_cpu_twins_share_the_c_abi_signatures(oracle):
     # error convention of the ABI: a bad argument is a code, not a crash
     assert fn["gags_raster_fwd"](0, n, w, h, None, None, None, None, None, None, None, 0, None, None, None, None, None, 0, None, 0,
                                  None) == -1
+
+
+def test_stage_bits_of_the_staged_backward_agree_with_the_header():
+    """The `stage` argument of gags_raster_bwd_colors_staged is an OR of a stage number and flag bits: the header defines them,
+    gags_amd/_lib.py mirrors them, and nothing else checks that the two sides agree.  The flag bits are distinct powers of two
+    above the stage mask; gags_raster_bwd_geom's one flag of the same kind is compared too."""
+    from gags_amd import _lib
+    src = open(os.path.join(ROOT, "include", "gags_raster.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"^#define\s+(GAGS_(?:STAGE|STAGED|GEOM)_\w+)\s+(\d+)\b", src, flags=re.M)}
+    stages = ["GAGS_STAGE_ALL", "GAGS_STAGE_ROWS", "GAGS_STAGE_SORT", "GAGS_STAGE_REDUCE", "GAGS_STAGE_MASK"]
+    bits = ["GAGS_STAGED_F32MFMA", "GAGS_STAGED_OUT_F16", "GAGS_STAGED_PREZEROED", "GAGS_STAGED_RANGE_SCRATCH",
+            "GAGS_STAGED_BLOCKWAVES", "GAGS_STAGED_EXACT_WEIGHTS"]
+    assert sorted(defs) == sorted(stages + bits + ["GAGS_GEOM_F32MFMA"]), sorted(defs)
+    for name, value in defs.items():
+        assert getattr(_lib, name) == value, name
+    assert [defs[s] for s in stages] == [0, 1, 2, 3, 15]
+    vals = [defs[b] for b in bits]
+    assert vals == [32, 64, 128, 256, 512, 1024]  # (the ABI)
+    assert all(v & (v - 1) == 0 and not (v & defs["GAGS_STAGE_MASK"]) for v in vals) and len(set(vals)) == len(vals)
+    assert defs["GAGS_GEOM_F32MFMA"] & (defs["GAGS_GEOM_F32MFMA"] - 1) == 0 and defs["GAGS_GEOM_F32MFMA"] != _lib.GAGS_RECS_BY_GAUSSIAN
 
 
 def test_python_side_raster_flags_are_distinct_bits():

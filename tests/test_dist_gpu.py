@@ -384,7 +384,7 @@ def test_compact_mask_is_the_ascending_nonzero_list(n, p):
 
 
 def test_reduce_stage_writes_the_exchanged_rows_itself():
-    """gags_raster_bwd_colors_staged_wire (round 6): under the by-view step the reduce kernel of a channel range also writes
+    """wire_pos / wire of gags_raster_bwd_colors_staged (round 6): under the by-view step the reduce kernel of a channel range also writes
     the block the ranks exchange -- row pos[g] of a dense [union rows, range] fp32 block for every Gaussian of the union --
     so no pack kernel re-reads the gradient.  Driven through the hooks of a RasterContext as gags_amd/dist.py drives them:
     every block equals the gradient's rows (zeros for union rows this view did not touch), with 128- and 256-channel ranges

@@ -449,6 +449,22 @@ def test_backward_by_channel_ranges_is_bit_identical(oracle):
     assert [(c0, c1) for _, c0, c1 in seen] == [(0, 128), (128, 256), (256, 384)]
     assert len({p for p, _, _ in seen}) == 1
     np.testing.assert_array_equal(g_rng["colors"], g_full["colors"])
+    # a width the ranges do not divide (200 is no multiple of 128): the hook gets the whole gradient in one piece, once --
+    # also when the stages are launched one by one for the profiler (that branch used to forget the hook)
+    from gags_amd import profiler
+    d = 200
+    s = scene_arrays(n, d, w, h, seed=42, view=3, scale_mult=5.0)
+    v_out = np.random.default_rng(10).standard_normal((h, w, d)).astype(np.float32)
+    _, _, _, g_plain = _run_gpu(s, w, h, s["colors"], None, v_out=v_out)
+    try:
+        for profiled in (False, True):
+            profiler.enable(profiled)
+            del seen[:]
+            _, _, _, g_hook = _run_gpu(s, w, h, s["colors"], None, v_out=v_out, context=rctx)
+            assert [(c0, c1) for _, c0, c1 in seen] == [(0, d)], (profiled, seen)
+            np.testing.assert_array_equal(g_hook["colors"], g_plain["colors"])
+    finally:
+        profiler.enable(False)
 
 
 def test_backward_through_a_range_sized_scratch_is_bit_identical(oracle):
@@ -1171,7 +1187,7 @@ def test_colour_backward_survives_cotangents_near_the_bottom_of_the_fp32_range()
 
 def test_persistent_gradient_buffer_is_bit_identical_and_gives_way_to_other_holders():
     """Round 6: the colours-only backward reduces into a buffer the RasterContext keeps between steps and writes only the
-    rows that have partial rows now or had some in the previous step (gags_raster_bwd_colors_staged_keep) -- the rows of
+    rows that have partial rows now or had some in the previous step (keep_prev / keep_cur of gags_raster_bwd_colors_staged) -- the rows of
     Gaussians that blend nothing (73 % at C3) are never written again.  Over alternating views (different rows every step) every
     gradient equals the plain entry's bit for bit; a gradient the caller still holds, or wrote to in place, is never
     overwritten: the step that finds the storage referenced or its version counter moved runs on a new buffer."""

@@ -22,18 +22,12 @@ cap = {}
 orig = R._backward_staged
 
 
-def spy(lib, rctx, offsets, n_isects, blk_rows, fwd_scratch, v_out, n_, d_, width, height, *extra, **kw):
-    # (*extra: whatever _backward_staged grew since -- flags, flatten_ids; passed through untouched)
-    ne = lib.gags_bwd_rowmap_elems(n_isects, width, height)
-    rm = torch.empty(ne, dtype=torch.int32, device=v_out.device)
-    tot = torch.empty(1, dtype=torch.int32, device=v_out.device)
-    sb = lib.gags_bwd_rowmap_scratch_bytes(n_isects)
-    tmp = torch.empty(max(sb, 4), dtype=torch.uint8, device=v_out.device)
-    R.check(lib.gags_bwd_rowmap(n_isects, width, height, R.ptr(offsets), R.ptr(blk_rows), R.ptr(fwd_scratch), fwd_scratch.numel(),
-                                R.ptr(rm), ne, R.ptr(tot), R.ptr(tmp), sb, None), "rowmap")
+def spy(lib, rctx, fwd, *a, **kw):
+    rm, _tot, _tmp = R._rowmap(lib, fwd)
     torch.cuda.synchronize()
-    cap.update(offsets=offsets.cpu().numpy().reshape(-1)[:-1], blk=blk_rows.cpu().numpy(), rm=rm.cpu().numpy(), I=n_isects)
-    return orig(lib, rctx, offsets, n_isects, blk_rows, fwd_scratch, v_out, n_, d_, width, height, *extra, **kw)
+    cap.update(offsets=fwd.offsets.cpu().numpy().reshape(-1)[:-1], blk=fwd.blk_rows.cpu().numpy(), rm=rm.cpu().numpy(),
+               I=fwd.n_isects)
+    return orig(lib, rctx, fwd, *a, **kw)
 
 
 R._backward_staged = spy

@@ -20,13 +20,13 @@ cap = {}
 orig = R.tile_binning
 def spy(*a, **k):
     out = orig(*a, **k)
-    cap["ids"], cap["packed"] = out[0], out[4][out[1].long()]  # per-Gaussian records -> per sorted intersection
+    cap["ids"], cap["packed"] = out.isect_ids, out.packed[out.flatten_ids.long()]  # per-Gaussian records -> per sorted intersection
     return out
 R.tile_binning = spy
 orig_b = R._backward_staged
-def spy_b(lib, rctx, offsets, n_isects, blk_rows, *a, **k):
-    cap["blk_rows"] = blk_rows.clone()
-    return orig_b(lib, rctx, offsets, n_isects, blk_rows, *a, **k)
+def spy_b(lib, rctx, fwd, *a, **k):
+    cap["blk_rows"] = fwd.blk_rows.clone()
+    return orig_b(lib, rctx, fwd, *a, **k)
 R._backward_staged = spy_b
 pkg = render(cam, pc, None, torch.zeros(3, device=dev), feature_mode=True)
 pkg["render"].sum().backward()
