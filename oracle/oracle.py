@@ -217,11 +217,15 @@ def sh_fwd(deg, means, campos, coeffs, radii=None):
 
 
 def rasterization(means, quats, scales, opacities, colors, viewmat, K, backgrounds, width, height,
-                  sh_degree=None, render_mode="RGB", tile_begin=0, tile_step=1):
+                  sh_degree=None, render_mode="RGB", tile_begin=0, tile_step=1, eps2d=0.3, near=0.01, far=1e10,
+                  radius_clip=0.0):
     """CPU restatement of `gsplat.rasterization(...)` as the reference calls it
     (/root/reference/gaussian_renderer/__init__.py:56-70), one camera, packed=False.
+    eps2d / near / far / radius_clip are gsplat's eps2d / near_plane / far_plane / radius_clip (defaults: the ones the
+    reference relies on by not passing them).
     Returns (render_colors [H,W,D'], render_alphas [H,W], info dict with every intermediate)."""
-    radii, means2d, depths, conics = project_fwd(means, quats, scales, viewmat, K, width, height)
+    radii, means2d, depths, conics = project_fwd(means, quats, scales, viewmat, K, width, height, eps2d=eps2d, near=near,
+                                                 far=far, radius_clip=radius_clip)
     opacities = _f32(opacities).reshape(-1)
     if sh_degree is not None:
         vm = np.asarray(viewmat, np.float64).reshape(4, 4)

@@ -22,6 +22,77 @@ def scene_arrays(n, d, width, height, seed=0, view=None, scale_mult=1.0, sh=Fals
     return out
 
 
+def _ypr_rotation(yaw, pitch, roll):
+    """Camera-to-world rotation Ry(yaw) Rx(pitch) Rz(roll), float64."""
+    cy_, sy_, cp, sp, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+    Ry = np.array([[cy_, 0.0, sy_], [0.0, 1.0, 0.0], [-sy_, 0.0, cy_]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, cp, -sp], [0.0, sp, cp]])
+    Rz = np.array([[cr, -sr, 0.0], [sr, cr, 0.0], [0.0, 0.0, 1.0]])
+    return Ry @ Rx @ Rz
+
+
+def general_scene(n, d, width, height, seed, *, fx, fy, cx, cy, ypr, centre, spread, scale_mult, z_range=(2, 12)):
+    """scene_arrays for a COLMAP-like camera: camera-to-world rotation R from (yaw, pitch, roll), camera centre C anywhere,
+    viewmat = [R^T | -R^T C], fx != fy and an arbitrary principal point.  The Gaussians are drawn in the camera frame --
+    pixel position uniform over `spread` x the image about its centre, unprojected through this K at a depth uniform in
+    `z_range` -- and moved to world coordinates; every other parameter is make_gaussians' for the seed.  spread > 1.3 puts
+    Gaussians beyond the tangent clamp of the projection (pixel outside [-0.15 W, 1.15 W], likewise in y)."""
+    R = _ypr_rotation(*ypr)
+    C = np.asarray(centre, np.float64)
+    vm = np.eye(4)
+    vm[:3, :3] = R.T
+    vm[:3, 3] = -R.T @ C
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32)
+    p = syn.make_gaussians(n, d, width, height, seed=seed, scale0=syn.SCALE0 * scale_mult)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed + 7919)
+    u = torch.rand(n, 3, generator=g, dtype=torch.float64).numpy()
+    px = 0.5 * width + (u[:, 0] - 0.5) * spread * width
+    py = 0.5 * height + (u[:, 1] - 0.5) * spread * height
+    z = z_range[0] + (z_range[1] - z_range[0]) * u[:, 2]
+    pc = np.stack([(px - cx) / fx * z, (py - cy) / fy * z, z], axis=1)
+    p["xyz"] = torch.from_numpy((pc @ R.T + C).astype(np.float32))
+    return dict(
+        means=p["xyz"].numpy(),
+        quats=torch.nn.functional.normalize(p["rotation"]).numpy(),
+        scales=p["scaling_log"].exp().numpy(),
+        opacities=torch.sigmoid(p["opacity_logit"]).reshape(-1).numpy(),
+        colors=None if d == 0 else p["semantic_feature"].numpy(),
+        sh=torch.cat([p["features_dc"], p["features_rest"]], dim=1).numpy(),
+        viewmat=vm.astype(np.float32), K=K, cam=None, raw=p, R=R, C=C)
+
+
+# General cameras shared by the CPU and the GPU tests, in units of the image (fx, fy, cx, cy are multiplied by W, W, W, H):
+# yaw / pitch / roll up to 2.5 rad, |C| up to ~10, fx/fy from 0.75 to 1.4, principal point off-centre and, in "pp_outside",
+# left of the image.
+GENERAL_CAMERAS = {
+    "pitch_roll": dict(fx=0.94, fy=0.70, cx=0.47, cy=0.54, ypr=(0.7, -0.4, 0.3), centre=(3.0, -1.5, 7.0), spread=1.5),
+    "behind": dict(fx=0.70, fy=0.92, cx=0.56, cy=0.42, ypr=(2.5, 1.1, -2.0), centre=(-6.0, 4.0, -5.0), spread=1.6),
+    "pp_outside": dict(fx=1.10, fy=0.78, cx=-0.15, cy=0.51, ypr=(-1.2, 0.5, 2.5), centre=(0.5, -9.0, 3.0), spread=1.9),
+    "upside_down": dict(fx=0.80, fy=0.95, cx=0.52, cy=0.62, ypr=(0.2, -2.2, 0.9), centre=(5.0, 5.0, -6.0), spread=1.7),
+}
+
+
+def general_camera(name, width, height):
+    """Keyword arguments of general_scene for one of GENERAL_CAMERAS at an image size."""
+    c = GENERAL_CAMERAS[name]
+    return dict(fx=c["fx"] * width, fy=c["fy"] * width, cx=c["cx"] * width, cy=c["cy"] * height, ypr=c["ypr"],
+                centre=c["centre"], spread=c["spread"])
+
+
+def clamp_census(s, width, height, radii):
+    """(visible Gaussians with an active tangent clamp in x, in y, visible, culled) for a scene and the radii it produced:
+    float64 restatement of the limits of SURVEY A3 (x/z outside [-(cx/fx + 0.3 tan), (W - cx)/fx + 0.3 tan])."""
+    vm, K = s["viewmat"].astype(np.float64), s["K"].astype(np.float64)
+    p = s["means"].astype(np.float64) @ vm[:3, :3].T + vm[:3, 3]
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    xr, yr = p[:, 0] / p[:, 2], p[:, 1] / p[:, 2]
+    out_x = (xr > (width - cx) / fx + 0.15 * width / fx) | (xr < -(cx / fx + 0.15 * width / fx))
+    out_y = (yr > (height - cy) / fy + 0.15 * height / fy) | (yr < -(cy / fy + 0.15 * height / fy))
+    vis = np.asarray(radii) > 0
+    return int((vis & out_x).sum()), int((vis & out_y).sum()), int(vis.sum()), int((~vis).sum())
+
+
 def rel_l2(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
