@@ -573,63 +573,116 @@ def _check_isects(n_isects, n_tiles=0):
                            f"view; the kernels index at most 2^28 = {MAX_ISECTS} less 16 per tile (INTEGRATION.md, memory model)")
 
 
-def _mfma_width(d):
-    """Feature widths served by the split matrix-core path (gags_mfma_width in csrc/common.h): every D >= 16 -- 16 is
-    what the reference rasterizes (train.py:68), 513 = 512 + 1 is BASELINE.json configs[4]."""
-    return d >= 16
+_FWD_VALU, _FWD_FUSED, _FWD_SPLIT, _FWD_LEAN16 = "valu", "fused", "split", "lean16"
+_BWD_NONE, _BWD_STAGED, _BWD_STAGED_GEOM, _BWD_VALU = "none", "staged", "staged+geom", "valu"
+
+
+class _Route(NamedTuple):
+    """Which kernels serve one rasterization() call and what the forward prepares for the backward: decided once by _route(),
+    read by projection, binning, trimming, the zero-fill, _Rasterize.forward and -- from ctx -- _Rasterize.backward.
+    (DESIGN.md section 1 has the table.)"""
+    fwd: str             # _FWD_VALU; _FWD_FUSED (single matrix-core kernel, no scratch); _FWD_SPLIT (weights pass + feature
+    #                      stream through a scratch of 1 KB per intersection); _FWD_LEAN16 (the weights pass with the 16-channel
+    #                      feature pass fused in: no scratch, nothing kept)
+    fwd_per_kernel: bool  # profiler on: the split forward's two kernels in two launches, one event pair each
+    records: bool        # projection / binning produce the per-Gaussian record table of the matrix-core kernels
+    half: bool           # the fp16 table is read as it is (widened in the feature pass); its gradient comes back in fp16
+    bwd: str             # _BWD_NONE (nothing requires grad); _BWD_STAGED (colours only, atomic-free); _BWD_STAGED_GEOM (geometry
+    #                      through gags_raster_bwd_geom, colours -- if wanted -- staged); _BWD_VALU (gags_raster_bwd: VALU / atomic)
+    geom: bool           # the backward produces v_means2d, v_conics, v_opacities
+    colors: bool         # ... and v_colors
+    early_rowmap: bool   # the forward enqueues the backward's row map behind its own kernels (RasterContext.early_rowmap)
+    trim: Any            # list trimming: False = never, None = automatic above TRIM_AUTO_BYTES, True = forced
+    zero_fill: bool      # the gradient's zero-fill starts on a second stream before the binning (RasterContext.overlap_zero_fill)
+    flags: int           # the caller's raster_flags, for the kernel-variant bits the translations below read (never the route);
+    #                      GAGS_FWD_F16MFMA only where it applies (an fp16 table read as it is, D >= 128)
+
+    @property
+    def keeps_scratch(self):
+        """The forward's scratch and slot counts are saved for the backward: exactly when a staged backward will read them."""
+        return self.bwd in (_BWD_STAGED, _BWD_STAGED_GEOM)
+
+    def without_isects(self):
+        """Late fact 1, known after the binning: no tile intersection.  The split forward runs as it is, in one launch (the lean
+        kernel wants a list to walk), and there is no row to number ahead of the backward."""
+        return self._replace(fwd=_FWD_SPLIT if self.fwd == _FWD_LEAN16 else self.fwd, fwd_per_kernel=False, early_rowmap=False)
+
+    def without_scratch(self):
+        """Late fact 2: the split forward's scratch could not be allocated.  The scratch-free kernels, which read an fp32 table:
+        single-kernel forward, gags_raster_bwd."""
+        return self._replace(fwd=_FWD_FUSED, fwd_per_kernel=False, half=False, early_rowmap=False,
+                             bwd=_BWD_NONE if self.bwd == _BWD_NONE else _BWD_VALU)
+
+
+def _route(n, d, f16, needs, raster_flags, profiling, capacity_mode=False, early_rowmap=True, overlap_zero_fill=False,
+           hooked=False, trim_lists=None):
+    """The _Route of a call, from plain values: n Gaussians, d = the FINAL channel count, f16 = the table is fp16, needs = which
+    of (means2d, conics, colors, opacities, backgrounds) require grad while a graph is recorded, the caller's raster_flags,
+    profiler.ENABLED, and the RasterContext settings that matter (hooked: grad_range_hook is set).
+    The widths: the matrix-core forward serves every D >= 16 (gags_mfma_width in csrc/common.h; 16 is what the reference
+    rasterizes, 513 = 512 + 1 is BASELINE.json configs[4]), the staged backward D <= 1024, gags_raster_bwd_geom D % 8 == 0
+    of those (below 16 the VALU kernel is faster)."""
+    wide = d >= 16
+    mfma = wide and n > 0 and not (raster_flags & (_lib.GAGS_FWD_NO_MFMA | _lib.GAGS_FWD_FUSED))
+    half = mfma and f16
+    geom = needs[0] or needs[1] or needs[3]
+    # a 16-channel fp32 render that nothing will be differentiated through (evaluation: render.py, the relevancy queries)
+    lean = (mfma and d == 16 and not half and not any(needs) and not (raster_flags & _lib.GAGS_FWD_EXACT) and not profiling)
+    fwd = (_FWD_LEAN16 if lean else _FWD_SPLIT if mfma
+           else _FWD_FUSED if (wide and not (raster_flags & _lib.GAGS_FWD_NO_MFMA)) else _FWD_VALU)
+    staged_ok = fwd == _FWD_SPLIT and d <= 1024 and not (raster_flags & _lib.GAGS_BWD_ATOMIC)
+    # (every gradient at a width gags_raster_bwd_geom does not serve: the VALU kernel, and nothing is kept for it)
+    bwd = (_BWD_NONE if not any(needs) else _BWD_STAGED_GEOM if (staged_ok and geom and d % 8 == 0)
+           else _BWD_STAGED if (staged_ok and needs[2] and not geom) else _BWD_VALU)
+    if not (half and d >= 128):
+        raster_flags &= ~_lib.GAGS_FWD_F16MFMA
+    return _Route(fwd=fwd, fwd_per_kernel=bool(profiling) and fwd == _FWD_SPLIT, records=wide, half=half, bwd=bwd,
+                  geom=bool(geom), colors=bool(needs[2]), flags=int(raster_flags),
+                  early_rowmap=bwd == _BWD_STAGED and bool(early_rowmap) and not capacity_mode,
+                  trim=trim_lists if fwd in (_FWD_SPLIT, _FWD_LEAN16) else False,
+                  zero_fill=bool(overlap_zero_fill) and not hooked and bwd == _BWD_STAGED and n * d >= ZERO_FILL_MIN_ELEMS)
 
 
 class _Rasterize(torch.autograd.Function):
-    """K9 forward / K10 backward over pre-binned intersections.
+    """K9 forward / K10 backward over pre-binned intersections, on the kernels the call's _Route names.
 
-    Matrix-core widths (D >= 16, D % 4 == 0) run the split forward: one weights pass (alpha, transmittance,
+    Matrix-core widths (D >= 16) run the split forward: one weights pass (alpha, transmittance,
     stop rule: once per view) that leaves weight tiles in a scratch buffer, then the feature stream.
     The same scratch feeds the staged, atomic-free colours-only backward."""
 
     @staticmethod
-    def forward(ctx, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, packed, width, height,
-                flags, prezero=None, rctx=None, n_isects=None, grad_on=True):
+    def forward(ctx, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, packed, width, height, route, rctx,
+                prezero=None):
         """offsets: the buffer of n_tiles + 1 int32 entries tile_binning returns as `offsets_full` (last entry = the
-        intersection count), or a gsplat-style [tile_h, tile_w] tensor together with `n_isects` (the count is then attached
-        here).  rctx: the RasterContext of the call."""
+        intersection count).  route: _route() of the call; rctx: its RasterContext."""
         lib = _lib.load()
-        # (ctx.needs_input_grad says what requires grad, not whether a graph is being recorded: under torch.no_grad() it is
-        # still True -- `grad_on` is torch.is_grad_enabled() at the call, taken by rasterization() outside this forward)
-        needs = tuple(bool(g) and bool(grad_on) for g in ctx.needs_input_grad)
+        n_isects = flatten_ids.shape[0]  # (capacity mode: the buffers' size; the kernels take the count from `offsets`)
+        if n_isects == 0:
+            route = route.without_isects()
         means2d, conics, opacities = _c(means2d), _c(conics), _c(opacities)
         # an fp16 feature table (BASELINE.json configs[4]) is read as it is by the matrix-core feature pass: widened
         # exactly, same fp32 arithmetic; every other kernel gets fp32
-        half = (colors.dtype == torch.float16 and packed is not None and colors.shape[0] > 0
-                and not (flags & (_lib.GAGS_FWD_NO_MFMA | _lib.GAGS_FWD_FUSED)))
-        colors = (colors if colors.is_contiguous() else colors.contiguous()) if half else _c(colors)
+        colors = (colors if colors.is_contiguous() else colors.contiguous()) if route.half else _c(colors)
         backgrounds = None if backgrounds is None else _c(backgrounds)
         n, d = colors.shape
         dev = colors.device
         n_tiles = _tiles(width, height)[2]
-        offsets = _offsets_with_count(offsets, n_tiles, flatten_ids.shape[0] if n_isects is None else n_isects)
-        n_isects = flatten_ids.shape[0]  # (capacity mode: the buffers' size; the kernels take the count from `offsets`)
+        if offsets.shape != (n_tiles + 1,) or offsets.dtype != torch.int32 or not offsets.is_contiguous():
+            raise ValueError(f"isect_offsets must be tile_binning's offsets_full: {n_tiles + 1} int32 entries, the last one the count")
         out = torch.empty(height, width, d, device=dev)
         alphas = torch.empty(height, width, device=dev)
         last_ids = torch.empty(height, width, dtype=torch.int32, device=dev)
-        split = n > 0 and packed is not None and not (flags & (_lib.GAGS_FWD_NO_MFMA | _lib.GAGS_FWD_FUSED))
-        scratch = blk_rows = None
-        nbytes = 0
-        # a 16-channel fp32 render that nothing will be differentiated through (evaluation: render.py, the relevancy queries):
-        # the fused weights + feature pass alone (csrc/raster_weights.hip) -- no weight tiles, no 1 KB per intersection of scratch
-        lean16 = (split and d == 16 and not half and n_isects > 0 and not any(needs)
-                  and not (flags & _lib.GAGS_FWD_EXACT) and not profiler.ENABLED)
-        if split and not lean16:
+        scratch, blk_rows, nbytes = None, None, 0
+        if route.fwd == _FWD_SPLIT:
             nbytes = lib.gags_raster_fwd_scratch_bytes(n_isects, width, height)
-            try:
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            except torch.OutOfMemoryError:
-                # the kept gradient buffers (_KeptGrad: up to KEEP_GRAD_SHAPES x [N, D]) are the memory this context can give
-                # back: released, then one more attempt
-                (rctx if rctx is not None else default_context()).forget_all_kept()
+            for _attempt in range(2):
                 try:
                     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                    break
                 except torch.OutOfMemoryError:
-                    scratch = None
+                    # the kept gradient buffers (_KeptGrad: up to KEEP_GRAD_SHAPES x [N, D]) are the memory this context can
+                    # give back: released, then one more attempt
+                    rctx.forget_all_kept()
             if scratch is None:
                 # slot space (1 KB per intersection) does not fit even after the caching allocator gave its blocks
                 # back: scratch-free kernels, which read an fp32 table only.  Said out loud: they are several times slower
@@ -638,15 +691,10 @@ class _Rasterize(torch.autograd.Function):
                 warnings.warn(f"gags_amd.rasterization: {nbytes / 2 ** 30:.1f} GiB of forward scratch for {n_isects} tile "
                               "intersections could not be allocated; this view runs on the scratch-free kernels "
                               "(INTEGRATION.md, memory model)", RuntimeWarning, stacklevel=3)
-                split, nbytes, scratch = False, 0, None
-                if half:
-                    half, colors = False, colors.float()
-        if lean16:
-            split = False
-        if split:
+                route, nbytes, colors = route.without_scratch(), 0, _c(colors)
+        if route.fwd == _FWD_SPLIT:
             blk_rows = torch.empty(n_tiles * 4, dtype=torch.int32, device=dev)  # per 8x8 pixel block
-        cflags = ((flags & 3) | (flags & _lib.GAGS_FWD_EXACT) | _lib.GAGS_RECS_BY_GAUSSIAN | (_lib.GAGS_FEAT_F16 if half else 0)
-                  | (64 if (half and d >= 128 and (flags & _lib.GAGS_FWD_F16MFMA)) else 0))
+        cflags = _fwd_flags(route)
 
         def launch(extra=0):
             check(lib.gags_raster_fwd(d, n, width, height, ptr(means2d), ptr(conics), ptr(opacities), ptr(colors),
@@ -655,121 +703,100 @@ class _Rasterize(torch.autograd.Function):
                                       cflags | extra, _stream()), "gags_raster_fwd")
 
         with profiler.stage("raster_fwd"):
-            if profiler.ENABLED and split and n_isects > 0:  # one event pair per kernel, for bench.py's roofline line
+            if route.fwd_per_kernel:  # one event pair per kernel, for bench.py's roofline line
                 with profiler.stage("raster_weights"):
                     launch(_lib.GAGS_FWD_ONLY_WEIGHTS)
                 with profiler.stage("raster_fwd_feat"):
                     launch(_lib.GAGS_FWD_ONLY_FEATURES)
             else:
                 launch()
-        if split:
+        if route.fwd == _FWD_SPLIT:
             profiler.note("fwd_blk_rows", blk_rows)
-        need_geom = needs[0] or needs[1] or needs[3]
-        rctx_ = rctx if rctx is not None else default_context()
         early = None
-        if (split and n_isects > 0 and rctx_.early_rowmap and needs[2] and not need_geom and _mfma_width(d)
-                and d <= 1024 and not (flags & _lib.GAGS_BWD_ATOMIC) and not rctx_.capacity_mode):
+        if route.early_rowmap:
             with profiler.stage("bwd_rowcount"):
-                early = _early_rowmap(lib, rctx_, _FwdState(offsets, n_isects, blk_rows, scratch, flatten_ids, n, d, width, height))
-        # wide-D geometry gradients on the matrix cores (gags_raster_bwd_geom) also consume the forward's scratch
-        geom_mfma = split and need_geom and _geom_mfma_width(d) and not (flags & _lib.GAGS_BWD_ATOMIC)
-        staged = (split and _mfma_width(d) and d <= 1024 and (needs[2] or geom_mfma)
-                  and not (flags & _lib.GAGS_BWD_ATOMIC))
-        ctx.geom_mfma = bool(geom_mfma and staged)
+                early = _early_rowmap(lib, rctx, _FwdState(offsets, n_isects, blk_rows, scratch, flatten_ids, n, d, width, height))
+        keep = route.keeps_scratch  # (wide-D geometry gradients on the matrix cores also consume the forward's scratch)
         ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, packed, alphas,
-                              last_ids, scratch if staged else None, blk_rows if staged else None)
-        ctx.cfg = (width, height, flags)
-        ctx.half = half
-        ctx.rctx = rctx if rctx is not None else default_context()
-        ctx.prezero = prezero if staged else None
-        ctx.early = early if staged else None
+                              last_ids, scratch if keep else None, blk_rows if keep else None)
+        ctx.route = route
+        ctx.cfg = (width, height, rctx, prezero if route.bwd == _BWD_STAGED else None, early)
         ctx.mark_non_differentiable(last_ids)
         return out, alphas, last_ids
 
     @staticmethod
     def backward(ctx, v_out, v_alphas, _v_last):
         lib = _lib.load()
+        route = ctx.route
         (means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, packed, alphas,
          last_ids, fwd_scratch, blk_rows) = ctx.saved_tensors
-        width, height, flags = ctx.cfg
+        width, height, rctx, prezero, early = ctx.cfg
         n, d = colors.shape
-        dev = colors.device
-        n_isects = flatten_ids.shape[0]
-        fwd = _FwdState(offsets, n_isects, blk_rows, fwd_scratch, flatten_ids, n, d, width, height)
-        need_geom = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[3]
-        v_out = torch.zeros(height, width, d, device=dev) if v_out is None else _c(v_out)
+        fwd = _FwdState(offsets, flatten_ids.shape[0], blk_rows, fwd_scratch, flatten_ids, n, d, width, height)
+        v_out = torch.zeros(height, width, d, device=colors.device) if v_out is None else _c(v_out)
         v_alphas = None if v_alphas is None else _c(v_alphas)
         v_bg = None
         if backgrounds is not None and ctx.needs_input_grad[4]:
             v_bg = ((1.0 - alphas)[..., None] * v_out).sum(dim=(0, 1))
-        if not need_geom and blk_rows is not None:
+        if route.bwd == _BWD_STAGED:
             # an fp16 table gets its gradient in fp16 straight from the reduce kernel (fp32 sums, rounded once): no fp32
             # tensor + cast pass (autograd wants the table's dtype; an fp32 master sits behind a .half() cast)
-            v_colors = _backward_staged(lib, ctx.rctx, fwd, v_out, _stage_bits(flags, ctx.half), ctx.prezero, early=ctx.early)
-            return None, None, v_colors, None, v_bg, None, None, None, None, None, None, None, None, None, None
-        if need_geom and blk_rows is not None and ctx.geom_mfma:
-            # wide D: colours through the staged backward, geometry through the matrix-core dot pass + scalar pass
-            v_colors = None
-            if ctx.needs_input_grad[2]:
-                v_colors = _backward_staged(lib, ctx.rctx, fwd, v_out, _stage_bits(flags, ctx.half))
-            if ctx.half:  # the geometry kernels read an fp32 table: widen the halves (exact) for this backward
-                colors = colors.float()
-            # compact numbering of the per-slot rows: one small prefix sum and a 4-byte readback instead of sorting the
-            # whole sparse slot space (6x the keys)
-            if GEOM_COMPACT_ROWS:
-                incl = torch.cumsum(blk_rows, 0, dtype=torch.int32)
-                row_base = (incl - blk_rows).contiguous()
-                n_rows = int(incl[-1].item()) if incl.numel() else 0
-            else:  # the C ABI's other numbering: rows (and the dot products) in the sparse slot space, no count needed
-                row_base, n_rows = None, -1
-            nb = lib.gags_raster_bwd_geom_scratch_bytes(n_isects, width, height, n, d, n_rows)
-            gscratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-            v_geo = torch.empty(n, 8, device=dev)
-            with profiler.stage("raster_bwd_geom"):
-                check(lib.gags_raster_bwd_geom(d, n, width, height, ptr(colors), ptr(backgrounds), ptr(offsets), n_isects,
-                                               ptr(packed), ptr(v_out), ptr(v_alphas), ptr(blk_rows), ptr(fwd_scratch),
-                                               fwd_scratch.numel(), ptr(gscratch), nb, ptr(v_geo), ptr(flatten_ids),
-                                               ptr(row_base), n_rows,
-                                               _lib.GAGS_RECS_BY_GAUSSIAN
-                                               | (_lib.GAGS_GEOM_F32MFMA if (flags & _lib.GAGS_BWD_F32MFMA) else 0),
-                                               _stream()),
-                      "gags_raster_bwd_geom")
-            v_con, v_m2d, v_opac = v_geo[:, 0:3].contiguous(), v_geo[:, 3:5].contiguous(), v_geo[:, 5].contiguous()
-            return v_m2d, v_con, v_colors, v_opac, v_bg, None, None, None, None, None, None, None, None, None, None
-        if ctx.half:  # VALU / atomic kernels read an fp32 table: widen the halves (exact); gradient returned in the table's dtype
-            colors = colors.float()
-        v_colors = torch.zeros(n, d, device=dev)
-        if need_geom:
-            v_opac = torch.zeros(n, device=dev)
-            v_m2d = torch.zeros(n, 2, device=dev)
-            v_con = torch.zeros(n, 3, device=dev)
-            bflags = (flags & 3) | _lib.GAGS_RECS_BY_GAUSSIAN
+            grads = (None, None, _backward_staged(lib, rctx, fwd, v_out, _stage_bits(route.flags, route.half), prezero, early=early),
+                     None)
+        elif route.bwd == _BWD_STAGED_GEOM:
+            grads = _backward_geom_mfma(lib, rctx, route, fwd, colors, backgrounds, packed, v_out, v_alphas)
         else:
-            v_opac = v_m2d = v_con = None
-            bflags = (flags & 3) | _lib.GAGS_BWD_COLORS_ONLY | _lib.GAGS_RECS_BY_GAUSSIAN
-        with profiler.stage("raster_bwd"):
-            check(lib.gags_raster_bwd(d, width, height, ptr(means2d), ptr(conics), ptr(opacities), ptr(colors),
-                                      ptr(backgrounds), ptr(offsets), ptr(flatten_ids), n_isects, ptr(packed),
-                                      ptr(alphas), ptr(last_ids), ptr(v_out), ptr(v_alphas), ptr(v_colors),
-                                      ptr(v_opac), ptr(v_m2d), ptr(v_con), bflags, _stream()), "gags_raster_bwd")
-        if ctx.half:
-            v_colors = v_colors.half()
-        return v_m2d, v_con, v_colors, v_opac, v_bg, None, None, None, None, None, None, None, None, None, None
+            grads = _backward_valu(lib, route, fwd, means2d, conics, opacities, colors, backgrounds, packed, alphas, last_ids,
+                                   v_out, v_alphas)
+        return _raster_grads(*grads, v_bg)
 
 
-def _offsets_with_count(offsets, n_tiles, n_isects):
-    """ABI v2: every raster kernel reads `isect_offsets[tile + 1]` as a tile's end, so the buffer must hold n_tiles + 1
-    entries, the last one = the intersection count (include/gags_raster.h).  tile_binning's `offsets_full` is such a buffer
-    and passes through; a gsplat-style [tile_h, tile_w] tensor (no entry behind its last tile) is copied into one with the
-    TRUE count `n_isects` the caller states -- never a buffer size."""
-    if offsets.dim() == 1 and offsets.numel() == n_tiles + 1 and offsets.is_contiguous() and offsets.dtype == torch.int32:
-        return offsets
-    if offsets.numel() != n_tiles:
-        raise ValueError(f"isect_offsets must have {n_tiles} (= tile_h * tile_w) entries, or {n_tiles + 1} with the count")
-    full = torch.empty(n_tiles + 1, dtype=torch.int32, device=offsets.device)
-    full[:n_tiles] = offsets.reshape(-1)
-    full[n_tiles] = int(n_isects)
-    return full
+def _raster_grads(v_m2d, v_con, v_colors, v_opac, v_bg):
+    """_Rasterize.backward's return: the five gradients in the slots of forward's tensor arguments, None for the rest."""
+    return (v_m2d, v_con, v_colors, v_opac, v_bg) + (None,) * 8
+
+
+def _backward_geom_mfma(lib, rctx, route, fwd, colors, backgrounds, packed, v_out, v_alphas):
+    """Wide D, geometry wanted: colours (if wanted) through the staged backward, geometry through the matrix-core dot pass +
+    scalar pass of gags_raster_bwd_geom, both on the forward's scratch.  Returns (v_means2d, v_conics, v_colors, v_opacities)."""
+    dev = colors.device
+    v_colors = _backward_staged(lib, rctx, fwd, v_out, _stage_bits(route.flags, route.half)) if route.colors else None
+    if route.half:  # the geometry kernels read an fp32 table: widen the halves (exact) for this backward
+        colors = colors.float()
+    # compact numbering of the per-slot rows: one small prefix sum and a 4-byte readback instead of sorting the
+    # whole sparse slot space (6x the keys)
+    if GEOM_COMPACT_ROWS:
+        incl = torch.cumsum(fwd.blk_rows, 0, dtype=torch.int32)
+        row_base = (incl - fwd.blk_rows).contiguous()
+        n_rows = int(incl[-1].item()) if incl.numel() else 0
+    else:  # the C ABI's other numbering: rows (and the dot products) in the sparse slot space, no count needed
+        row_base, n_rows = None, -1
+    nb = lib.gags_raster_bwd_geom_scratch_bytes(fwd.n_isects, fwd.width, fwd.height, fwd.n, fwd.d, n_rows)
+    gscratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    v_geo = torch.empty(fwd.n, 8, device=dev)
+    with profiler.stage("raster_bwd_geom"):
+        check(lib.gags_raster_bwd_geom(fwd.d, fwd.n, fwd.width, fwd.height, ptr(colors), ptr(backgrounds), ptr(fwd.offsets),
+                                       fwd.n_isects, ptr(packed), ptr(v_out), ptr(v_alphas), ptr(fwd.blk_rows),
+                                       ptr(fwd.fwd_scratch), fwd.fwd_scratch.numel(), ptr(gscratch), nb, ptr(v_geo),
+                                       ptr(fwd.flatten_ids), ptr(row_base), n_rows, _geom_flags(route), _stream()),
+              "gags_raster_bwd_geom")
+    return v_geo[:, 3:5].contiguous(), v_geo[:, 0:3].contiguous(), v_colors, v_geo[:, 5].contiguous()
+
+
+def _backward_valu(lib, route, fwd, means2d, conics, opacities, colors, backgrounds, packed, alphas, last_ids, v_out, v_alphas):
+    """gags_raster_bwd, the VALU / atomic kernels: colours, and -- route.geom -- geometry.  They read an fp32 table: the halves
+    are widened (exact) and the gradient goes back in the table's dtype.  Returns (v_means2d, v_conics, v_colors, v_opacities)."""
+    dev = colors.device
+    if route.half:
+        colors = colors.float()
+    v_colors = torch.zeros(fwd.n, fwd.d, device=dev)
+    v_opac, v_m2d, v_con = ([torch.zeros(fwd.n, *k, device=dev) for k in ((), (2,), (3,))] if route.geom else (None, None, None))
+    with profiler.stage("raster_bwd"):
+        check(lib.gags_raster_bwd(fwd.d, fwd.width, fwd.height, ptr(means2d), ptr(conics), ptr(opacities), ptr(colors),
+                                  ptr(backgrounds), ptr(fwd.offsets), ptr(fwd.flatten_ids), fwd.n_isects, ptr(packed),
+                                  ptr(alphas), ptr(last_ids), ptr(v_out), ptr(v_alphas), ptr(v_colors),
+                                  ptr(v_opac), ptr(v_m2d), ptr(v_con), _bwd_flags(route), _stream()), "gags_raster_bwd")
+    return v_m2d, v_con, v_colors.half() if route.half else v_colors, v_opac
 
 
 def _channel_ranges(d, spec):
@@ -789,11 +816,6 @@ def _channel_ranges(d, spec):
         out.append((c, c + w))
         c, i = c + w, i + 1
     return out
-
-
-def _geom_mfma_width(d):
-    """Widths whose geometry gradients run through gags_raster_bwd_geom (below that the VALU kernel is faster)."""
-    return d >= 16 and d % 8 == 0 and d <= 1024
 
 
 class _EarlyRowmap:
@@ -848,6 +870,28 @@ def _stage_bits(raster_flags, half):
             | (_lib.GAGS_STAGED_OUT_F16 if half else 0)
             | (_lib.GAGS_STAGED_BLOCKWAVES if (raster_flags & _lib.GAGS_BWD_BLOCKWAVES) else 0)
             | (_lib.GAGS_STAGED_EXACT_WEIGHTS if (raster_flags & _lib.GAGS_BWD_EXACT_WEIGHTS) else 0))
+
+
+# the two raster_flags whose public value IS the header's: they travel to gags_raster_fwd / gags_raster_bwd as they are (the
+# forward reads only the second)
+_C_SHARED = _lib.GAGS_BWD_COLORS_ONLY | _lib.GAGS_FWD_NO_MFMA
+
+
+def _fwd_flags(route):
+    """`flags` of gags_raster_fwd (the profiler's per-kernel launches add GAGS_FWD_ONLY_*)."""
+    return ((route.flags & (_C_SHARED | _lib.GAGS_FWD_EXACT)) | _lib.GAGS_RECS_BY_GAUSSIAN
+            | (_lib.GAGS_FEAT_F16 if route.half else 0)
+            | (_lib.GAGS_FWD_F16MFMA_C if (route.half and route.flags & _lib.GAGS_FWD_F16MFMA) else 0))
+
+
+def _bwd_flags(route):
+    """`flags` of gags_raster_bwd."""
+    return (route.flags & _C_SHARED) | _lib.GAGS_RECS_BY_GAUSSIAN | (0 if route.geom else _lib.GAGS_BWD_COLORS_ONLY)
+
+
+def _geom_flags(route):
+    """`flags` of gags_raster_bwd_geom."""
+    return _lib.GAGS_RECS_BY_GAUSSIAN | (_lib.GAGS_GEOM_F32MFMA if (route.flags & _lib.GAGS_BWD_F32MFMA) else 0)
 
 
 def _rowmap(lib, fwd):
@@ -1035,6 +1079,24 @@ def _backward_staged(lib, rctx, fwd, v_out, stage_bits=0, prezero=None, exact_ro
     return v_colors
 
 
+def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh, render_mode, raw_params):
+    """What _Rasterize will be handed, known before anything runs: (d, f16, needs) = the final channel count (after SH
+    evaluation and the depth channel of RGB+D / RGB+ED), whether the final table is fp16 (only a table passed through as it
+    is), and which of (means2d, conics, colors, opacities, backgrounds) will require grad -- autograd's own rule: an output
+    requires grad when a graph is recorded and any tensor it was computed from does.  rasterization() checks all three
+    against the tensors themselves before it rasterizes."""
+    def rg(*ts):
+        return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+    proj = rg(means, quats, scales, viewmats, Ks) or (raw_params and rg(opacities))  # (means2d, conics, depths)
+    if render_mode in ("D", "ED"):
+        return 1, False, (proj, proj, proj, proj if raw_params else rg(opacities), False)
+    depth = render_mode != "RGB"
+    d = (3 if sh else colors.shape[-1]) + (1 if depth else 0)
+    v_cols = rg(colors) or (sh and rg(means, viewmats)) or (depth and proj)
+    return (d, colors.dtype == torch.float16 and not sh and not depth,
+            (proj, proj, v_cols, proj if raw_params else rg(opacities), rg(backgrounds)))
+
+
 def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height,
                   near_plane=0.01, far_plane=1e10, radius_clip=0.0, eps2d=0.3, sh_degree=None, packed=False,
                   tile_size=16, backgrounds=None, render_mode="RGB", sparse_grad=False, absgrad=False,
@@ -1068,15 +1130,17 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     width, height = int(width), int(height)
     viewmat, K = viewmats[0], Ks[0]
 
+    # the final channel count -- after SH evaluation and the depth channel of RGB+D / RGB+ED -- and with it the route, once
+    d, f16, needs = _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh_degree is not None,
+                                 render_mode, raw_params)
+    route = _route(n, d, f16, needs, int(raster_flags), profiler.ENABLED, rctx.capacity_mode, rctx.early_rowmap,
+                   rctx.overlap_zero_fill, rctx.grad_range_hook is not None, rctx.trim_lists)
+
     records = None
     if raw_params:
-        # (the record table is only read by the matrix-core path: D >= 16 after the depth channel of RGB+D / RGB+ED is appended)
-        dfinal = (3 if sh_degree is not None else colors.shape[-1]) + (1 if render_mode in ("RGB+D", "RGB+ED") else 0)
-        if render_mode in ("D", "ED"):
-            dfinal = 1
         radii, means2d, depths, conics, tiles, opacities, records = _ProjectRaw.apply(
             means, quats, scales, opacities, viewmat, K, width, height, float(eps2d), float(near_plane), float(far_plane),
-            float(radius_clip), float(scaling_modifier), bool(_mfma_width(dfinal) and n > 0))
+            float(radius_clip), float(scaling_modifier), route.records and n > 0)
         if records.numel() == 0:
             records = None
     else:
@@ -1105,15 +1169,15 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         cols = depths[:, None]
         bg = None if bg is None else torch.zeros(1, device=bg.device)
 
+    if (d, f16, needs) != (cols.shape[-1], cols.dtype == torch.float16, tuple(
+            torch.is_grad_enabled() and t is not None and t.requires_grad for t in (means2d, conics, cols, opacities, bg))):
+        raise RuntimeError("gags_amd.rasterization: the colour table is not what the route was built for (_table_ahead)")
+
     prezero = None
-    dz = cols.shape[-1]
-    if (rctx.overlap_zero_fill and rctx.grad_range_hook is None and torch.is_grad_enabled() and cols.requires_grad and _mfma_width(dz)
-            and dz <= 1024 and n * dz >= ZERO_FILL_MIN_ELEMS and not (raster_flags & (_lib.GAGS_BWD_ATOMIC | _lib.GAGS_FWD_NO_MFMA
-                                                                                      | _lib.GAGS_FWD_FUSED))
-            and not (means.requires_grad or quats.requires_grad or scales.requires_grad or opacities.requires_grad)):
+    if route.zero_fill:
         # colours-only (GAD) backward ahead: its gradient tensor is mostly rows of zeros.  Fill it now, on a second stream,
         # under the binning kernels; the backward's reduce stage then writes only the rows that exist (_backward_staged)
-        vbuf = torch.empty(n, dz, device=cols.device, dtype=torch.float16 if cols.dtype == torch.float16 else torch.float32)
+        vbuf = torch.empty(n, d, device=cols.device, dtype=torch.float16 if f16 else torch.float32)
         side = rctx.side_stream(cols.device)
         ev0, ev1 = torch.cuda.Event(), torch.cuda.Event()
         ev0.record()
@@ -1124,30 +1188,26 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         vbuf.record_stream(side)
         prezero = (vbuf, ev1)
 
-    dcols = cols.shape[-1]
-    wide = _mfma_width(dcols)  # the matrix-core path wants packed records
     cap_key = (n, width, height, means.device.index)
 
     def run(cap):
         with torch.no_grad(), profiler.stage("binning"):
-            b = tile_binning(means2d, radii, depths, tiles, width, height, conics if wide else None,
-                             _c(opacities) if wide else None, cap, records=records if wide else None, context=rctx)
+            b = tile_binning(means2d, radii, depths, tiles, width, height, conics if route.records else None,
+                             _c(opacities) if route.records else None, cap, records=records, context=rctx)
         offs, flat = b.offsets_full, b.flatten_ids
         # heavy views: the lists cut to what their tiles read (_trim_lists) -- the raster passes, their scratch and the backward
         # work on the cut lists; callers still get the full ones in `info`
         trimmed = None
         n_full = flat.shape[0]
-        if (cap is None and wide and b.packed is not None and n_full > 0 and rctx.trim_lists is not False
-                and not (raster_flags & (_lib.GAGS_FWD_NO_MFMA | _lib.GAGS_FWD_FUSED))):
+        if cap is None and n_full > 0 and route.trim is not False:
             lib_ = _lib.load()
-            if rctx.trim_lists or lib_.gags_raster_fwd_scratch_bytes(n_full, width, height) > TRIM_AUTO_BYTES:
+            if route.trim or lib_.gags_raster_fwd_scratch_bytes(n_full, width, height) > TRIM_AUTO_BYTES:
                 with torch.no_grad():
                     trimmed = _trim_lists(lib_, n, width, height, offs, flat, n_full, b.packed)
                 offs, flat = trimmed[0], trimmed[1]
         # any width in ONE rasterization: 513 = 512 CLIP channels + 1 (BASELINE.json configs[4] "512-d feat + granularity")
         # is four 128-channel slices and one lane of a narrow slice on the same matrix-core kernels, into one output tensor
-        r = _Rasterize.apply(means2d, conics, cols, opacities, bg, offs, flat, b.packed, width, height, int(raster_flags), prezero,
-                             rctx, None, torch.is_grad_enabled())
+        r = _Rasterize.apply(means2d, conics, cols, opacities, bg, offs, flat, b.packed, width, height, route, rctx, prezero)
         if trimmed is not None:
             # last_ids are sorted indices: a COPY goes back to the full lists' numbering for the caller (the autograd node keeps
             # its own, which matches the lists it saved)

@@ -287,6 +287,27 @@ def test_stage_bits_of_the_staged_backward_agree_with_the_header():
     assert defs["GAGS_GEOM_F32MFMA"] & (defs["GAGS_GEOM_F32MFMA"] - 1) == 0 and defs["GAGS_GEOM_F32MFMA"] != _lib.GAGS_RECS_BY_GAUSSIAN
 
 
+def test_forward_and_backward_flags_agree_with_the_header():
+    """Every forward / backward flag #define of the header against its mirror in gags_amd/_lib.py.  One mirror has a name of its
+    own: the header's GAGS_FWD_F16MFMA (64) is _lib.GAGS_FWD_F16MFMA_C, because _lib.GAGS_FWD_F16MFMA is the PUBLIC request bit
+    (128; 64 was taken by the python-side GAGS_BWD_F32MFMA) that rasterization._fwd_flags translates."""
+    from gags_amd import _lib
+    src = open(os.path.join(ROOT, "include", "gags_raster.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"^#define\s+(GAGS_(?:BWD|FWD|FEAT|RECS)_\w+)\s+(\d+)\b", src, flags=re.M)}
+    assert sorted(defs) == sorted(["GAGS_BWD_COLORS_ONLY", "GAGS_FWD_NO_MFMA", "GAGS_FEAT_F16", "GAGS_FWD_F16MFMA", "GAGS_FWD_EXACT",
+                                   "GAGS_FWD_ONLY_WEIGHTS", "GAGS_FWD_ONLY_FEATURES", "GAGS_RECS_BY_GAUSSIAN"]), sorted(defs)
+    for name, value in defs.items():
+        assert getattr(_lib, "GAGS_FWD_F16MFMA_C" if name == "GAGS_FWD_F16MFMA" else name) == value, name
+    assert [defs[k] for k in ("GAGS_BWD_COLORS_ONLY", "GAGS_FWD_NO_MFMA", "GAGS_FEAT_F16", "GAGS_FWD_F16MFMA", "GAGS_RECS_BY_GAUSSIAN",
+                              "GAGS_FWD_ONLY_WEIGHTS", "GAGS_FWD_ONLY_FEATURES", "GAGS_FWD_EXACT")] == [1, 2, 32, 64, 256, 512, 1024,
+                                                                                                     2048]  # (the ABI)
+    vals = list(defs.values())
+    assert all(v & (v - 1) == 0 for v in vals) and len(set(vals)) == len(vals)
+    # the two constants of one name: the request bit is NOT the C value, and the C value collides with another request bit --
+    # which is why no raster_flags word may reach gags_raster_fwd untranslated
+    assert _lib.GAGS_FWD_F16MFMA == 128 != _lib.GAGS_FWD_F16MFMA_C == _lib.GAGS_BWD_F32MFMA
+
+
 def test_python_side_raster_flags_are_distinct_bits():
     """render(..., raster_flags=) takes an OR of these: each selectable behaviour needs a bit of its own (two of them sharing one
     would silently select both kernels' worth of behaviour), and the retired GAGS_BWD_F16SPLIT stays 0."""
