@@ -139,6 +139,12 @@ SIGNATURES = {
     "gags_depthsample_scratch_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "gags_depthsample_map": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_depthsample_scatter": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # N7: the photometric loss of the RGB stage
+    "gags_photometric_partials": (_i64, [_i32, _i32, _i32]),
+    "gags_photometric_fwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _f64, _f64, _f64,
+                                    _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_photometric_bwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                    _i64, _i64, _i64, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

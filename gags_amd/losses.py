@@ -7,6 +7,10 @@ names, arguments and results as the reference's, on HIP kernels (include/gags_ne
     utils/loss_utils.py:103-136   scale_region_regulation_loss(scale_map, seg_map, mix_seg=True)
     utils/loss_utils.py:138-154   get_trained_seg(seg_map, scale_map)
     scene/dataset_readers.py:54-121  read_sam_clip_feature(img_embed, seg_map, scale_map)   (default mode)
+    utils/loss_utils.py:168-198   ssim(img1, img2, window_size=11, size_average=True)                      (row N7)
+    utils/image_utils.py:17-19    psnr(img1, img2)                                                         (row N7)
+plus photometric_loss(image, gt, lambda_dssim) = (1 - lambda) l1_loss + lambda (1 - ssim), the loss of an RGB step, as one
+forward and one backward kernel (csrc/photometric.hip),
 and the fusion the reference's train.py:165-166 spells as three full-size elementwise passes plus a [512,H,W]
 ground-truth tensor:
     distill_l1_map(pred, img_embed, seg_map, scale_map) == l1_loss_map(pred * mask, gt * mask), mask
@@ -337,3 +341,118 @@ def distill_l1_map(pred, img_embed, seg_map, scale_map):
     gt, mask = read_sam_clip_feature(img_embed, seg_map, scale_map); gradients reach `pred` and `scale_map`."""
     l1, mask = _DistillL1.apply(pred, img_embed, seg_map, scale_map)
     return l1, (mask != 0)[None]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# N7: the photometric loss of the RGB stage (include/gags_next.h, csrc/photometric.hip)
+
+# utils/loss_utils.py:158-160 gaussian(11, 1.5): exp(-(x - 5)**2 / 4.5) in Python doubles, rounded into a float32 tensor,
+# divided by its float32 sum -- the eleven float32 values, spelled out (they sum to 1 - 3.1e-8, and nothing renormalises
+# them).  This tuple is what the kernels are launched with; tests/test_photometric_cpu.py compares it with the reference's.
+SSIM_WINDOW = (0.001028380123898387, 0.0075987582094967365, 0.036000773310661316, 0.10936068743467331, 0.21300552785396576,
+               0.26601171493530273, 0.21300552785396576, 0.10936068743467331, 0.036000773310661316, 0.0075987582094967365,
+               0.001028380123898387)
+_WINDOW_C = (ctypes.c_float * 11)(*SSIM_WINDOW)
+
+
+def _photo_view(t):
+    """(tensor, planes, images, h, w, element strides of plane / row / column) of a [C,H,W] or [B,C,H,W] float32 GPU tensor
+    read where it lies: the planes must be equally spaced (a contiguous tensor, or the [C,H,W] view of the rasterizer's
+    [H,W,C] memory); anything else is copied once."""
+    if not t.is_cuda:
+        raise RuntimeError("gags_amd.losses: tensors must live on the GPU (there is no CPU path)")
+    if t.dim() not in (3, 4):
+        raise ValueError(f"expected [C,H,W] or [B,C,H,W], got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        t = t.float()
+    if any(st == 0 and sz > 1 for st, sz in zip(t.stride(), t.shape)):  # (an expanded tensor: its gradient needs elements of its own)
+        t = t.contiguous()
+    if t.dim() == 4:
+        b, c = t.shape[:2]
+        if not (b == 1 or c == 1 or t.stride(0) == c * t.stride(1)):
+            t = t.contiguous()
+        sp = t.stride(1) if c > 1 else t.stride(0)
+    else:
+        b, c = 1, t.shape[0]
+        sp = t.stride(0)
+    h, w = t.shape[-2:]
+    if b * c * h * w == 0:
+        raise ValueError(f"empty image {tuple(t.shape)}")
+    return t, b * c, t.shape[0], h, w, (sp, t.stride(-2), t.stride(-1))
+
+
+def _photo_forward(x, y, bias, wa, wb, reduce_all, need_grad):
+    """One gags_photometric_fwd: (out [1] or [images] float, sums [images, 3] double, k [2] float, dm or None, views)."""
+    x, planes, images, h, w, xs = _photo_view(x)
+    y, planes_y, _, hy, wy, ys = _photo_view(y)
+    if (planes_y, hy, wy) != (planes, h, w) or x.dim() != y.dim():
+        raise ValueError(f"image {tuple(x.shape)} vs ground truth {tuple(y.shape)}")
+    lib = _lib.load()
+    dev = x.device
+    partials = torch.empty(lib.gags_photometric_partials(planes, h, w), 3, dtype=torch.float64, device=dev)
+    sums = torch.empty(images, 3, dtype=torch.float64, device=dev)
+    out = torch.empty(1 if reduce_all else images, device=dev)
+    k = torch.empty(2, device=dev)
+    dm = torch.empty(3, planes, h, w, device=dev) if need_grad else None
+    check(lib.gags_photometric_fwd(planes, images, h, w, ptr(x), *xs, ptr(y), *ys, _WINDOW_C, bias, wa, wb, 1 if reduce_all else 0,
+                                   ptr(dm), None, ptr(partials), ptr(sums), ptr(out), ptr(k), _st()), "gags_photometric_fwd")
+    return out, sums, k, dm, (x, xs, y, ys, planes, images, h, w)
+
+
+class _Photometric(torch.autograd.Function):
+    """out = bias + wa mean|x - y| + wb mean(ssim map), over everything ([] result) or per image ([images])."""
+
+    @staticmethod
+    def forward(ctx, image, gt, bias, wa, wb, reduce_all):
+        if gt.requires_grad:
+            raise RuntimeError("gags_amd.losses: the ground truth of ssim / photometric_loss is not differentiated")
+        need = ctx.needs_input_grad[0]
+        out, _, k, dm, (x, xs, y, ys, planes, images, h, w) = _photo_forward(image, gt, bias, wa, wb, reduce_all, need)
+        if need:
+            ctx.save_for_backward(x, y, dm, k)
+            ctx.geom = (xs, ys, planes, 1 if reduce_all else images, h, w)
+        return out[0] if reduce_all else out
+
+    @staticmethod
+    def backward(ctx, v):
+        x, y, dm, k = ctx.saved_tensors
+        xs, ys, planes, groups, h, w = ctx.geom
+        # (a, b) per image = the cotangent times (wa / n, wb / n), formed on the device: no readback inside the backward pass
+        coef = (v.detach().reshape(-1, 1).float() * k).contiguous()
+        vx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)  # written in x's own layout
+        check(_lib.load().gags_photometric_bwd(planes, groups, h, w, ptr(x), *xs, ptr(y), *ys, _WINDOW_C, ptr(dm), ptr(coef),
+                                               ptr(vx), *xs, _st()), "gags_photometric_bwd")
+        return vx, None, None, None, None, None
+
+
+def _check_window(window_size):
+    if window_size != 11:
+        raise NotImplementedError("ssim: only window_size=11 (the reference's default, the one train.py uses) is implemented")
+
+
+def ssim(img1, img2, window_size=11, size_average=True):
+    """utils/loss_utils.py:168-198 on [C,H,W] or [B,C,H,W]: the mean of the SSIM map, or with size_average=False the mean per
+    image ([B]; a [C,H,W] input is one image).  Differentiable in img1."""
+    _check_window(window_size)
+    if img1.dim() == 3 and not size_average:
+        return _Photometric.apply(img1[None], img2[None], 0.0, 0.0, 1.0, False)
+    return _Photometric.apply(img1, img2, 0.0, 0.0, 1.0, bool(size_average))
+
+
+def photometric_loss(image, gt, lambda_dssim=0.2):
+    """(1 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1 - ssim(image, gt)): 3DGS's RGB loss
+    (arguments/__init__.py:88: lambda_dssim = 0.2), one forward launch plus the sum of the workgroups' partials, one backward
+    launch.  `image` may be the [3,H,W] view render() returns: it is read, and its gradient written, through its strides."""
+    lam = float(lambda_dssim)
+    return _Photometric.apply(image, gt, lam, 1.0 - lam, -lam, True)
+
+
+def psnr(img1, img2):
+    """utils/image_utils.py:17-19: 20 log10(1 / sqrt(mse)) with the mean squared error per entry of the FIRST dimension (the
+    reference's batch), [B, 1]; from the third partial sum of the forward kernel.  Not differentiated."""
+    with torch.no_grad():
+        a = img1 if img1.dim() == 4 else img1[:, None]
+        b = img2 if img2.dim() == 4 else img2[:, None]
+        _, sums, _, _, (_, _, _, _, planes, images, h, w) = _photo_forward(a, b, 0.0, 0.0, 0.0, False, False)
+        mse = sums[:, 2:3] / float(planes // images * h * w)
+        return (20.0 * torch.log10(1.0 / torch.sqrt(mse))).float()

@@ -327,6 +327,38 @@ int gags_depthsample_scatter(int64_t n, int n_cams, int h, int w, const float *x
                              const float *depths, float vis_thresh, int cut_bound, const float *min_depth, float *samples,
                              void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- N7: the photometric loss of the RGB stage (utils/loss_utils.py:20, 158-198; utils/image_utils.py:17-19) ------------
+ * 3DGS's (1 - lambda) L1 + lambda (1 - SSIM) on images of `planes` = images x channels planes of h x w pixels, one forward and
+ * one backward kernel (csrc/photometric.hip).  SSIM is the reference's: an 11 x 11 zero-padded window whose weight is the
+ * product of two of the eleven taps `window` (a HOST array: the taps travel as kernel arguments; gags_amd.losses.SSIM_WINDOW),
+ * moments mu1, mu2, E[x^2] - mu1^2, E[y^2] - mu2^2, E[xy] - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2 (as floats),
+ *     map = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)).
+ * x, y and v_x are read and written through ELEMENT strides (plane, row, column): the rasterizer's [H, W, 3] memory is consumed
+ * as it lies (strides 1, 3 W, 3), a contiguous [C, H, W] target through (H W, W, 1).  Strides must be >= 0 for x and y and
+ * describe non-overlapping elements for v_x.  The filtered moments and everything derived from them are formed in double from
+ * the float inputs (the subtraction E[x^2] - mu1^2 cancels on low-contrast windows); what is stored is float.
+ *
+ * Forward: every workgroup (a 32 x 16 tile of one plane) leaves three doubles in `partials`
+ * [gags_photometric_partials(planes, h, w), 3]: sum of the map, sum |x - y|, sum (x - y)^2 over its pixels; no atomics.  One
+ * more small launch adds them in a fixed order: sums[n_images, 3] (planes % n_images == 0; an image is planes / n_images
+ * consecutive planes of n = that many h w elements) and, with r = sums / n per image (reduce_all = 0) or over everything
+ * (reduce_all = 1: n = planes h w, one result),
+ *     out[i] = bias + wa r[1] + wb r[0]   (float; photometric loss: bias = lambda, wa = 1 - lambda, wb = -lambda; SSIM: 0, 0, 1)
+ *     k[0] = wa / n, k[1] = wb / n        (float; what the backward's coefficients are the cotangent's multiples of)
+ * dm (optional) [3, planes, h, w]: the per-pixel partial derivatives of the map the backward filters -- d map / d mu1 (with the
+ * mu-terms of the two below folded in), d map / d sigma1^2, d map / d sigma12.  ssim_map (optional) [planes, h, w]. */
+int64_t gags_photometric_partials(int planes, int h, int w); /* host only; 0 for a shape the entries reject */
+int gags_photometric_fwd(int planes, int n_images, int h, int w, const float *x, int64_t x_sp, int64_t x_sr, int64_t x_sc,
+                         const float *y, int64_t y_sp, int64_t y_sr, int64_t y_sc, const float *window, double bias, double wa,
+                         double wb, int reduce_all, float *dm, float *ssim_map, double *partials, double *sums, float *out,
+                         float *k, void *stream);
+/* Backward, one launch: v_x = a sign(x - y) + b (F[dm0] + 2 x F[dm1] + y F[dm2]) with F the same zero-padded filter (its own
+ * adjoint), sign(0) = 0, and (a, b) = coef[image of the plane][0..1] read on the device (coef [n_images, 2] floats: the
+ * cotangent times k, or one pair for everything when n_images = 1).  Written through v_x's strides. */
+int gags_photometric_bwd(int planes, int n_images, int h, int w, const float *x, int64_t x_sp, int64_t x_sr, int64_t x_sc,
+                         const float *y, int64_t y_sp, int64_t y_sr, int64_t y_sc, const float *window, const float *dm,
+                         const float *coef, float *v_x, int64_t v_sp, int64_t v_sr, int64_t v_sc, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
