@@ -157,7 +157,7 @@ GAGS_RECS_BY_GAUSSIAN = 256  # C flag: `packed` is the per-Gaussian record table
 GAGS_BWD_ATOMIC = 4  # python-side: use the atomic colours-only backward instead of the staged one
 GAGS_FEAT_F16 = 32  # forward: colors is an fp16 table (include/gags_raster.h)
 GAGS_BWD_F32MFMA = 64  # python-side: staged backward contracts with v_mfma_f32_32x32x2_f32 (round 1-2's kernel) instead of the
-#                        default fp32-equivalent split operands on the 16-bit matrix cores (csrc/raster_bwd_mfma.hip)
+#                        default fp32-equivalent split operands on the 16-bit matrix cores (csrc/raster_bwd_rows.hip)
 GAGS_BWD_BLOCKWAVES = 4096  # python-side: the staged backward's rows kernel in round 4's shape (a wave per 8x8 pixel block, rows
 #                             merged in LDS: GAGS_STAGED_BLOCKWAVES) instead of the default (a wave per 32 channels, rows merged in the accumulators)
 GAGS_BWD_EXACT_WEIGHTS = 8192  # python-side: the default rows kernel with the weights as THREE fp16 terms (exact) and five product terms

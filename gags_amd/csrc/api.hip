@@ -2,74 +2,17 @@
 // (narrow / odd D, full geometry gradients) and the matrix-core kernels (D >= 16, D % 4 == 0;
 // the single-kernel fallbacks: D % 32 == 0).
 #include <cstdlib>
-#include "common.h"
+#include "launch.h"
 #include "scan.h"
 
-// raster_valu.hip
-int gags_raster_fwd_valu(int d, int width, int height, const float *means2d, const float *conics,
-                         const float *opacities, const float *colors, const float *backgrounds,
-                         const int32_t *offsets, const int32_t *flat, int n_isects, float *out, float *alphas,
-                         int32_t *last_ids, hipStream_t st);
-int gags_raster_bwd_valu(int d, int width, int height, const float *means2d, const float *conics,
-                         const float *opacities, const float *colors, const float *backgrounds,
-                         const int32_t *offsets, const int32_t *flat, int n_isects, const float *alphas,
-                         const int32_t *last_ids, const float *v_out, const float *v_alpha, float *v_colors,
-                         float *v_opac, float *v_m2d, float *v_con, bool geom, hipStream_t st);
-// raster_weights.hip
-int gags_pack_isects_launch(int n, int n_isects, const int32_t *flat, const float *means2d, const float *conics,
-                            const float *opacities, const int32_t *radii, void *grec, void *packed, hipStream_t st);
-int gags_raster_weights_launch(int width, int height, int n_gauss, const void *packed, int by_gauss, const int32_t *offsets,
-                               const int32_t *flat, int n_isects, float *wt, int32_t *gid_s, int32_t *sidx_s,
-                               int32_t *hit, int32_t *blk_rows, float *Tbuf, float *alphas, int32_t *last_ids,
-                               hipStream_t st, const float *colors16 = nullptr, const float *backgrounds = nullptr,
-                               float *render_colors = nullptr);
-int gags_list_need_launch(int width, int height, int n_gauss, const void *packed, int by_gauss, const int32_t *offsets,
-                          const int32_t *flat, int n_isects, int32_t *need, hipStream_t st);
-int gags_trim_offsets_launch(int n_tiles, const int32_t *cum, int32_t *off_new, hipStream_t st);
-int gags_trim_gather_launch(int n_tiles, const int32_t *off_old, const int32_t *off_new, const int32_t *flat_in, int32_t *flat_out,
-                            hipStream_t st);
-int gags_trim_last_ids_launch(int width, int height, const int32_t *off_old, const int32_t *off_new, const float *alphas,
-                              int32_t *last_ids, hipStream_t st);
-// raster_fwd_mfma.hip
-int gags_raster_fwd_feat_launch(int d, int width, int height, int n_gauss, const float *colors, int colors_f16, int exact,
-                                const float *backgrounds, const int32_t *offsets, int n_isects,
-                                const int32_t *blk_rows, const float *wt, const int32_t *gid_s, const float *Tbuf,
-                                float *out, hipStream_t st);
-int gags_raster_fwd_fused_launch(int d, int width, int height, const void *packed, const float *colors,
-                                 const float *backgrounds, const int32_t *offsets, const int32_t *flat, int n_isects,
-                                 float *out, float *alphas, int32_t *last_ids, int by_gauss, hipStream_t st);
-// raster_bwd_mfma.hip
-int64_t gags_bwd_staged_scratch_bytes_impl(int64_t rows, int n_gauss, int d);
-int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, const int32_t *offsets, int n_isects,
-                                  const float *v_out, const int32_t *blk_rows, const int32_t *trow, int64_t rows,
-                                  const float *wt, const int32_t *gid_s, const int32_t *trow_s, void *scratch,
-                                  int64_t scratch_bytes, float *v_colors, int stage, int ch_begin, int ch_count,
-                                  const int32_t *rows_dev, const int32_t *wire_pos, float *wire, const uint8_t *keep_prev,
-                                  uint8_t *keep_cur, hipStream_t st);
-int64_t gags_raster_bwd_geom_scratch_bytes_impl(int64_t n_isects, int width, int height, int n_gauss, int d, int64_t n_rows);
-int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const float *colors, const float *backgrounds,
-                                const int32_t *offsets, int n_isects, const void *packed, const float *v_out,
-                                const float *v_alphas, const int32_t *blk_rows, const float *wt, const int32_t *gid_s,
-                                const int32_t *sidx_s, const float *Tbuf, void *scratch, int64_t scratch_bytes, float *v_geo,
-                                int by_gauss, const int32_t *row_base, int64_t n_rows, const int32_t *hit,
-                                const int32_t *flatten_ids, int f32mfma, hipStream_t st);
-int gags_blended_mask_launch(int n_isects, const int32_t *hit, const int32_t *flatten_ids, unsigned char *mask, hipStream_t st);
-int gags_bwd_slot_rows_launch(int width, int height, int n_isects, const int32_t *offsets, const int32_t *blk_rows,
-                              const int32_t *sidx_s, const int32_t *trow, int32_t *trow_s, hipStream_t st);
-int gags_raster_bwd_atomic_launch(int d, int width, int height, const void *packed, const int32_t *offsets,
-                                  const int32_t *flat, int n_isects, const float *v_out, float *v_colors,
-                                  int by_gauss, hipStream_t st);
-
 namespace {
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 struct FwdScratch {
     int64_t wt, gid, sidx, hit, tbuf, total;
 };
 // slot space: gags_slot_count() slots of 64 weights (common.h)
 inline FwdScratch fwd_layout(int64_t n_isects, int width, int height)
 {
-    const int64_t tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    const int64_t slots = gags_slot_count(n_isects, tile_w * tile_h);
+    const int64_t slots = gags_slot_count(n_isects, gags_tiles(width, height).n);
     FwdScratch L;
     int64_t o = 0;
     L.wt = o; o += al256(slots * 256);
@@ -87,8 +30,7 @@ inline bool fused_width(int d) { return d >= 32 && d % 32 == 0; }  // single-ker
 inline bool isects_ok(int64_t n_isects, int width, int height)
 {
     if (n_isects < 0 || n_isects >= GAGS_MAX_ISECTS || width <= 0 || height <= 0) return false;
-    const int64_t tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    return gags_slot_count(n_isects, tile_w * tile_h) < (1ll << 30);
+    return gags_slot_count(n_isects, gags_tiles(width, height).n) < (1ll << 30);
 }
 }  // namespace
 
@@ -182,11 +124,11 @@ extern "C" int gags_trim_lists(int width, int height, const int32_t *isect_offse
                                const int32_t *flatten_ids, int32_t *offsets_out, int32_t *flatten_out, void *stream)
 {
     if (width <= 0 || height <= 0 || !isect_offsets || !need_cum || !offsets_out) return GAGS_EINVAL;
-    const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    int rc = gags_trim_offsets_launch(tile_w * tile_h, need_cum, offsets_out, (hipStream_t)stream);
+    const int n_tiles = gags_tiles(width, height).n;
+    int rc = gags_trim_offsets_launch(n_tiles, need_cum, offsets_out, (hipStream_t)stream);
     if (rc != GAGS_OK || !flatten_out) return rc;  // (flatten_out NULL: the offsets only)
     if (!flatten_ids) return GAGS_EINVAL;
-    return gags_trim_gather_launch(tile_w * tile_h, isect_offsets, offsets_out, flatten_ids, flatten_out, (hipStream_t)stream);
+    return gags_trim_gather_launch(n_tiles, isect_offsets, offsets_out, flatten_ids, flatten_out, (hipStream_t)stream);
 }
 
 extern "C" int gags_trim_last_ids(int width, int height, const int32_t *isect_offsets, const int32_t *offsets_trimmed,
@@ -234,8 +176,7 @@ namespace {
 inline int64_t rowmap_slot_off(int64_t n_isects) { return al256((n_isects + 1) * 4) / 4; }
 inline int64_t slot_count(int64_t n_isects, int width, int height)
 {
-    const int64_t tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    return gags_slot_count(n_isects, tile_w * tile_h);
+    return gags_slot_count(n_isects, gags_tiles(width, height).n);
 }
 }  // namespace
 

@@ -3,7 +3,7 @@
 // gather work over [C, H, W] maps: coalesced along pixels, small tables (segment embeddings, segment statistics) left
 // to L2; nothing is reshaped into a GEMM.  Numerics follow the reference's torch ops (fp32; sums that torch does as
 // one big reduction are accumulated in double here).
-#include "common.h"
+#include "launch.h"
 #include "gags_next.h"
 
 namespace {
@@ -1040,15 +1040,10 @@ extern "C" int gags_segment_stats_runs(int64_t n_pix, int c, const float *x, con
         copies != gags_segment_stats_runs_copies(n_pix, c, n_seg, layout))
         return GAGS_EINVAL;
     const int64_t lds = runs_lds_bytes(c, n_seg);
-    static bool raised = false;  // (dynamic LDS above 64 KB is an opt-in per kernel)
-    if (!raised) {
-        if (hipFuncSetAttribute((const void *)segment_stats_runs_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)RUNS_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void *)segment_stats_runs_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)RUNS_LDS_MAX) != hipSuccess)
-            return GAGS_ELAUNCH;
-        raised = true;
-    }
+    static bool raised[GAGS_MAX_DEVICES];  // (dynamic LDS above 64 KB is an opt-in per kernel and device)
+    if (!gags_raise_dynamic_lds(raised, {(const void *)segment_stats_runs_kernel<16>, (const void *)segment_stats_runs_kernel<1>},
+                                (int)RUNS_LDS_MAX))
+        return GAGS_ELAUNCH;
     if (c == 16)
         hipLaunchKernelGGL(segment_stats_runs_kernel<16>, dim3((unsigned)copies), dim3(256), (size_t)lds, (hipStream_t)stream, n_pix, x,
                            seg, n_seg, s1, s2, cnt);

@@ -19,12 +19,8 @@
 //     result: no atomics on the output, bit-reproducible.
 #include <algorithm>
 #include <cmath>
-#include "common.h"
+#include "launch.h"
 #include "gags_next.h"
-
-int64_t gags_sort_u64_scratch_bytes(int64_t n);
-int gags_sort_pairs_u64(int64_t n, int first_bit, int nbits, const uint64_t *keys_in, const int32_t *vals_in,
-                        uint64_t *keys_out, int32_t *vals_out, void *scratch, int64_t scratch_bytes, hipStream_t st);
 
 namespace {
 
@@ -197,8 +193,6 @@ __global__ __launch_bounds__(256) void vote_kernel(int64_t n, int n_masks, const
     out[o] = ((int64_t)c > (int64_t)threshold || (mask[o] && c >= 10)) ? 1 : 0;
     if (counts) counts[o] = c;
 }
-
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
 inline unsigned grid_stride_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 2048); }
 

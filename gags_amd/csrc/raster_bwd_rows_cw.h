@@ -1,4 +1,4 @@
-// ---- staged: rows, CHANNEL waves (round 5) -- included by raster_bwd_mfma.hip inside its anonymous namespace ----------
+// ---- staged: rows, CHANNEL waves (round 5) -- included by raster_bwd_rows.hip inside its anonymous namespace ----------
 // The contraction of raster_bwd_rows_f16 with the roles of the four waves turned by 90 degrees.  There, wave b owns pixel
 // block b of the tile for all 128 channels of the slice and the four waves' partial rows of a tile row meet in LDS (park, two
 // barriers whose position the four run lengths negotiate, a 240-instruction merge); here wave w owns 32 CHANNELS of the
@@ -26,18 +26,6 @@
 // two: per (tile, channel) for the cotangent, and for the weights ONE constant for the view since round 6 (FIXS below; until
 // round 5, and still with three-term weights or GAGS_BWD_ROWSCALE=1, one per (row, block), applied when a block's accumulator
 // is folded into the total); both leave when the row is stored.
-__device__ __forceinline__ void split8x2(const float (&x)[8], float scale, f16x8 &hi, f16x8 &lo)
-{
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) {
-        const f32x2v_t v = {x[i] * scale, x[i + 1] * scale};
-        const f16x2_t h = __builtin_convertvector(v, f16x2_t);
-        const f32x2v_t r = v - __builtin_convertvector(h, f32x2v_t);
-        const f16x2_t l = __builtin_convertvector(r, f16x2_t);
-        hi[i] = h[0]; hi[i + 1] = h[1];
-        lo[i] = l[0]; lo[i + 1] = l[1];
-    }
-}
 
 // TA = fp16 terms of a weight (2, or 3: exact), NM = product terms (3 = a0 b0 + a0 b1 + a1 b0; 5 with TA = 3)
 // FIXS (round 6, the default with <2, 3>): ONE weight scale for the whole view, 2^15, instead of a power of two per (row, block).

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "raster_mfma_common.h"
+#include "launch.h"
 
 using namespace gags_mfma;
 

@@ -207,4 +207,39 @@ struct HitStream {
     }
 };
 
+// ---- fp32 values as sums of fp16 terms (operands of the 16-bit matrix cores: raster_bwd_rows.hip, raster_bwd_geom.hip) ----
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// two or three terms, each the round-to-nearest of what the previous ones left over of x * scale;
+// pairs through v_cvt_pk_f16_f32 (round to nearest even, new on gfx950): one conversion instruction per two values and term
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2v_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split8x2(const float (&x)[8], float scale, f16x8 &hi, f16x8 &lo)
+{
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+        const f32x2v_t v = {x[i] * scale, x[i + 1] * scale};
+        const f16x2_t h = __builtin_convertvector(v, f16x2_t);
+        const f32x2v_t r = v - __builtin_convertvector(h, f32x2v_t);
+        const f16x2_t l = __builtin_convertvector(r, f16x2_t);
+        hi[i] = h[0]; hi[i + 1] = h[1];
+        lo[i] = l[0]; lo[i + 1] = l[1];
+    }
+}
+
+__device__ __forceinline__ void split8x3(const float (&x)[8], float scale, f16x8 &t0, f16x8 &t1, f16x8 &t2)
+{
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+        const f32x2v_t v = {x[i] * scale, x[i + 1] * scale};
+        const f16x2_t h = __builtin_convertvector(v, f16x2_t);
+        const f32x2v_t r = v - __builtin_convertvector(h, f32x2v_t);
+        const f16x2_t m = __builtin_convertvector(r, f16x2_t);
+        const f32x2v_t q = r - __builtin_convertvector(m, f32x2v_t);
+        const f16x2_t l = __builtin_convertvector(q, f16x2_t);
+        t0[i] = h[0]; t0[i + 1] = h[1];
+        t1[i] = m[0]; t1[i + 1] = m[1];
+        t2[i] = l[0]; t2[i + 1] = l[1];
+    }
+}
+
 }  // namespace gags_mfma

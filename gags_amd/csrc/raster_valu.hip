@@ -8,7 +8,7 @@
 // depth-sorted range are staged through LDS in batches of 256 (xy, conic, opacity, id).
 // Feature rows are wave-uniform: they are fetched with scalar loads (SGPR operands of v_fmac),
 // not through LDS.  HBM/LDS-latency bound at these widths.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 

@@ -13,7 +13,7 @@
 //   gid[slot]      : Gaussian id of the slot (N for the zero slot that pads an odd count);
 //   sidx[slot]     : sorted intersection index of the slot (-1 for the pad slot), and hit[sidx] = 1: the backward
 //                    numbers the (tile, Gaussian) pairs that blended anything by a prefix sum over `hit` and merges
-//                    the four blocks' partial gradient rows of such a pair into ONE row (raster_bwd_mfma.hip);
+//                    the four blocks' partial gradient rows of such a pair into ONE row (raster_bwd_rows.hip);
 //   blk_rows[blk]  : number of slots of the block (even);
 //   Tbuf / render_alphas / last_ids : per-pixel results of the chain.
 // Slots of a block live in a fixed, sparse region of the slot space (no counting pre-pass):
@@ -22,6 +22,7 @@
 // 8x8 rather than 8x4 blocks: a Gaussian then leaves ~36 % fewer (block, slot) rows, and those rows are the
 // backward's HBM traffic; the price is ~30 % more zero weights inside the MFMA tiles.
 #include "raster_mfma_common.h"
+#include "launch.h"
 
 using namespace gags_mfma;
 

@@ -9,7 +9,7 @@
 // Traffic per pass: read 12 B + write 12 B per pair + one extra 8 B key read for the
 // histogram = 32 B/pair; 45-bit keys at 1080p (13 tile bits) need 6 passes.
 // HBM-bound integer work: nothing here is reshaped into a GEMM.
-#include "common.h"
+#include "launch.h"
 #include "scan.h"
 
 namespace {
