@@ -145,6 +145,13 @@ SIGNATURES = {
                                     _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_photometric_bwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
                                     _i64, _i64, _i64, _vp]),
+    # N8: adaptive density control (csrc/densify.hip)
+    "gags_densify_stats": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "gags_densify_decide": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "gags_densify_plan": (_i32, [_i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gags_densify_gather": (_i32, [_i64, _vp, _vp, _i32, _vp, _vp]),
+    "gags_densify_children": (_i32, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "gags_reset_opacity": (_i32, [_i64, _vp, _vp, _vp, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)
@@ -174,6 +181,15 @@ GAGS_FWD_FUSED = 8  # python-side: single-kernel matrix-core forward (no scratch
 GAGS_STAGE_ALL, GAGS_STAGE_ROWS, GAGS_STAGE_SORT, GAGS_STAGE_REDUCE, GAGS_STAGE_MASK = 0, 1, 2, 3, 15
 GAGS_STAGED_F32MFMA, GAGS_STAGED_OUT_F16, GAGS_STAGED_PREZEROED = 32, 64, 128
 GAGS_STAGED_RANGE_SCRATCH, GAGS_STAGED_BLOCKWAVES, GAGS_STAGED_EXACT_WEIGHTS = 256, 512, 1024
+GAGS_KIND_KEEP, GAGS_KIND_CLONE, GAGS_KIND_CHILD_A, GAGS_KIND_CHILD_B = 0, 1, 2, 3  # `kind` of gags_densify_plan
+GAGS_GATHER_MAX_DESC, GAGS_GATHER_COPY, GAGS_GATHER_MOMENT = 24, 0, 1  # gags_densify_gather
+
+
+class GatherDesc(ctypes.Structure):
+    """gags_gather_desc of include/gags_next.h."""
+    _fields_ = [("in_", _vp), ("out", _vp), ("row_floats", ctypes.c_int32), ("mode", ctypes.c_int32)]
+
+
 GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instructions (what GAGS_BWD_F32MFMA asks of that kernel)
 
 _lib = None

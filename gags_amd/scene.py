@@ -12,7 +12,8 @@ Only what `render(...)` reads is mirrored:
   `world_view_transform` = W2C^T, built as utils/graphics_utils.py:38-49 does.
 
 PLY / checkpoint I/O (`save_ply`, `load_ply`, `capture`, `restore`: SURVEY.md 8f N3) go through
-gags_amd/io_formats.py; densification and COLMAP loading are out of scope.
+gags_amd/io_formats.py; adaptive density control (`densify_and_prune`, `add_densification_stats`, `reset_opacity`, ...:
+SURVEY.md 8f N8) through gags_amd/densify.py; COLMAP loading is out of scope.
 """
 import math
 
@@ -175,8 +176,9 @@ class GaussianModel:
         return self
 
     def capture(self):
-        """The reference's 13-tuple (scene/gaussian_model.py:63-78); the densification statistics it carries are
-        empty here (densification is dead code in the feature flow)."""
+        """The reference's 13-tuple (scene/gaussian_model.py:63-78).  The densification statistics it carries are the
+        model's own once training_setup_rgb / the densification methods created them, zeros of the right shapes before
+        (the feature flow never densifies)."""
         dev = self._xyz.device
         n = self._xyz.shape[0]
         return (self.active_sh_degree, self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
@@ -217,3 +219,85 @@ class GaussianModel:
         else:  # host-side bookkeeping only (CPU unit tests): the stock optimizer the reference uses
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
         return self.optimizer
+
+    # -- the RGB stage's optimizer and adaptive density control: scene/gaussian_model.py:147-149, 183-220, 261-264, 321-482
+    #    (gags_amd/densify.py; train.py:206-218 runs on these unchanged) ------------------------------------------------
+    def training_setup_rgb(self, training_args, semantic_dim=16, spatial_lr_scale=None):
+        """Every tensor optimised: the seven named groups the reference's training_setup keeps as comments
+        (scene/gaussian_model.py:193-199) with the rates of arguments/__init__.py:76-85, FeatureAdam(lr=0.0, eps=1e-15), the
+        densification statistics, percent_dense and the position schedule.  training_setup (feature-only) is untouched."""
+        from . import densify
+        from .optim import FeatureAdam
+        if not self._xyz.is_cuda:
+            raise RuntimeError("gags_amd.scene.training_setup_rgb: no CPU path (the model must live on the GPU)")
+        n, dev = self._xyz.shape[0], self._xyz.device
+        if spatial_lr_scale is not None:
+            self.spatial_lr_scale = spatial_lr_scale
+        elif not hasattr(self, "spatial_lr_scale"):
+            self.spatial_lr_scale = 1.0
+        self.percent_dense = training_args.percent_dense
+        if self._semantic_feature is None or self._semantic_feature.shape[0] != n:
+            self._semantic_feature = nn.Parameter(torch.zeros((n, semantic_dim), device=dev))
+        for _, attr in densify.GROUPS:
+            p = getattr(self, attr)
+            if not isinstance(p, nn.Parameter):
+                p = nn.Parameter(p.detach().contiguous().float())
+                setattr(self, attr, p)
+            p.requires_grad_(True)
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        self.max_radii2D = torch.zeros((n,), device=dev)
+        a = training_args
+        groups = [
+            {"params": [self._xyz], "lr": a.position_lr_init * self.spatial_lr_scale, "name": "xyz"},
+            {"params": [self._features_dc], "lr": a.feature_lr, "name": "f_dc"},
+            {"params": [self._features_rest], "lr": a.feature_lr / 20.0, "name": "f_rest"},
+            {"params": [self._opacity], "lr": a.opacity_lr, "name": "opacity"},
+            {"params": [self._scaling], "lr": a.scaling_lr, "name": "scaling"},
+            {"params": [self._rotation], "lr": a.rotation_lr, "name": "rotation"},
+            {"params": [self._semantic_feature], "lr": a.semantic_feature_lr, "name": "semantic_feature"},
+        ]
+        self.optimizer = FeatureAdam(groups, lr=0.0, eps=1e-15)
+        self.xyz_scheduler_args = dict(lr_init=a.position_lr_init * self.spatial_lr_scale,
+                                       lr_final=a.position_lr_final * self.spatial_lr_scale,
+                                       lr_delay_mult=a.position_lr_delay_mult, max_steps=a.position_lr_max_steps)
+        self.invalidate_activations()
+        return self.optimizer
+
+    def update_learning_rate(self, iteration):
+        """Learning rate of the "xyz" group at `iteration` (host arithmetic); None when there is no such group."""
+        from . import densify
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                lr = densify.expon_lr(iteration, **self.xyz_scheduler_args)
+                group["lr"] = lr
+                return lr
+
+    def oneupSHdegree(self):
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, width, height):
+        """accum += |grad scaled to the [-1, 1] screen|, denom += 1 over update_filter.  The reference also scales
+        viewspace_point_tensor.grad in place; nothing reads it afterwards, so it is left as it is."""
+        from . import densify
+        densify.stats(self, viewspace_point_tensor.grad, None, update_filter, None, width, height)
+
+    def update_max_radii(self, radii, visibility_filter):
+        """train.py:209: max_radii2D[v] = max(max_radii2D[v], radii[v])."""
+        from . import densify
+        densify.stats(self, None, radii, None, visibility_filter, 0, 0)
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, *, generator=None, samples=None):
+        """Clone, split and prune in one plan and one gather.  samples: the [2 n_split, 3] standard-normal draws of the split
+        children (tests); otherwise torch.randn(generator=generator) on the device once the count is known."""
+        from . import densify
+        densify.densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, generator=generator, samples=samples)
+
+    def prune_points(self, mask):
+        from . import densify
+        densify.prune_points(self, mask)
+
+    def reset_opacity(self):
+        from . import densify
+        densify.reset_opacity(self)

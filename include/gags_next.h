@@ -359,6 +359,73 @@ int gags_photometric_bwd(int planes, int n_images, int h, int w, const float *x,
                          const float *y, int64_t y_sp, int64_t y_sr, int64_t y_sc, const float *window, const float *dm,
                          const float *coef, float *v_x, int64_t v_sp, int64_t v_sr, int64_t v_sc, void *stream);
 
+/* ---- N8: adaptive density control (scene/gaussian_model.py:261-264, 321-482; train.py:206-218) ---------------------------
+ * densify_and_prune as ONE plan and ONE gather (csrc/densify.hip).  Every clone, split and prune decision -- including whether
+ * a split child survives the final prune -- depends only on the SOURCE Gaussian, so: decide (four flags per Gaussian), the
+ * library's inclusive prefix sum on each flag array (K5; totals stay on the device), plan (source row and class of every output
+ * row), gather (every tensor, once), children (positions and scales of the split children).  fp32, no FMA, IEEE division, no
+ * atomics: bit-reproducible.  n = 0 (and an output of 0 rows) is accepted everywhere and launches nothing.
+ *
+ * Thresholds travel as floats: the reference compares a float32 tensor with a Python scalar, i.e. with the scalar rounded to
+ * float32.  The caller forms percent_dense * extent and 0.1 * extent in double and rounds once.
+ *
+ * Statistics of one view (gaussian_model.py:476-482, train.py:209), one thread per Gaussian:
+ *   u = update_filter[i] != 0 (NULL: radii[i] > 0):      accum[i] += sqrt(fl(gx half_w)^2 + fl(gy half_h)^2), denom[i] += 1
+ *   v = visibility_filter[i] != 0 (NULL: radii[i] > 0):  max_radii[i] = max(max_radii[i], (float) radii[i])
+ * with (gx, gy) = v_means2d[i, 0..1].  v_means2d NULL: only the radii update; max_radii NULL: only accum / denom. */
+int gags_densify_stats(int n, const float *v_means2d, const int32_t *radii, const unsigned char *update_filter,
+                       const unsigned char *visibility_filter, float half_w, float half_h, float *accum, float *denom,
+                       float *max_radii, void *stream);
+/* Decisions.  g = accum / denom with NaN -> 0 (x / 0 = inf stays), m = max_k exp(scaling[i, k]), o = sigmoid(opacity[i]):
+ *   clone    = |g| >= max_grad and m <= dense_thr          split = g >= max_grad and m > dense_thr
+ *   prune    = o < min_opacity or (use_screen and (0 > max_screen_size or m > world_thr))
+ *   prune_ch = o < min_opacity or (use_screen and (0 > max_screen_size or m / 1.6f > world_thr))
+ * (the screen-size test reads max_radii2D AFTER the clone step zeroed it: it compares zeros, as the reference does).
+ * flags [4, n] int32: keeps itself = !split and !prune; clone survives = clone and !prune; split-selected = split;
+ * children survive = split and !prune_ch. */
+int gags_densify_decide(int n, const float *accum, const float *denom, const float *scaling, const float *opacity,
+                        float max_grad, float dense_thr, float min_opacity, float world_thr, float max_screen_size,
+                        int use_screen, int32_t *flags, void *stream);
+/* Plan.  cum [4, n] = the inclusive prefix sums of the four flag rows, totals [4] (DEVICE) their sums (TK, TC, TS, TH); n_out =
+ * TK + TC + 2 TH as the caller read it.  Output order: kept originals, surviving clones, surviving first children, surviving
+ * second children, each in source order.  Per output row j: src[j] = source Gaussian, kind[j] = GAGS_KIND_*, zrow[j] = row of
+ * the [2 TS, 3] normal samples a child uses = rank of its source among the split-selected (before pruning) + copy * TS
+ * (-1 for rows that are no children).  Rows at or past n_out are not written. */
+#define GAGS_KIND_KEEP 0
+#define GAGS_KIND_CLONE 1
+#define GAGS_KIND_CHILD_A 2
+#define GAGS_KIND_CHILD_B 3
+int gags_densify_plan(int n, const int32_t *flags, const int32_t *cum, const int32_t *totals, int64_t n_out, int32_t *src,
+                      unsigned char *kind, int32_t *zrow, void *stream);
+/* Gather, one launch for up to GAGS_GATHER_MAX_DESC tensors: out[j, :] = in[src[j], :] (COPY), or that for kind[j] == KEEP and
+ * zeros otherwise (MOMENT: Adam's exp_avg / exp_avg_sq).  descs_host is a HOST array; rows are row_floats > 0 contiguous
+ * floats.  16-byte lanes where row_floats % 4 == 0 and both bases are 16-byte aligned, 4-byte lanes otherwise; element offsets
+ * are 64-bit (n_out row_floats may pass 2^31; n_out itself < 2^31).  src must index rows of `in`. */
+#define GAGS_GATHER_MAX_DESC 24
+#define GAGS_GATHER_COPY 0
+#define GAGS_GATHER_MOMENT 1
+typedef struct {
+    const float *in;
+    float *out;
+    int32_t row_floats;
+    int32_t mode;
+} gags_gather_desc;
+int gags_densify_gather(int64_t n_out, const int32_t *src, const unsigned char *kind, int n_desc,
+                        const gags_gather_desc *descs_host, void *stream);
+/* Children: rows j in [first_child, n_out) of xyz_out / scaling_out ([n_out, 3]; overwrites what the gather copied there), from
+ * source i = src[j] (< n_src) and sample row k = zrow[j] (< n_z) of z [n_z, 3], in this order of operations:
+ *   norm = sqrt(((w w + x x) + y y) + z z) of the STORED quaternion (w, x, y, z); q = stored / norm (four divisions)
+ *   R = the matrix of utils/general_utils.py:78-99: R00 = 1 - 2 (y y + z z), R01 = 2 (x y - w z), R02 = 2 (x z + w y), ...
+ *   t_a = exp(scaling[i, a]) * z[k, a]
+ *   xyz_out[j, r] = ((R[r][0] t_0 + R[r][1] t_1) + R[r][2] t_2) + xyz[i, r]
+ *   scaling_out[j, a] = log(exp(scaling[i, a]) / 1.6f)                                  (1.6f = fl32(0.8 * 2)) */
+int gags_densify_children(int64_t n_out, int64_t first_child, int n_src, const int32_t *src, const int32_t *zrow,
+                          const float *xyz_in, const float *scaling_in, const float *rotation_in, const float *z, int64_t n_z,
+                          float *xyz_out, float *scaling_out, void *stream);
+/* reset_opacity (gaussian_model.py:261-264), in place: x = min(sigmoid(o), 0.01f) (a NaN stays), o = log(x / (1 - x));
+ * exp_avg / exp_avg_sq (each optional) = 0. */
+int gags_reset_opacity(int64_t n, float *opacity, float *exp_avg, float *exp_avg_sq, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
