@@ -152,6 +152,9 @@ SIGNATURES = {
     "gags_densify_gather": (_i32, [_i64, _vp, _vp, _i32, _vp, _vp]),
     "gags_densify_children": (_i32, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "gags_reset_opacity": (_i32, [_i64, _vp, _vp, _vp, _vp]),
+    # N9: scene initialisation from a point cloud (csrc/knn.hip)
+    "gags_knn3_dist2_scratch_bytes": (_i64, [_i64]),
+    "gags_knn3_dist2": (_i32, [_i64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

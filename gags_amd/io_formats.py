@@ -4,6 +4,8 @@
 * point_cloud.ply -- binary little-endian PLY, one `vertex` element of float32 properties in the order of
   scene/gaussian_model.py:222-237 (`construct_list_of_attributes`): x y z nx ny nz f_dc_* f_rest_* opacity scale_*
   rot_* semantic_*; written / read as :240-259 / :266-318 do (f_dc / f_rest stored channel-major: `transpose(1,2)`).
+* points3D.ply    -- the initial point cloud as storePly / fetchPly keep it (scene/dataset_readers.py:206-229): x y z nx ny
+  nz float32 and red green blue uchar, binary little-endian (`write_point_cloud` / `read_point_cloud`).
 * chkpnt*.pth     -- `torch.save((gaussians.capture(), iteration))`, capture() being the 13-tuple of
   scene/gaussian_model.py:63-78 (a 12-tuple for an RGB checkpoint without features: :80-113, train.py:82-94).
 * <image>_f.npy [n_seg, 512] / <image>_s.npy [4, h, w] -- per-image segment embeddings and the four segment-id
@@ -122,6 +124,41 @@ def read_ply(path, max_sh_degree=3):
         "rotation": np.stack([col(nm) for nm in numbered("rot")], axis=1),
         "semantic_feature": np.stack([col(nm) for nm in sem_names], axis=1) if sem_names else None,
     }
+
+
+POINT_CLOUD_PROPERTIES = (("x", "float"), ("y", "float"), ("z", "float"), ("nx", "float"), ("ny", "float"), ("nz", "float"),
+                          ("red", "uchar"), ("green", "uchar"), ("blue", "uchar"))  # storePly's dtype, in file order
+
+
+def write_point_cloud(path, xyz, rgb):
+    """storePly (scene/dataset_readers.py:214-229): positions [N,3] as float32, zero normals, colours [N,3] in 0 .. 255 as
+    uchar (cast as numpy's assignment to a 'u1' field casts: truncation)."""
+    xyz = np.asarray(xyz)
+    rgb = np.asarray(rgb)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+        raise ValueError(f"write_point_cloud: xyz {xyz.shape} and rgb {rgb.shape} must both be [N, 3]")
+    data = np.zeros(xyz.shape[0], dtype=[(nm, _PLY_TYPES[ty]) for nm, ty in POINT_CLOUD_PROPERTIES])
+    for a, nm in enumerate(("x", "y", "z")):
+        data[nm] = xyz[:, a]
+    for a, nm in enumerate(("red", "green", "blue")):
+        data[nm] = rgb[:, a]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]
+    header += "".join(f"property {ty} {nm}\n" for nm, ty in POINT_CLOUD_PROPERTIES) + "end_header\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(data.tobytes())
+
+
+def read_point_cloud(path):
+    """fetchPly (scene/dataset_readers.py:206-212) -> scene.BasicPointCloud: points [N,3] in the file's type, colors [N,3] =
+    red green blue / 255.0 (float64), normals [N,3]."""
+    from .scene import BasicPointCloud
+    _, d = read_ply_table(path)
+    positions = np.vstack([d["x"], d["y"], d["z"]]).T
+    colors = np.vstack([d["red"], d["green"], d["blue"]]).T / 255.0
+    normals = np.vstack([d["nx"], d["ny"], d["nz"]]).T
+    return BasicPointCloud(points=positions, colors=colors, normals=normals)
 
 
 def load_language_features(prefix, render_hw=None, device="cpu"):

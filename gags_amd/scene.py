@@ -13,9 +13,12 @@ Only what `render(...)` reads is mirrored:
 
 PLY / checkpoint I/O (`save_ply`, `load_ply`, `capture`, `restore`: SURVEY.md 8f N3) go through
 gags_amd/io_formats.py; adaptive density control (`densify_and_prune`, `add_densification_stats`, `reset_opacity`, ...:
-SURVEY.md 8f N8) through gags_amd/densify.py; COLMAP loading is out of scope.
+SURVEY.md 8f N8) through gags_amd/densify.py; a model is started from a point cloud by `create_from_pcd` (SURVEY.md 8f N9:
+gags_amd/knn.py for the initial scales, io_formats.read_point_cloud for points3D.ply, `nerfpp_norm` for the cameras' extent);
+the COLMAP binary and text loaders are out of scope.
 """
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -62,6 +65,65 @@ class Camera:
 
 def inverse_sigmoid(x):
     return torch.log(x / (1 - x))
+
+
+class BasicPointCloud(NamedTuple):
+    """utils/graphics_utils.py:17-20: what fetchPly returns and create_from_pcd takes."""
+    points: np.ndarray
+    colors: np.ndarray
+    normals: np.ndarray
+
+
+SH_C0 = 0.28209479177387814  # utils/sh_utils.py:24
+
+
+def RGB2SH(rgb):
+    """utils/sh_utils.py:114-115."""
+    return (rgb - 0.5) / SH_C0
+
+
+def SH2RGB(sh):
+    """utils/sh_utils.py:117-118."""
+    return sh * SH_C0 + 0.5
+
+
+def nerfpp_norm(cameras):
+    """getNerfppNorm (scene/dataset_readers.py:123-147) over objects with `.R` and `.T` (this module's Camera, or the reference's
+    CameraInfo): {"translate": minus the mean camera centre [3], "radius": 1.1 x the largest distance of a centre from it}.
+    The radius is the `cameras_extent` that create_from_pcd takes as spatial_lr_scale and densify_and_prune as extent.
+    Host numpy, in the reference's order of operations."""
+    centers = []
+    for cam in cameras:
+        c2w = np.linalg.inv(getWorld2View2(cam.R, cam.T))
+        centers.append(c2w[:3, 3:4])
+    centers = np.hstack(centers)
+    center = np.mean(centers, axis=1, keepdims=True)
+    diagonal = np.max(np.linalg.norm(centers - center, axis=0, keepdims=True))
+    return {"translate": -center.flatten(), "radius": diagonal * 1.1}
+
+
+def _init_tensors(points, colors, dist2, max_sh_degree, semantic_feature_size=0, speedup=False):
+    """The element-wise part of create_from_pcd (scene/gaussian_model.py:153-180) on whatever device its inputs live on:
+    points [N,3] and colors [N,3] float32 tensors, dist2 [N] the 3-nearest-neighbour mean squared distances.  Returns the
+    raw tensors by attribute name (semantic feature: None when semantic_feature_size == 0)."""
+    n, dev = points.shape[0], points.device
+    # RGB2SH with a tensor divisor: torch divides by a Python scalar on the GPU as a product with its reciprocal (2 ulp from
+    # the reference's CPU result); tensor / tensor is the IEEE division on both devices
+    fused_color = (colors - 0.5) / torch.tensor(SH_C0, dtype=colors.dtype, device=dev)
+    features = torch.zeros((n, 3, (max_sh_degree + 1) ** 2), dtype=torch.float32, device=dev)
+    features[:, :3, 0] = fused_color
+    semantic = None
+    if semantic_feature_size != 0:
+        if speedup:
+            semantic_feature_size = int(semantic_feature_size / 32)
+        semantic = torch.zeros((n, semantic_feature_size), dtype=torch.float32, device=dev)
+    scales = torch.log(torch.sqrt(torch.clamp_min(dist2, 0.0000001)))[..., None].repeat(1, 3)
+    rots = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    rots[:, 0] = 1
+    opacities = inverse_sigmoid(0.1 * torch.ones((n, 1), dtype=torch.float32, device=dev))
+    return {"_xyz": points, "_features_dc": features[:, :, 0:1].transpose(1, 2).contiguous(),
+            "_features_rest": features[:, :, 1:].transpose(1, 2).contiguous(), "_scaling": scales, "_rotation": rots,
+            "_opacity": opacities, "_semantic_feature": semantic, "max_radii2D": torch.zeros((n,), device=dev)}
 
 
 class GaussianModel:
@@ -157,6 +219,24 @@ class GaussianModel:
             m._semantic_feature = nn.Parameter(semantic_feature.contiguous().float(), requires_grad=True)
         m.active_sh_degree = sh_degree if active_sh_degree is None else active_sh_degree
         return m
+
+    def create_from_pcd(self, pcd, spatial_lr_scale, semantic_feature_size=0, speedup=False, device="cuda"):
+        """scene/gaussian_model.py:151-180, field by field: positions from pcd.points, SH band 0 from pcd.colors (in [0, 1]),
+        the higher bands zero, isotropic log-scales from the distance to the three nearest neighbours (gags_amd/knn.py: the
+        HIP kernel, no CPU path), identity rotations, opacity 0.1, a zero semantic feature of semantic_feature_size (/ 32
+        with speedup) columns unless the size is 0.  Every tensor is an nn.Parameter with requires_grad=True;
+        active_sh_degree is 0 and spatial_lr_scale is kept for training_setup_rgb."""
+        from . import knn
+        self.spatial_lr_scale = spatial_lr_scale
+        points = torch.tensor(np.asarray(pcd.points)).float().to(device)
+        colors = torch.tensor(np.asarray(pcd.colors)).float().to(device)
+        t = _init_tensors(points, colors, knn.dist2(points), self.max_sh_degree, semantic_feature_size, speedup)
+        self.max_radii2D = t.pop("max_radii2D")
+        for attr, v in t.items():
+            setattr(self, attr, None if v is None else nn.Parameter(v.contiguous().requires_grad_(True)))
+        self.active_sh_degree = 0
+        self.invalidate_activations()
+        return self
 
     # -- on-disk formats: scene/gaussian_model.py:63-113,240-318 (gags_amd/io_formats.py) ----------------------
     def save_ply(self, path):

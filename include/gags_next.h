@@ -426,6 +426,21 @@ int gags_densify_children(int64_t n_out, int64_t first_child, int n_src, const i
  * exp_avg / exp_avg_sq (each optional) = 0. */
 int gags_reset_opacity(int64_t n, float *opacity, float *exp_avg, float *exp_avg_sq, void *stream);
 
+/* ---- N9: scene initialisation from a point cloud (scene/gaussian_model.py:151-180 create_from_pcd; simple_knn distCUDA2) ------
+ * dist2[i] = each point's mean squared distance to its three nearest neighbours.  The numerical contract: for point i, over all
+ * j != i (excluded by INDEX, not by position: a duplicate point has distance 0 and counts as a neighbour),
+ *   d2_ij = (dx*dx + dy*dy) + dz*dz,  dx = x_j - x_i (dy, dz likewise), float32, no FMA
+ *   b0 <= b1 <= b2 = the three smallest d2_ij as VALUES
+ *   dist2[i] = ((b0 + b1) + b2) / 3.0f                                    written in input order.
+ * The multiset of the three smallest values does not depend on the visiting order: the result is bit-reproducible and
+ * bit-equal to a float32 brute force (tests/knn_ref.py), whatever the traversal (csrc/knn.hip: Morton order, boxes of 256
+ * sorted points pruned by a float32-exact lower bound).
+ * n < 4 (the reference would give a point an infinite scale) or n >= 2^31: GAGS_EINVAL, nothing launched; the scratch size of
+ * such an n is 0.  Non-finite coordinates give unspecified values (the call still terminates and stays inside its buffers).
+ * xyz [n, 3] and dist2 [n] are device pointers; scratch is linear in n (about 44 n bytes). */
+int64_t gags_knn3_dist2_scratch_bytes(int64_t n);
+int gags_knn3_dist2(int64_t n, const float *xyz, float *dist2, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
