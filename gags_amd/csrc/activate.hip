@@ -6,8 +6,50 @@
 // Plain HBM / L2-bound image kernels: one thread per pixel, coalesced along x.
 #include "common.h"
 #include "gags_next.h"
+#include "reduce.h"
 
 namespace {
+
+// N4, first half: LERF relevancy (eval/openclip_encoder.py:42-56): one wave per pixel embedding, phrases in LDS.
+constexpr int REL_MAX_PHRASES = 32;
+
+__global__ __launch_bounds__(256) void relevancy_kernel(int64_t n_pix, int c, int n_pos, int n_neg,
+                                                        const float *__restrict__ embed, const float *__restrict__ pos,
+                                                        const float *__restrict__ neg, float *__restrict__ probs)
+{
+    extern __shared__ float ph[];  // [n_pos + n_neg][c]
+    const int np = n_pos + n_neg;
+    for (int i = threadIdx.x; i < np * c; i += 256) ph[i] = i < n_pos * c ? pos[i] : neg[i - n_pos * c];
+    __syncthreads();
+    __shared__ float sims[4][REL_MAX_PHRASES];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t p = (int64_t)blockIdx.x * 4 + wv;
+    if (p >= n_pix) return;
+    float e[16];  // this lane's share of the embedding (c <= 1024)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) e[q] = (lane + 64 * q < c) ? embed[(size_t)p * c + lane + 64 * q] : 0.f;
+    for (int j = 0; j < np; ++j) {
+        float d = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (lane + 64 * q < c) d = fmaf(e[q], ph[j * c + lane + 64 * q], d);
+        for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off, 64);
+        if (lane == 0) sims[wv][j] = d;
+    }
+    if (lane != 0) return;
+    for (int j = 0; j < n_pos; ++j) {
+        float best0 = 0.f, best1 = 0.f;
+        for (int k = 0; k < n_neg; ++k) {
+            const float a = 10.f * sims[wv][j], b = 10.f * sims[wv][n_pos + k];
+            const float m = fmaxf(a, b);
+            const float ea = expf(a - m), eb = expf(b - m);
+            const float p0 = ea / (ea + eb), p1 = eb / (ea + eb);
+            if (k == 0 || p0 < best0) { best0 = p0; best1 = p1; }  // argmin keeps the first minimum
+        }
+        probs[((size_t)j * n_pix + p) * 2] = best0;
+        probs[((size_t)j * n_pix + p) * 2 + 1] = best1;
+    }
+}
 
 // cv2.BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), the default border of cv2.filter2D
 __device__ __forceinline__ int reflect101(int i, int n)
@@ -16,14 +58,6 @@ __device__ __forceinline__ int reflect101(int i, int n)
     while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
     return i;
 }
-
-// float <-> unsigned key with the same order (min / max of the maps by integer atomics: exact and order-independent)
-__device__ __forceinline__ unsigned f2key(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // horizontal pass: rowsum[k, y, x] = sum_{dx = -a .. box-1-a} src[k, y, reflect(x + dx)],  a = box / 2 (cv2's anchor).
 // Sums in double, rounded once at the end of the vertical pass: the reflected border makes neighbouring windows hold the
@@ -64,7 +98,8 @@ __global__ __launch_bounds__(256) void box_cols_kernel(int h, int w, int box, co
         avg[o] = av;
         blended[o] = bl;
     }
-    unsigned kmin = in ? f2key(bl) : 0xffffffffu, kmax = in ? f2key(bl) : 0u, kavg = in ? f2key(av) : 0u;
+    // (three values behind ONE barrier: gags_block_minmax plus a max-only call would be a second barrier and more LDS)
+    unsigned kmin = in ? gags_f2key(bl) : 0xffffffffu, kmax = in ? gags_f2key(bl) : 0u, kavg = in ? gags_f2key(av) : 0u;
     for (int off = 32; off > 0; off >>= 1) {
         kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, off, 64));
         kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, off, 64));
@@ -92,8 +127,8 @@ __global__ __launch_bounds__(256) void normalise_kernel(int64_t hw, float thresh
 {
     const int k = blockIdx.y;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const float mn = key2f(keys[3 * k]), mx = key2f(keys[3 * k + 1]);
-    if (p == 0) { stats[3 * k] = mn; stats[3 * k + 1] = mx; stats[3 * k + 2] = key2f(keys[3 * k + 2]); }
+    const float mn = gags_key2f(keys[3 * k]), mx = gags_key2f(keys[3 * k + 1]);
+    if (p == 0) { stats[3 * k] = mn; stats[3 * k + 1] = mx; stats[3 * k + 2] = gags_key2f(keys[3 * k + 2]); }
     if (p >= hw) return;
     float o = blended[(size_t)k * hw + p] - mn;
     o = o / ((mx - mn) + 1e-9f);
@@ -124,6 +159,20 @@ __global__ __launch_bounds__(256) void majority_kernel(int h, int w, int s, cons
 inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
+
+extern "C" int gags_relevancy(int64_t n_pix, int c, int n_pos, int n_neg, const float *embed, const float *pos,
+                              const float *neg, float *probs, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (n_pix < 0 || c <= 0 || n_pos <= 0 || n_neg <= 0 || n_pos + n_neg > REL_MAX_PHRASES || c > 1024 ||
+        (size_t)(n_pos + n_neg) * c * 4 > 60000 || !pos || !neg || (n_pix > 0 && (!embed || !probs)))
+        return GAGS_EINVAL;
+    if (n_pix == 0) return GAGS_OK;
+    hipLaunchKernelGGL(relevancy_kernel, dim3((unsigned)((n_pix + 3) / 4)), dim3(256), (size_t)(n_pos + n_neg) * c * 4,
+                       (hipStream_t)stream, n_pix, c, n_pos, n_neg, embed, pos, neg, probs);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}
 
 extern "C" int64_t gags_relevancy_activate_scratch_bytes(int n_phrases, int h, int w)
 {

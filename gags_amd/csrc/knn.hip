@@ -25,20 +25,13 @@
 #include <cmath>
 #include "launch.h"
 #include "gags_next.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int KNN_BOX = 256;       // sorted points per box = threads per query workgroup (gags_amd/knn.py: BOX)
 constexpr int KNN_SEED = 3;        // the best three start from sorted neighbours s - 3 .. s + 3
 constexpr int KNN_CELL_MAX = 1023;  // 10 bits per axis
-
-// float <-> unsigned key with the same order (as csrc/pointquery.hip)
-__device__ __forceinline__ unsigned f2key(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // bbox[0..2] = keys of the minima, bbox[3..5] = keys of the maxima
 __global__ void knn_bbox_init_kernel(unsigned *__restrict__ bbox)
@@ -52,10 +45,11 @@ __global__ __launch_bounds__(256) void knn_bbox_kernel(int64_t n, const float *_
     const int a = blockIdx.y;
     unsigned kmin = 0xffffffffu, kmax = 0u;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const unsigned u = f2key(xyz[i * 3 + a]);
+        const unsigned u = gags_f2key(xyz[i * 3 + a]);
         kmin = min(kmin, u);
         kmax = max(kmax, u);
     }
+    // (gags_block_minmax's tree, inline: with the two destinations formed at a call the compiler schedules this kernel differently)
     for (int off = 32; off > 0; off >>= 1) {
         kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, off, 64));
         kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, off, 64));
@@ -94,9 +88,9 @@ __global__ __launch_bounds__(256) void knn_key_kernel(int64_t n, const float *__
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const unsigned cx = knn_cell(xyz[i * 3 + 0], key2f(bbox[0]), key2f(bbox[3]));
-    const unsigned cy = knn_cell(xyz[i * 3 + 1], key2f(bbox[1]), key2f(bbox[4]));
-    const unsigned cz = knn_cell(xyz[i * 3 + 2], key2f(bbox[2]), key2f(bbox[5]));
+    const unsigned cx = knn_cell(xyz[i * 3 + 0], gags_key2f(bbox[0]), gags_key2f(bbox[3]));
+    const unsigned cy = knn_cell(xyz[i * 3 + 1], gags_key2f(bbox[1]), gags_key2f(bbox[4]));
+    const unsigned cz = knn_cell(xyz[i * 3 + 2], gags_key2f(bbox[2]), gags_key2f(bbox[5]));
     keys[i] = (knn_spread(cx) << 2) | (knn_spread(cy) << 1) | knn_spread(cz);
 }
 

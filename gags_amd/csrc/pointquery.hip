@@ -21,6 +21,7 @@
 #include <cmath>
 #include "launch.h"
 #include "gags_next.h"
+#include "reduce.h"
 
 namespace {
 
@@ -28,29 +29,6 @@ constexpr int CELL_BITS = 16;
 constexpr uint64_t CELL_MAX = (1u << CELL_BITS) - 1;
 constexpr int PHRASE_SHIFT = 3 * CELL_BITS;  // key = phrase << 48 | cx << 32 | cy << 16 | cz
 constexpr int MAX_MASKS = 65534;            // phrase field 16 bits, value n_masks = the sentinel
-
-// float <-> unsigned key with the same order (as csrc/activate.hip)
-__device__ __forceinline__ unsigned f2key(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__device__ __forceinline__ void block_minmax(unsigned kmin, unsigned kmax, unsigned *dst_min, unsigned *dst_max)
-{
-    __shared__ unsigned red[2][4];
-    for (int off = 32; off > 0; off >>= 1) {
-        kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, off, 64));
-        kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = kmin; red[1][threadIdx.x >> 6] = kmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMin(dst_min, min(min(red[0][0], red[0][1]), min(red[0][2], red[0][3])));
-        if (dst_max) atomicMax(dst_max, max(max(red[1][0], red[1][1]), max(red[1][2], red[1][3])));
-    }
-}
 
 __global__ void minmax_init_kernel(int n_keys, unsigned *__restrict__ keys)
 {
@@ -64,11 +42,11 @@ __global__ __launch_bounds__(256) void rel_minmax_kernel(int64_t n, const float 
     const int k = blockIdx.y;
     unsigned kmin = 0xffffffffu, kmax = 0u;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const unsigned u = f2key(probs[((int64_t)k * n + i) * 2]);
+        const unsigned u = gags_f2key(probs[((int64_t)k * n + i) * 2]);
         kmin = min(kmin, u);
         kmax = max(kmax, u);
     }
-    block_minmax(kmin, kmax, keys + 2 * k, keys + 2 * k + 1);
+    gags_block_minmax(kmin, kmax, keys + 2 * k, keys + 2 * k + 1);
 }
 
 // compute_relvancy.py:363-367, in the reference's order (max(fl(r_i - min)) == fl(max - min): fl(. - min) is monotone)
@@ -77,7 +55,7 @@ __global__ __launch_bounds__(256) void rel_normalise_kernel(int64_t n, float thr
                                                             unsigned char *__restrict__ mask)
 {
     const int k = blockIdx.y;
-    const float mn = key2f(keys[2 * k]), mx = key2f(keys[2 * k + 1]);
+    const float mn = gags_key2f(keys[2 * k]), mx = gags_key2f(keys[2 * k + 1]);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t o = (int64_t)k * n + i;
         float r = probs[o * 2] - mn;
@@ -100,8 +78,8 @@ __global__ __launch_bounds__(256) void bbox_kernel(int64_t n, const float *__res
     const int a = blockIdx.y;
     unsigned kmin = 0xffffffffu;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        kmin = min(kmin, f2key(xyz[i * 3 + a]));
-    block_minmax(kmin, 0u, bbox + a, nullptr);
+        kmin = min(kmin, gags_f2key(xyz[i * 3 + a]));
+    gags_block_minmax(kmin, 0u, bbox + a, nullptr);
 }
 
 __device__ __forceinline__ uint64_t cell_coord(float x, float lo, double cell)
@@ -117,9 +95,9 @@ __global__ __launch_bounds__(256) void cell_kernel(int64_t n, const float *__res
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint64_t cx = cell_coord(xyz[i * 3 + 0], key2f(bbox[0]), cell);
-    const uint64_t cy = cell_coord(xyz[i * 3 + 1], key2f(bbox[1]), cell);
-    const uint64_t cz = cell_coord(xyz[i * 3 + 2], key2f(bbox[2]), cell);
+    const uint64_t cx = cell_coord(xyz[i * 3 + 0], gags_key2f(bbox[0]), cell);
+    const uint64_t cy = cell_coord(xyz[i * 3 + 1], gags_key2f(bbox[1]), cell);
+    const uint64_t cz = cell_coord(xyz[i * 3 + 2], gags_key2f(bbox[2]), cell);
     pcell[i] = (cx << (2 * CELL_BITS)) | (cy << CELL_BITS) | cz;
 }
 

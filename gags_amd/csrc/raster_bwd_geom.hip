@@ -13,6 +13,7 @@
 #include <algorithm>
 #include "raster_mfma_common.h"
 #include "launch.h"
+#include "reduce.h"
 
 using namespace gags_mfma;
 
@@ -462,19 +463,6 @@ int gags_blended_mask_launch(int n_isects, const int32_t *hit, const int32_t *fl
     return GAGS_OK;
 }
 
-// wave64 sum on the VALU (DPP: quad swaps, row mirrors, row broadcasts; the total lands in lane 63), returned
-// wave-uniform -- __shfl_xor goes through the LDS crossbar, and six sums per slot made that the kernel's bound
-__device__ __forceinline__ float geom_wave_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 // (prototype: -Wmissing-prototypes)
 __global__ __launch_bounds__(64) void raster_bwd_geom(int, int, int, int, int, const GRec *, const int32_t *, int, const int32_t *,
                                                       const float *, const int32_t *, const int32_t *, const float *, const float *,
@@ -574,8 +562,8 @@ __global__ __launch_bounds__(64) void raster_bwd_geom(int width, int height, int
                 g5 = vis * v_alpha;
             }
         }
-        g0 = geom_wave_sum(g0); g1 = geom_wave_sum(g1); g2 = geom_wave_sum(g2);
-        g3 = geom_wave_sum(g3); g4 = geom_wave_sum(g4); g5 = geom_wave_sum(g5);
+        g0 = gags_wave_sum(g0); g1 = gags_wave_sum(g1); g2 = gags_wave_sum(g2);
+        g3 = gags_wave_sum(g3); g4 = gags_wave_sum(g4); g5 = gags_wave_sum(g5);
         if (lane < 8) {
             const float v = lane == 0 ? g0 : lane == 1 ? g1 : lane == 2 ? g2 : lane == 3 ? g3 : lane == 4 ? g4 : lane == 5 ? g5 : 0.f;
             grow[(size_t)row * 8 + lane] = v;

@@ -9,6 +9,7 @@
 // Feature rows are wave-uniform: they are fetched with scalar loads (SGPR operands of v_fmac),
 // not through LDS.  HBM/LDS-latency bound at these widths.
 #include "launch.h"
+#include "reduce.h"
 
 namespace {
 
@@ -106,34 +107,6 @@ __global__ __launch_bounds__(256) void raster_fwd_valu(
     }
 }
 
-// wave64 sum by DPP: quad swaps, half-row / row mirrors, then row broadcasts; total lands in
-// lane 63 and is returned wave-uniform (SGPR) through readlane.
-__device__ __forceinline__ float dpp_f(float v, int ctrl, int row_mask)
-{
-    int r;
-    switch (ctrl) {  // ctrl must be a literal for the builtin
-        case 0xB1: r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false); break;
-        case 0x4E: r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false); break;
-        case 0x141: r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false); break;
-        case 0x140: r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false); break;
-        case 0x142: r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false); break;
-        default: r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false); break;
-    }
-    (void)row_mask;
-    return __int_as_float(r);
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += dpp_f(v, 0xB1, 0xF);
-    v += dpp_f(v, 0x4E, 0xF);
-    v += dpp_f(v, 0x141, 0xF);
-    v += dpp_f(v, 0x140, 0xF);
-    v += dpp_f(v, 0x142, 0xA);
-    v += dpp_f(v, 0x143, 0xC);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 __device__ __forceinline__ void atomic_add_f32(float *p, float v)
 {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -220,7 +193,7 @@ __global__ __launch_bounds__(256) void raster_bwd_valu(
             float mine = 0.f;  // lane k ends up owning the wave total of channel k
 #pragma unroll
             for (int k = 0; k < CDIM; ++k) {
-                const float tot = wave_sum(fac * vc[k]);
+                const float tot = gags_wave_sum(fac * vc[k]);
                 mine = (lane == k) ? tot : mine;
                 if (GEOM) {
                     const float ck = c[k < nch ? k : 0];
@@ -247,8 +220,8 @@ __global__ __launch_bounds__(256) void raster_bwd_valu(
                         g5 = vis * v_alpha;
                     }
                 }
-                g0 = wave_sum(g0); g1 = wave_sum(g1); g2 = wave_sum(g2);
-                g3 = wave_sum(g3); g4 = wave_sum(g4); g5 = wave_sum(g5);
+                g0 = gags_wave_sum(g0); g1 = gags_wave_sum(g1); g2 = gags_wave_sum(g2);
+                g3 = gags_wave_sum(g3); g4 = gags_wave_sum(g4); g5 = gags_wave_sum(g5);
                 if (lane < 3) atomic_add_f32(v_conics + 3 * (size_t)g + lane, lane == 0 ? g0 : (lane == 1 ? g1 : g2));
                 else if (lane < 5) atomic_add_f32(v_means2d + 2 * (size_t)g + (lane - 3), lane == 3 ? g3 : g4);
                 else if (lane == 5) atomic_add_f32(v_opacities + g, g5);

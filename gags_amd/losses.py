@@ -1,5 +1,5 @@
 """The image-space losses and ground-truth assembly of the distillation step, same function
-names, arguments and results as the reference's, on HIP kernels (include/gags_next.h, csrc/losses.hip):
+names, arguments and results as the reference's, on HIP kernels (include/gags_next.h, csrc/seg_losses.hip, distill_l1.hip, head_distill.hip):
 
     utils/loss_utils.py:20-24     l1_loss, l1_loss_map
     utils/loss_utils.py:32-57     Scale_balance_loss(loss_map, seg_map, mask, mix_seg=True)
@@ -119,7 +119,7 @@ def _segment_copies(x, seg_map, n_seg, pixel_major=False):
     c = x.shape[1] if pixel_major else x.shape[0]
     lib = _lib.load()
     k = lib.gags_segment_stats_runs_copies(n_pix, c, n_seg, 1 if pixel_major else 0) if RUNS else 0
-    if k > 0:  # sums by runs of equal ids into one private table per workgroup: no global atomics (csrc/losses.hip)
+    if k > 0:  # sums by runs of equal ids into one private table per workgroup: no global atomics (csrc/seg_losses.hip)
         s1 = torch.empty(k, n_seg, c, dtype=torch.float64, device=x.device)
         s2 = torch.empty_like(s1)
         cnt = torch.empty(k, n_seg, dtype=torch.int32, device=x.device)
@@ -196,7 +196,7 @@ class _RegionVar(torch.autograd.Function):
         pm = x.is_cuda and x.dtype == torch.float32 and not x.is_contiguous() and x.permute(1, 2, 0).is_contiguous()
         x = x.permute(1, 2, 0) if pm else _f(x)
         n_seg = _n_seg(seg_map)
-        # unbiased variances (torch.var) from moments accumulated in double about a member of each group (csrc/losses.hip): the
+        # unbiased variances (torch.var) from moments accumulated in double about a member of each group (csrc/seg_losses.hip): the
         # subtraction is a double-precision one on accurately summed terms; segments of 0 or 1 pixels are skipped
         # (loss_utils.py:124-125); copies' sum, variances, loss and the backward's tables in two launches (gags_segment_loss)
         loss, coef, mean = _segment_loss(1, x.reshape(-1, c) if pm else x.reshape(c, -1), seg.reshape(-1), n_seg, pixel_major=pm)

@@ -44,7 +44,7 @@ int gags_segment_stats(int64_t n_pix, int c, const float *x, const float *seg, i
  * layout 1: x is pixel-major [n_pix, c] (the rasterizer's own memory under the [C,H,W] view: no `.contiguous()` copy). */
 int gags_segment_stats_multi(int64_t n_pix, int c, const float *x, const float *seg, int n_seg, int copies, double *s1,
                              double *s2, int32_t *cnt, int layout, void *stream);
-/* The same moments by runs of equal ids (round 6; csrc/losses.hip segment_stats_runs_kernel): no atomics in global memory, the
+/* The same moments by runs of equal ids (round 6; csrc/seg_losses.hip segment_stats_runs_kernel): no atomics in global memory, the
  * cost per pixel independent of how finely the map is cut.  Serves c == 16 pixel-major (layout 1) and c == 1 with
  * n_seg * (16 c + 4) <= 150 KB; gags_segment_stats_runs_copies returns the number of private copies s1 / s2 / cnt must hold
  * ([copies, n_seg, c], [copies, n_seg]; every element is written: no zero fill), or 0 when the shape is not served -- use

@@ -1,4 +1,4 @@
-"""The distillation step's loss kernels (csrc/losses.hip) against the float64 restatement of tests/loss_ref.py, at the
+"""The distillation step's loss kernels (csrc/seg_losses.hip, distill_l1.hip, head_distill.hip) against the float64 restatement of tests/loss_ref.py, at the
 shapes, channel counts and segment counts where the kernels take different paths.  tests/test_loss_ref_cpu.py ties the
 restatement to the reference's own outputs; here it is the yardstick for every kernel at sizes the fixture cannot reach.
 
@@ -506,3 +506,26 @@ def test_scale_regulation_loss_at_1080p_against_float64():
     # log: (1 + 2) U |log| + U, the quotient 2 U q, the sum U (|log| + q), the factor v / n rounded 1 and the product 1
     vb = vn * U * (4 * lg.abs() + 3 * q + 3) + 2 * U * want.abs()
     within(s.grad, want, vb, "entropy gradient")
+
+
+def test_entropy_gradient_with_a_host_cotangent_one_past_a_workgroup():
+    """gags_entropy_bwd (entropy_bwd_kernel: the factor v / n arrives as a host float; gags_amd.losses calls the device-scalar
+    form above) at n = 257, one element past a workgroup, with entries 0, 1 and near 1e-6: the gradient's bound of the test
+    above, and nothing written past the end."""
+    from gags_amd import _lib
+    g = gen(78)
+    n = 257
+    s0 = torch.softmax(3.0 * torch.randn(3, n, device=DEV, generator=g), 0)[0].contiguous()
+    s0[0], s0[1], s0[255], s0[256] = 0.0, 1.0, 1.5e-6, 1.0
+    v = 0.8125
+    vn = v / n
+    vs = torch.full((n + 1,), float("nan"), device=DEV)
+    assert _lib.load().gags_entropy_bwd(n, P(s0), vn, P(vs), stream()) == 0
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(vs[n])) and not bool(torch.isnan(vs[:n]).any())
+    sd = s0.double()
+    lg = torch.log(sd + R.EPS_LOG)
+    q = sd / (sd + R.EPS_LOG)
+    want = -(lg + q) * vn
+    vb = vn * U * (4 * lg.abs() + 3 * q + 3) + 2 * U * want.abs()
+    within(vs[:n], want, vb, "entropy gradient, host cotangent")
