@@ -5,6 +5,7 @@ Public surface (mirrors the reference's):
     gags_amd.rasterization.rasterization(means, quats, scales, opacities, colors, viewmats, Ks, ...)
     gags_amd.scene.GaussianModel / Camera
     gags_amd.distCUDA2(points)                   (simple_knn._C.distCUDA2; gags_amd/knn.py)
+    gags_amd.sam_masks.mask_nms / masks_update / assemble_seg_maps   (preprocess.py's mask post-processing)
 All device work goes through the C-ABI library gags_amd/csrc/libgags_hip.so
 (include/gags_raster.h); there is no CPU or PyTorch fallback -- a missing library raises.
 """

@@ -155,6 +155,15 @@ SIGNATURES = {
     # N9: scene initialisation from a point cloud (csrc/knn.hip)
     "gags_knn3_dist2_scratch_bytes": (_i64, [_i64]),
     "gags_knn3_dist2": (_i32, [_i64, _vp, _vp, _vp, _i64, _vp]),
+    # N10: SAM mask post-processing on bit-packed masks (csrc/sam_masks.hip)
+    "gags_masks_max_count": (_i32, []),
+    "gags_masks_pair_chunk_words": (_i32, []),
+    "gags_masks_pack": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp]),
+    "gags_masks_pairs": (_i32, [_i32, _i64, _vp, _vp, _vp]),
+    "gags_masks_colmax": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    "gags_masks_paint": (_i32, [_i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "gags_masks_nms_scratch_bytes": (_i64, [_i32, _i64]),
+    "gags_masks_nms_colmax": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

@@ -172,6 +172,24 @@ def load_language_features(prefix, render_hw=None, device="cpu"):
     return img_embed.to(device), seg_map.contiguous().to(device)
 
 
+def save_language_features(prefix, feature, seg_maps):
+    """The inverse of load_language_features: `<prefix>_f.npy` [n_seg, 512] and `<prefix>_s.npy` [4, h, w], both float32 --
+    the dtypes preprocess.py's sava_numpy ends up with (:332-336: both tensors are slices of float32 buffers).  Tensors
+    (any device) or arrays; ids up to 2^24 are exact as float32.  Returns the two paths."""
+    def a(t):
+        return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+    feature, seg_maps = a(feature), a(seg_maps)
+    if feature.ndim != 2 or seg_maps.ndim != 3:
+        raise ValueError(f"feature {feature.shape} must be [n_seg, D] and seg_maps {seg_maps.shape} [levels, h, w]")
+    if seg_maps.size and int(seg_maps.max()) >= feature.shape[0]:
+        raise ValueError(f"seg_maps name segment {int(seg_maps.max())}, feature holds {feature.shape[0]} rows")
+    os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+    np.save(prefix + "_s.npy", seg_maps.astype(np.float32))
+    np.save(prefix + "_f.npy", feature.astype(np.float32))
+    return prefix + "_f.npy", prefix + "_s.npy"
+
+
 def save_checkpoint(path, gaussians, iteration):
     """train.py:230-232: torch.save((gaussians.capture(), iteration), path)."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

@@ -441,6 +441,44 @@ int gags_reset_opacity(int64_t n, float *opacity, float *exp_avg, float *exp_avg
 int64_t gags_knn3_dist2_scratch_bytes(int64_t n);
 int gags_knn3_dist2(int64_t n, const float *xyz, float *dist2, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- N10: SAM mask post-processing of the GAS stage (preprocess.py:373-489 mask_nms / filter / masks_update / mask2segmap,
+ * :307-318 the level concatenation) on bit-packed masks (csrc/sam_masks.hip) ------------------------------------------------
+ * masks[M, n_pixels]: one byte per pixel of the flattened row-major image, nonzero = set (torch bool and uint8 alike).
+ * bits[M, nw] 64-bit words, nw = ceil(n_pixels / 64): pixel p is bit (p & 63) of word (p >> 6); the unused high bits of the
+ * last word are zero.  area[M] int32 = set pixels per mask.
+ *   inter[i, j] = sum_w popcount(bits[i, w] & bits[j, w])       int32, the full symmetric matrix; inter[i, i] = area[i]
+ * (integer atomics into the matrix the entry zeroes: exact, order-independent; no float atomic anywhere in N10).
+ * colmax[3, M] fp32 in mask_nms's arithmetic, over RANKS: order[M] lists the mask indices by descending score, a_i = area of
+ * rank i, I = inter of the two ranks; counts converted to fp32, IEEE fp32 division, 1 - a b unfused, 0.5f and 0.85f:
+ *   for i < j:  r_i = I / a_i,  r_j = I / a_j,  iou = I / (a_i + a_j - I)   (the union as an integer, then converted)
+ *               inner[i, j] = 1 - r_j r_i  when r_i < 0.5 and r_j >= 0.85      (upper entry)
+ *               inner[j, i] = 1 - r_j r_i  when r_i >= 0.85 and r_j < 0.5      (lower entry);  everything else 0
+ *   colmax[0][c] = max(0, max_{i < c} iou[i, c])
+ *   colmax[1][c] = max(0, max_{r < c} inner[r, c])
+ *   colmax[2][c] = max(0, max_{r >= c - 1} inner[r, c])   (the reference's torch.tril(., diagonal=1): the first superdiagonal
+ *                                                          belongs to the "lower" maximum too -- reproduced on purpose)
+ * A zero-area mask makes its quotients NaN or inf; a NaN never wins a maximum, nothing else happens (the Python layer
+ * refuses such a mask).  An entry of order or kept outside [0, M) is skipped.
+ * paint: seg[n_pixels] int32 = offset + the largest k whose mask kept[k] covers the pixel, -1 where none does ("later paint
+ * wins", mask2segmap); kept[n_kept] ascending mask indices, n_kept <= M, offset >= 0.  n_kept == 0: all -1.
+ * Requires 1 <= n_pixels < 2^24 (beyond it the reference's float sums are no longer exact integers: no bit-exact contract)
+ * and 0 <= M <= gags_masks_max_count() = 8192 (inter is M x M int32: 256 MiB at the cap, and i M + j stays far inside
+ * int32).  M == 0: nothing is launched, GAGS_OK.  Every pointer is a device pointer. */
+int gags_masks_max_count(void);
+/* words of one mask that one block of the pair kernel reduces; more words than this are split across blocks */
+int gags_masks_pair_chunk_words(void);
+int gags_masks_pack(int n_masks, int64_t n_pixels, const unsigned char *masks, void *bits, int32_t *area, void *stream);
+int gags_masks_pairs(int n_masks, int64_t n_pixels, const void *bits, int32_t *inter, void *stream);
+int gags_masks_colmax(int n_masks, const int32_t *inter, const int32_t *area, const int32_t *order, float *colmax,
+                      void *stream);
+int gags_masks_paint(int n_masks, int64_t n_pixels, const void *bits, int n_kept, const int32_t *kept, int offset,
+                     int32_t *seg, void *stream);
+/* pack + pairs + colmax in one call: area[M] and colmax[3, M] out; bits and inter live in scratch (the _scratch_bytes()
+ * bytes, 0 when M == 0) */
+int64_t gags_masks_nms_scratch_bytes(int n_masks, int64_t n_pixels);
+int gags_masks_nms_colmax(int n_masks, int64_t n_pixels, const unsigned char *masks, const int32_t *order, int32_t *area,
+                          float *colmax, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
