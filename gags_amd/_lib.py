@@ -91,6 +91,7 @@ SIGNATURES = {
     "gags_region_var_bwd": (_i32, [_i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "gags_gather_seg_coef": (_i32, [_i64, _vp, _i32, _vp, _vp, _vp]),
     "gags_sam_clip_feature": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_sam_clip_feature_max": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_sam_clip_feature_bwd_scale": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gags_distill_l1_map_fwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "gags_distill_l1_map_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
@@ -164,6 +165,14 @@ SIGNATURES = {
     "gags_masks_paint": (_i32, [_i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     "gags_masks_nms_scratch_bytes": (_i64, [_i32, _i64]),
     "gags_masks_nms_colmax": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # N11: PCA colouring of a feature map (csrc/featurevis.hip)
+    "gags_featvis_row_chunk": (_i32, []),
+    "gags_featvis_moments_scratch_bytes": (_i64, [_i32, _i64]),
+    "gags_featvis_moments": (_i32, [_i32, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "gags_featvis_project": (_i32, [_i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "gags_featvis_select_scratch_bytes": (_i64, [_i32]),
+    "gags_featvis_select": (_i32, [_i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "gags_featvis_colour": (_i32, [_i64, _vp, _f32, _f32, _vp, _vp, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

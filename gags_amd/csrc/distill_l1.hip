@@ -19,14 +19,19 @@ constexpr int CB = 64;       // channels per block
 constexpr int LDP = CB + 1;  // LDS row pitch (floats): conflict-free in both phases
 
 // F_l[ch] for 16 channels starting at c0 of one pixel, as torch computes it:
-// h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11); the products by the lambdas are folded into wgt[] here
+// h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11); the products by the lambdas are folded into wgt[] here.
+// REF_ORDER: the taps enter the fused chain in the order 10, 11, 01, 00 instead of 00, 01, 10, 11 -- the order of torch's CPU
+// upsample kernel for the channels-last tensor read_sam_clip_feature hands it, whose bits the max-mode fixture holds (of the 24
+// orders only this one reproduces them; tests/featurevis_ref.py).  The default order is what modes 0-3 have always computed.
+template <bool REF_ORDER = false>
 __device__ __forceinline__ void level_feature16(const Taps &t, int l, const float *__restrict__ img_embed, int c, int c0,
                                                 float (&f)[16])
 {
 #pragma unroll
     for (int j = 0; j < 16; ++j) f[j] = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int kk = 0; kk < 4; ++kk) {
+        const int k = REF_ORDER ? (kk < 2 ? 2 + kk : 3 - kk) : kk;
         if (t.wgt[k] == 0.f) continue;  // identity resize: a single tap
         const float4 *row = reinterpret_cast<const float4 *>(img_embed + (size_t)t.id[l][k] * c + c0);
 #pragma unroll
@@ -38,7 +43,8 @@ __device__ __forceinline__ void level_feature16(const Taps &t, int l, const floa
     }
 }
 
-// MODE 0: feature_map + mask; 1: v_scale from v_feature; 2: fused L1 map forward; 3: fused L1 map backward
+// MODE 0: feature_map + mask; 1: v_scale from v_feature; 2: fused L1 map forward; 3: fused L1 map backward;
+// 4: max mode (dataset_readers.py:81-88, what render.py asks for): the arg-max level's feature where THAT level is valid
 template <int MODE>
 __global__ __launch_bounds__(256) void sam_feature_kernel(int c, int H, int W, int h, int w, int n_emb,
                                                           const float *__restrict__ pred /* 2,3: pred; 1: v_feature */,
@@ -71,6 +77,17 @@ __global__ __launch_bounds__(256) void sam_feature_kernel(int c, int H, int W, i
     __syncthreads();
     const float maskB = red[0][pb][0];
     __syncthreads();
+    float lv[3] = {0.f, 0.f, 0.f};  // MODE 4: the levels' own validities, then sc[] = one_hot(argmax scale_map)
+    if (MODE == 4) {
+        if (qa == 0) { red[0][pa][1] = tp.lvl[0]; red[0][pa][2] = tp.lvl[1]; red[0][pa][3] = tp.lvl[2]; }
+        __syncthreads();
+#pragma unroll
+        for (int l = 0; l < 3; ++l) lv[l] = red[0][pb][1 + l];
+        int k = sc[1] > sc[0] ? 1 : 0;  // torch.argmax: the first of equal maxima
+        if (sc[2] > sc[k]) k = 2;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) sc[l] = l == k ? 1.f : 0.f;
+    }
     const float vB = (MODE == 3) ? v_map[pBc] * (1.0f / (float)c) : 0.f;
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;  // MODE 2: |diff| sum in acc0; MODE 1 / 3: v_scale partials
 
@@ -78,7 +95,7 @@ __global__ __launch_bounds__(256) void sam_feature_kernel(int c, int H, int W, i
         // this block's 16 values of the channel-major operand are requested FIRST, all at once, and arrive while the
         // embedding rows are gathered (inside the loop below they would be waited for four at a time)
         float pv[CB / 4];
-        if (MODE != 0) {
+        if (MODE != 0 && MODE != 4) {
 #pragma unroll
             for (int k = 0; k < CB / 4; ++k) pv[k] = pred[(size_t)min(cb + rb + 4 * k, c - 1) * HW + pBc];
             __builtin_amdgcn_sched_barrier(0);  // keep the requests up here (the scheduler would sink them to their uses)
@@ -87,7 +104,7 @@ __global__ __launch_bounds__(256) void sam_feature_kernel(int c, int H, int W, i
         for (int l = 0; l < 3; ++l) {
             float f[16];
             const int c0 = cb + qa * 16;
-            if (c0 < c) level_feature16(tp, l, img_embed, c, c0, f);
+            if (c0 < c) level_feature16<MODE == 4>(tp, l, img_embed, c, c0, f);
 #pragma unroll
             for (int j = 0; j < 16; ++j) F[l][pa][qa * 16 + j] = (c0 < c) ? f[j] : 0.f;
         }
@@ -101,6 +118,11 @@ __global__ __launch_bounds__(256) void sam_feature_kernel(int c, int H, int W, i
             if (MODE == 0) {
                 // feature_map_s * scale_map[0] + feature_map_m * scale_map[1] + feature_map_l * scale_map[2]
                 if (live) out0[o] = (f0 * sc[0] + f1 * sc[1]) + f2 * sc[2];
+            } else if (MODE == 4) {
+                // feature_map_s * one_hot[0] * mask_s + feature_map_m * one_hot[1] * mask_m + feature_map_l * one_hot[2] * mask_l
+                const float v = ((f0 * sc[0]) * lv[0] + (f1 * sc[1]) * lv[1]) + (f2 * sc[2]) * lv[2];
+                if (live) out0[o] = v;
+                if (live && ch == 0) out1[pB] = v != 0.f ? 1.f : 0.f;  // mask = feature_map[0:1] != 0: channel 0 alone
             } else if (MODE == 1) {
                 const float v = live ? pv[k] : 0.f;
                 acc0 = fmaf(v, f0, acc0); acc1 = fmaf(v, f1, acc1); acc2 = fmaf(v, f2, acc2);
@@ -123,6 +145,7 @@ __global__ __launch_bounds__(256) void sam_feature_kernel(int c, int H, int W, i
         if (rb == 0 && inB) out1[pB] = maskB;
         return;
     }
+    if (MODE == 4) return;
     red[rb][pb][0] = acc0; red[rb][pb][1] = acc1; red[rb][pb][2] = acc2;
     __syncthreads();
     if (rb == 0 && inB) {
@@ -244,6 +267,18 @@ extern "C" int gags_sam_clip_feature(int c, int H, int W, int h, int w, int n_em
     GAGS_CLEAR_ERR();
     if (!sam_args_ok(c, H, W, h, w, n_emb) || !img_embed || !seg_map || !scale_map || !feature_map || !mask) return GAGS_EINVAL;
     hipLaunchKernelGGL(sam_feature_kernel<0>, dim3((H * W + TP - 1) / TP), dim3(256), 0, (hipStream_t)stream, c, H, W, h, w,
+                       n_emb, (const float *)nullptr, img_embed, seg_map, scale_map, (const float *)nullptr, feature_map, mask);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}
+
+extern "C" int gags_sam_clip_feature_max(int c, int H, int W, int h, int w, int n_emb, const float *img_embed,
+                                         const float *seg_map, const float *scale_map, float *feature_map, float *mask,
+                                         void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (!sam_args_ok(c, H, W, h, w, n_emb) || !img_embed || !seg_map || !scale_map || !feature_map || !mask) return GAGS_EINVAL;
+    hipLaunchKernelGGL(sam_feature_kernel<4>, dim3((H * W + TP - 1) / TP), dim3(256), 0, (hipStream_t)stream, c, H, W, h, w,
                        n_emb, (const float *)nullptr, img_embed, seg_map, scale_map, (const float *)nullptr, feature_map, mask);
     GAGS_CHECK_LAUNCH();
     return GAGS_OK;

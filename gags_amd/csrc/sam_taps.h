@@ -8,6 +8,7 @@ struct Taps {
     int id[3][4];   // embedding row of (level, tap)
     float wgt[4];   // bilinear weights of the four taps (same for every level)
     float mask;     // 1 if all three levels have a segment at the nearest source pixel
+    float lvl[3];   // the same per level (max mode blanks a pixel by its arg-max level's own validity)
 };
 
 __device__ __forceinline__ Taps make_taps(int p, int H, int W, int h, int w, int n_emb, const float *__restrict__ seg_map)
@@ -34,7 +35,9 @@ __device__ __forceinline__ Taps make_taps(int p, int H, int W, int h, int w, int
             const int id = (int)lev[sp[k]];
             t.id[l][k] = id < 0 ? id + n_emb : id;  // img_embed[-1] is the LAST row in the reference (Python indexing)
         }
-        ok = ok && lev[ny * w + nx] != -1.0f;
+        const bool ok_l = lev[ny * w + nx] != -1.0f;
+        t.lvl[l] = ok_l ? 1.f : 0.f;
+        ok = ok && ok_l;
     }
     t.mask = ok ? 1.f : 0.f;
     return t;

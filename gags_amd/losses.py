@@ -291,9 +291,21 @@ class _SamFeature(torch.autograd.Function):
 
 
 def read_sam_clip_feature(img_embed, seg_map, scale_map, max_mode=False, median_mode=False, show_scale_map=False):
-    """(feature_map [C,H,W], mask [1,H,W] bool) as scene/dataset_readers.py:54-121 in its default mode."""
-    if max_mode or median_mode or show_scale_map:
-        raise NotImplementedError("read_sam_clip_feature: only the default mode (train.py:162,165) is implemented")
+    """(feature_map [C,H,W], mask [1,H,W] bool) as scene/dataset_readers.py:54-121 in its default mode, or with
+    max_mode=True (:81-88, render.py:64,154; forward only): the arg-max level's feature where that level has a segment,
+    and mask = feature_map[0:1] != 0."""
+    if median_mode or show_scale_map:
+        raise NotImplementedError("read_sam_clip_feature: only the default mode (train.py:162,165) and max_mode "
+                                  "(render.py:64,154) are implemented")
+    if max_mode:
+        with torch.no_grad():
+            e, seg, sc = _f(img_embed), _f(seg_map), _f(scale_map)
+            c, (_, h, w), (_, H, W) = e.shape[1], seg.shape, sc.shape
+            feat = torch.empty(c, H, W, device=e.device)
+            mask = torch.empty(H, W, device=e.device)
+            check(_lib.load().gags_sam_clip_feature_max(c, H, W, h, w, e.shape[0], ptr(e), ptr(seg), ptr(sc), ptr(feat),
+                                                        ptr(mask), _st()), "gags_sam_clip_feature_max")
+        return feat, (mask != 0)[None]
     feat, mask = _SamFeature.apply(img_embed, seg_map, scale_map)
     return feat, (mask != 0)[None]
 

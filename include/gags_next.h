@@ -84,6 +84,12 @@ int gags_sam_clip_feature(int c, int H, int W, int h, int w, int n_emb, const fl
                           const float *scale_map, float *feature_map, float *mask, void *stream);
 int gags_sam_clip_feature_bwd_scale(int c, int H, int W, int h, int w, int n_emb, const float *img_embed,
                                     const float *seg_map, const float *v_feature, float *v_scale, void *stream);
+/* The same function with max_mode=True (:81-88; what render.py:64,154 asks for), forward only: k = argmax_l scale_map[l]
+ * (the lowest index among equal maxima), one_hot = its indicator, valid_l = (level l's id at the nearest-resized source pixel
+ * != -1):  feature_map = (F_s one_hot[0]) valid_s + (F_m one_hot[1]) valid_m + (F_l one_hot[2]) valid_l  in the reference's
+ * order -- F_k where level k is valid, else 0 -- and mask[H, W] = feature_map[0] != 0 (channel 0 ALONE, as the reference), 0/1. */
+int gags_sam_clip_feature_max(int c, int H, int W, int h, int w, int n_emb, const float *img_embed, const float *seg_map,
+                              const float *scale_map, float *feature_map, float *mask, void *stream);
 
 /* train.py:165-166 fused: l1_map[H, W] = mean_c |pred * mask - gt * mask| with gt, mask = read_sam_clip_feature(...)
  * WITHOUT materialising the [c, H, W] ground truth (4.25 GB at 1080p x 512) or the two masked copies.
@@ -478,6 +484,30 @@ int gags_masks_paint(int n_masks, int64_t n_pixels, const void *bits, int n_kept
 int64_t gags_masks_nms_scratch_bytes(int n_masks, int64_t n_pixels);
 int gags_masks_nms_colmax(int n_masks, int64_t n_pixels, const unsigned char *masks, const int32_t *order, int32_t *area,
                           float *colmax, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---- N11: PCA colouring of a feature map (render.py:33-48 feature_visualize_saving; csrc/featurevis.hip) ------------------------
+ * x is a [c, H, W] fp32 map of n_pix = H W pixels: layout 0 = channel-major (element (ch, p) at x[ch n_pix + p]), layout 1 =
+ * pixel-major (x[p c + ch]: the memory behind the decoders' permuted view); neither is copied.  c % 16 == 0, 16 <= c <= 1024,
+ * 1 <= n_pix <= 2^26.  x^ = x / max(||x||_2, 1e-12) per pixel (F.normalize).  The sample is every third pixel: p % 3 == 0,
+ * S = ceil(n_pix / 3) of them.
+ *   moments:  sum[c] = sum x^, gram[c, c] = sum x^ x^T over the sample, both float64 (S >= 4).  Exact-f32 matrix instructions
+ *             on per-workgroup partial tiles (gags_featvis_row_chunk() sampled rows each), summed in float64 in a fixed order:
+ *             two runs give the same bits.
+ *   project:  t[p, k] = sum_ch (x^[ch] - mean[ch]) components[k, ch] for EVERY pixel, t [n_pix, 3]; mean [c], components [3, c].
+ *   select:   out[j] = the ranks[j]-th smallest (0-based) of n pooled floats, exactly (two 16-bit histogram passes over
+ *             order-preserving keys; -0.0 orders before +0.0).  Element i is values[(i / group) * stride + i % group]: group = 3,
+ *             stride = 9 pools t's sampled rows.  `ranks` is a HOST array of n_ranks <= 8 values in [0, n); n < 2^31.
+ *   colour:   vis[i] = clamp((t[i] - sub) / div, 0, 1) for n values; vis_u8 (optional) = trunc(255 vis[i]). */
+int gags_featvis_row_chunk(void);
+int64_t gags_featvis_moments_scratch_bytes(int c, int64_t n_pix);
+int gags_featvis_moments(int c, int64_t n_pix, const float *x, int layout, double *sum, double *gram, void *scratch,
+                         int64_t scratch_bytes, void *stream);
+int gags_featvis_project(int c, int64_t n_pix, const float *x, int layout, const float *mean, const float *components, float *t,
+                         void *stream);
+int64_t gags_featvis_select_scratch_bytes(int n_ranks);
+int gags_featvis_select(int64_t n, const float *values, int64_t group, int64_t stride, int n_ranks, const int64_t *ranks,
+                        float *out, void *scratch, int64_t scratch_bytes, void *stream);
+int gags_featvis_colour(int64_t n, const float *t, float sub, float div, float *vis, unsigned char *vis_u8, void *stream);
 
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
