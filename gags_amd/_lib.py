@@ -173,6 +173,12 @@ SIGNATURES = {
     "gags_featvis_select_scratch_bytes": (_i64, [_i32]),
     "gags_featvis_select": (_i32, [_i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "gags_featvis_colour": (_i32, [_i64, _vp, _f32, _f32, _vp, _vp, _vp]),
+    # N12: query images and loss maps (csrc/queryvis.hip)
+    "gags_query_images_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "gags_query_images": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _i64, _vp]),
+    "gags_query_colour": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_feature_loss_maps": (_i32, [_i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

@@ -4,6 +4,7 @@
 // [0, 1], threshold, and the 7x7 majority filter eval/utils.py:55-64 runs as a Python double loop over every pixel --
 // and the box mean + arg-max lerf_localization (:163-176) needs.  All phrases in one call, everything stays on the GPU.
 // Plain HBM / L2-bound image kernels: one thread per pixel, coalesced along x.
+#include "box_mean.h"
 #include "common.h"
 #include "gags_next.h"
 #include "reduce.h"
@@ -51,48 +52,18 @@ __global__ __launch_bounds__(256) void relevancy_kernel(int64_t n_pix, int c, in
     }
 }
 
-// cv2.BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), the default border of cv2.filter2D
-__device__ __forceinline__ int reflect101(int i, int n)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-    return i;
-}
-
-// horizontal pass: rowsum[k, y, x] = sum_{dx = -a .. box-1-a} src[k, y, reflect(x + dx)],  a = box / 2 (cv2's anchor).
-// Sums in double, rounded once at the end of the vertical pass: the reflected border makes neighbouring windows hold the
-// same multiset of pixels, and lerf_localization takes EVERY position that attains the maximum (:174-176) -- fp32 partial
-// sums in window order would break such exact ties.
-__global__ __launch_bounds__(256) void box_rows_kernel(int h, int w, int box, const float *__restrict__ src,
-                                                       double *__restrict__ rowsum)
-{
-    extern __shared__ float seg[];  // 256 + box values of the row
-    const int y = blockIdx.y, k = blockIdx.z, x0 = blockIdx.x * 256, a = box / 2;
-    const float *row = src + ((size_t)k * h + y) * w;
-    for (int i = threadIdx.x; i < 256 + box; i += 256) seg[i] = row[reflect101(x0 + i - a, w)];
-    __syncthreads();
-    const int x = x0 + threadIdx.x;
-    if (x >= w) return;
-    double s = 0.0;
-    for (int i = 0; i < box; ++i) s += (double)seg[threadIdx.x + i];
-    rowsum[((size_t)k * h + y) * w + x] = s;
-}
-
-// vertical pass + blend: avg = (sum over the column window) / box^2, blended = 0.5 (avg + src); min / max of the blended
+// vertical pass (box_mean.h) + blend: avg = (sum over the column window) / box^2, blended = 0.5 (avg + src); min / max of the blended
 // map and max of avg per phrase (keys[k] = {min blended, max blended, max avg})
 __global__ __launch_bounds__(256) void box_cols_kernel(int h, int w, int box, const float *__restrict__ src,
                                                        const double *__restrict__ rowsum, float *__restrict__ avg,
                                                        float *__restrict__ blended, unsigned *__restrict__ keys)
 {
     __shared__ unsigned red[3][4];
-    const int k = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x, a = box / 2;
+    const int k = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
     const bool in = x < w;
     float av = 0.f, bl = 0.f;
     if (in) {
-        const double *col = rowsum + (size_t)k * h * w + x;
-        double s = 0.0;
-        for (int i = 0; i < box; ++i) s += col[(size_t)reflect101(y + i - a, h) * w];
-        av = (float)(s / (double)(box * box));
+        av = box_col_mean(h, w, box, rowsum, k, y, x);
         const size_t o = ((size_t)k * h + y) * w + x;
         bl = 0.5f * (av + src[o]);
         avg[o] = av;

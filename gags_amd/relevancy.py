@@ -10,8 +10,8 @@ phrase and level through torch.mm + stack + softmax + gather).
 `activate_maps` / `localize` are the rest of the per-view query path, evaluate_iou_loc.py:100-146 (`activate_stream`:
 30x30 box mean -- cv2.filter2D on the host in the reference, one device->host->device round trip per phrase -- blend,
 min-max normalise, clip, threshold, eval/utils.py:55-64 majority filter, IoU) and :163-176 (`lerf_localization`: box
-mean, arg-max, hit test against the annotated boxes), for all phrases in one call on the GPU.  Saving heat maps /
-composited images to disk (colormaps, mediapy) is out of scope."""
+mean, arg-max, hit test against the annotated boxes), for all phrases in one call on the GPU.  The heat-map and
+composited images built from these tensors, and their PNG files, are gags_amd/queryvis.py (N12)."""
 import ctypes
 
 import torch

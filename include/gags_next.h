@@ -509,6 +509,47 @@ int gags_featvis_select(int64_t n, const float *values, int64_t group, int64_t s
                         float *out, void *scratch, int64_t scratch_bytes, void *stream);
 int gags_featvis_colour(int64_t n, const float *t, float sub, float div, float *vis, unsigned char *vis_u8, void *stream);
 
+/* ---- N12: query images and loss maps (compute_relvancy.py:100-144 activate_stream --image_mode, the same images at
+ * evaluate_iou_loc.py:108-163, 216-221; :439-447 compute_loss --loss_mode; csrc/queryvis.hip) --------------------------------------
+ * Query images.  n_maps = frames x phrases maps of h x w pixels; heat (`blended`), output, mask (`mask_smooth`) and stats are
+ * what gags_relevancy_activate wrote for them; image[n_frames, h, w, 3] fp32 in [0, 1], map m uses image m / (n_maps / n_frames);
+ * lut[256, 3] fp32.  All arithmetic is fp32, one IEEE operation per step, no fused multiply-add.  Per map m and pixel p:
+ *   idx(t)    = (int)(t * 255.0f) with a NaN t taken as 0, clamped to 0..255;  colour(t) = lut[idx(t)]   (eval/colormaps.py:105-113)
+ *   heatmap_rgb = colour(output)                                                                          (:113, colormaps.py:69-80)
+ *   lerf_rgb    = heat < 0.5f ? image * 0.3f : colour(q),   q = clip(p / (pmax + 1e-6f), 0, 1),           (:118-121)
+ *                 p = clip(heat - 0.5f, 0, 1),  pmax = clip(stats[m][1] - 0.5f, 0, 1)
+ *                 (stats[m][1] = max heat, and x -> clip(x - 0.5f, 0, 1) is monotone: pmax IS the reference's p.max(); no reduction)
+ *   avg2        = the box x box mean of output by gags_relevancy_activate's rule for avg (anchor box / 2, BORDER_REFLECT_101,
+ *                 sums in double, rounded once)                                                            (:136)
+ *   mask_rgb    = mask ? colour(b) : (image * 0.4f) + 0.1f,   b = clip(0.5f * output + 0.5f * avg2, 0, 1)  (:138-142)
+ *   *_u8 (optional: all three or none) = trunc(clamp(x * 255.0f + 0.5f, 0, 255)) of the float results: THIS project's 8-bit rule
+ *                 (gags_amd/featurevis.py _save_image), declared here; the reference writes its PNGs through mediapy.
+ * clip keeps a NaN (torch.clip), idx maps it to 0.  One thread per pixel, the LUT in LDS, grid (pixel blocks, n_maps): one launch
+ * for every phrase of every frame; no atomics, results are bit-reproducible.
+ * gags_query_colour: the colour kernel alone on a given avg2.  gags_query_images: the box mean of output into avg2[n_maps, h, w]
+ * (scratch: the _scratch_bytes() bytes), then the colour kernel.
+ * GAGS_EINVAL: a null pointer (the *_u8 excepted), a size <= 0, n_maps % n_frames != 0, box outside 1..1024, n_maps or h above
+ * 65535; GAGS_ESCRATCH: scratch too small.  n_maps == 0 is a no-op. */
+int64_t gags_query_images_scratch_bytes(int n_maps, int h, int w);
+int gags_query_images(int n_maps, int n_frames, int h, int w, const float *heat, const float *output, const unsigned char *mask,
+                      const float *stats, const float *image, const float *lut, int box, float *avg2, float *heatmap_rgb,
+                      float *lerf_rgb, float *mask_rgb, unsigned char *heatmap_u8, unsigned char *lerf_u8, unsigned char *mask_u8,
+                      void *scratch, int64_t scratch_bytes, void *stream);
+int gags_query_colour(int n_maps, int n_frames, int h, int w, const float *heat, const float *output, const unsigned char *mask,
+                      const float *avg2, const float *stats, const float *image, const float *lut, float *heatmap_rgb,
+                      float *lerf_rgb, float *mask_rgb, unsigned char *heatmap_u8, unsigned char *lerf_u8, unsigned char *mask_u8,
+                      void *stream);
+/* Loss maps of compute_loss (:440-447).  feature and gt are maps of c channels x n_pix pixels, each in its own layout (0 =
+ * channel-major x[ch n_pix + p], 1 = pixel-major x[p c + ch]); mask[n_pix] fp32 multiplies both.  Per pixel, with fl() one fp32
+ * operation:  a = fl(gt * m), b = fl(feature * m), d = fl(a - b),
+ *   l2 = sqrtf((float) sum_ch (double) fl(d * d)),  mean_abs_feature = (float)(sum_ch (double)|b| / c),  mean_abs_gt likewise of |a|.
+ * The sums are accumulated in double and rounded once.  Their order is fixed by the channel index alone -- channel ch belongs to
+ * run (ch % 64) / 16, every run is added in ascending channel order, and the four runs meet as (r0 + r1) + (r2 + r3) -- so any
+ * combination of layouts gives the same bits.  Every element of both maps is read once, along its map's fast axis.
+ * 1 <= c <= 65536, 0 <= n_pix <= 2^30 (0: a no-op). */
+int gags_feature_loss_maps(int c, int64_t n_pix, const float *feature, int feature_layout, const float *gt, int gt_layout,
+                           const float *mask, float *l2, float *mean_abs_feature, float *mean_abs_gt, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
