@@ -179,6 +179,9 @@ SIGNATURES = {
                                  _vp, _i64, _vp]),
     "gags_query_colour": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_feature_loss_maps": (_i32, [_i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # N13: crop statistics for SAM's depth-aware prompt grids (csrc/promptgrid.hip)
+    "gags_promptgrid_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "gags_promptgrid_stats": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

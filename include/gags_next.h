@@ -550,6 +550,34 @@ int gags_query_colour(int n_maps, int n_frames, int h, int w, const float *heat,
 int gags_feature_loss_maps(int c, int64_t n_pix, const float *feature, int feature_layout, const float *gt, int gt_layout,
                            const float *mask, float *l2, float *mean_abs_feature, float *mean_abs_gt, void *stream);
 
+/* ---- N13: crop statistics for SAM's depth-aware prompt grids (preprocess.py:114-149 build_depth_point_grid,
+ * utils/SAM_utils.py:294-353 sample_based_mapping / build_mindepth_point_grid; csrc/promptgrid.hip) --------------------------
+ * depths[C, h, w] fp32 (the rendered ED depth), samples[C, h, w] fp32 or NULL (N6's depth-sample maps), n = n_per_side.  Every
+ * image is cut into n x n crops, crop k = ix n + iy (x outer: the order of itertools.product(crop_x0, crop_y0)).  The geometry
+ * is integer and computed by the HOST in float64 exactly as numpy does (gags_amd/prompts.py crop_layout); the kernel never
+ * evaluates a linspace.  tab (DEVICE, int32 [2 n + 20]) = x0[n], y0[n], sx[10], sy[10]:
+ *   x0[i] = int32(linspace(0, w - 1, n + 1)[i]), crop_w = int(w / n); crop k covers columns [x0, min(x0 + crop_w, w)) and
+ *   rows [y0, min(y0 + crop_h, h)): its shape (hc, wc).  Crops leave gaps when w % n != 0: that is the reference's grid.
+ *   sx[j] = int32(linspace(0, wc - 1, 11)[j]), sy likewise of hc; sub-crop i (jx = i % 10, jy = i / 10) covers the crop's rows
+ *   [sy[jy], min(hc - 1, sy[jy] + hc / 10)) and columns [sx[jx], min(wc - 1, sx[jx] + wc / 10)).  Neighbouring windows may share
+ *   a pixel, a side under 10 gives empty windows, and the last row and column of a crop are in no window.
+ * Outputs per camera c and crop k, [C, n n]:
+ *   depth_sum float64 = sum of the crop's depths, depth_count int32 = hc wc;
+ *   with samples: sample_sum float64 / sample_count int32 over the crop's samples != 0 (a NaN or a negative sample is
+ *   non-zero, as for torch), sub_count[C, n n, 100] int32 = the non-zero samples in each sub-crop window.
+ * The sums are float64 sums of the fp32 values in a fixed order (per-lane partials, a shuffle tree, the waves in order, row
+ * slabs in ascending order; no floating-point atomics): equal inputs give equal bits.  The integer outputs are exact (the
+ * sub-crop counters are integer LDS atomics: order-independent).  The kernel clamps every
+ * start into the image and every window into its crop: no table can make it read outside the maps.
+ * Crops are split into row slabs when C n n workgroups would not fill the chip (partials in scratch, a finishing step in a
+ * fixed order).  scratch: the _scratch_bytes() bytes; 0 exactly when there is one slab and the workgroup writes the results.
+ * GAGS_EINVAL: a size < 1, h w >= 2^31, n > 4096, crop_w / crop_h outside 0 .. w / h, C n n > 2^23, a null pointer (samples and
+ * its three outputs excepted, together); GAGS_ESCRATCH: scratch too small. */
+int64_t gags_promptgrid_scratch_bytes(int n_cams, int h, int w, int n_per_side, int crop_h);
+int gags_promptgrid_stats(int n_cams, int h, int w, int n_per_side, int crop_w, int crop_h, const float *depths,
+                          const float *samples, const int32_t *tab, double *depth_sum, int32_t *depth_count, double *sample_sum,
+                          int32_t *sample_count, int32_t *sub_count, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
