@@ -19,37 +19,27 @@
 // i.e. a relative error <= ~2^-16 per product -- 32x tighter than the TF32 arithmetic (10-bit significands) torch runs the
 // reference's nn.Conv2d stacks in by default on the GPU its README names -- at half the matrix work and two thirds of the
 // split / LDS work of the exact tier.  fp32 tensors in memory, fp32 accumulation, the same deterministic reductions.
-#include "common.h"
-#include "gags_next.h"
+#include "decoder_common.h"
+#ifdef GAGS_H16
+#error "decoder_exact.hip splits fp32 into bfloat16 terms: it is compiled once, without -DGAGS_H16"
+#endif
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int XM = 128, XN = 128, XK = 32;  // workgroup tile: 128 x 128 outputs, 32 contraction elements per step
 constexpr int XLD = XK + 8;                 // LDS row pitch in bf16 (80 B: 16-byte aligned rows, banks spread)
 // (the kernels are templates over the number of bf16 terms per operand, NT in {3: exact, 2: bf16x2})
 
-// two floats -> packed bf16 pair, round to nearest even, in one instruction (v_cvt_pk_bf16_f32, new on gfx950)
-typedef __bf16 xbf16x2_t __attribute__((ext_vector_type(2)));
-typedef float xf32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned xpack(float lo, float hi)
-{
-    const xf32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, xbf16x2_t));
-}
-
 // (a, b) -> NT packed bf16 pairs t[s] = (term s of a) | (term s of b) << 16; NT = 3: x = h + m + l exactly; NT = 2: h + m
 template <int NT>
 __device__ __forceinline__ void split3x2(float a, float b, unsigned (&t)[NT])
 {
-    t[0] = xpack(a, b);
+    t[0] = h16_pack(a, b);
     float ra = a - __uint_as_float(t[0] << 16), rb = b - __uint_as_float(t[0] & 0xffff0000u);
-    t[1] = xpack(ra, rb);
+    t[1] = h16_pack(ra, rb);
     if constexpr (NT == 3) {
         ra -= __uint_as_float(t[1] << 16); rb -= __uint_as_float(t[1] & 0xffff0000u);
-        t[2] = xpack(ra, rb);
+        t[2] = h16_pack(ra, rb);
     }
 }
 
@@ -413,7 +403,7 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(int n_chunks, int64_t el
     out[e] = s;
 }
 
-// backward of the output heads in fp32 (see decoder.hip head_bwd_kernel): one wave per pixel
+// backward of the output heads in fp32 (see decoder_head.hip head_bwd_kernel): one wave per pixel
 //   mode 0 (y = x / max(||x||, eps)):  dz = (g - y <y, g>) / max(||x||, eps);   mode 1 (softmax):  dz = y (g - <y, g>)
 constexpr int HX_MAX = 16;  // values of a row per lane: C <= 1024
 __global__ __launch_bounds__(256) void head_bwd_exact_kernel(int64_t P, int C, int ldx, int mode, const float *__restrict__ x,

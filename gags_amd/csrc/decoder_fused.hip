@@ -2,7 +2,7 @@
 // convolutions of the forward -- and the nine input-gradient GEMMs of the backward -- run per 64-pixel tile with the
 // activations resident in LDS; only what the other direction needs crosses HBM (forward: each layer's output once, for the
 // ReLU masks and the weight gradients; backward: each layer's dz once, for the weight gradients).  Layer by layer
-// (csrc/decoder.hip) every GEMM read its input from HBM and wrote its output back: 15 launches, 12 of 30 ms per iteration.
+// (csrc/decoder_gemm.hip) every GEMM read its input from HBM and wrote its output back: 15 launches, 12 of 30 ms per iteration.
 //
 // Tile = 64 pixels, workgroup = 4 waves, two workgroups per CU.  A layer is  out^T[256 n x 64 p] = W[256 x K] act^T[K x 64]:
 // the MFMA A operand is the weight matrix (row n, 16-byte rows straight from global memory / L2: 128 KB per layer, shared by
@@ -12,19 +12,12 @@
 // Arithmetic is that of gags_decoder_layer (bf16 operands, fp32 accumulate in ascending k, bias + ReLU in fp32, one
 // rounding to bf16): the results are BIT-IDENTICAL to the layer-by-layer path (tests/test_decoders_gpu.py).
 #include <stdlib.h>
-#include "common.h"
-#include "half16.h"
-#include "gags_next.h"
+#include "decoder_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float ff32x2_t __attribute__((ext_vector_type(2)));
-using gags_h16::h16_mfma;
-__device__ __forceinline__ unsigned fpack(float lo, float hi) { return gags_h16::h16_pack_sat(lo, hi); }  // (both kernels set the mode)
-__device__ __forceinline__ float flo(unsigned u) { return gags_h16::h16_lo(u); }
-__device__ __forceinline__ float fhi(unsigned u) { return gags_h16::h16_hi(u); }
+// (pairs are packed with h16_pack_sat throughout: both kernels set the mode first, csrc/half16.h)
 
 #ifndef GAGS_ABL
 #define GAGS_ABL 0  // timing-only ablations of the fused kernels (tools/chain_bench.py; results are WRONG with any of them): 1 no HBM
@@ -39,16 +32,10 @@ typedef unsigned short (*Tile)[FLD];
 
 // the tiles' HBM stores are non-temporal (`nt`): 10.6 GB per 1080p forward that nothing reads before the kernel ends stream past
 // the L2 the weight fragments live in (round 6: -2 %; GAGS_ABL & 32 restores plain stores)
-typedef unsigned nt_u32x4 __attribute__((ext_vector_type(4)));
-typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void stream_store(uint4 *dst, uint4 v)
+template <class V>  // uint4 or float4
+__device__ __forceinline__ void stream_store(V *dst, V v)
 {
-    if (!(GAGS_ABL & 32)) __builtin_nontemporal_store(nt_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_u32x4 *>(dst));
-    else *dst = v;
-}
-__device__ __forceinline__ void stream_store(float4 *dst, float4 v)
-{
-    if (!(GAGS_ABL & 32)) __builtin_nontemporal_store(nt_f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_f32x4 *>(dst));
+    if (!(GAGS_ABL & 32)) nt_store(dst, v);
     else *dst = v;
 }
 
@@ -144,8 +131,8 @@ __device__ __forceinline__ void epilogue_hidden(const f32x16 (&acc)[2][2], const
             for (int j = 0; j < 2; ++j) {
                 const ff32x2_t a01 = {acc[i][j][4 * g], acc[i][j][4 * g + 1]}, a23 = {acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
                 const ff32x2_t v01 = a01 + b01, v23 = a23 + b23;
-                unsigned u0 = gags_h16::h16_pack_sat(v01[0], v01[1]);
-                unsigned u1 = gags_h16::h16_pack_sat(v23[0], v23[1]);
+                unsigned u0 = h16_pack_sat(v01[0], v01[1]);
+                unsigned u1 = h16_pack_sat(v23[0], v23[1]);
                 unsigned m0, m1;
                 asm("v_pk_max_i16 %0, %1, 0" : "=v"(u0) : "v"(u0));
                 asm("v_pk_max_i16 %0, %1, 0" : "=v"(u1) : "v"(u1));
@@ -189,6 +176,13 @@ __device__ __forceinline__ void store_tile(unsigned short *__restrict__ dst, int
     }
 }
 
+// the sum of eight packed values: added in fp32, rounded once (add_h16x2 with the mode's saturation)
+__device__ __forceinline__ uint4 add_sat_h16x8(uint4 x, uint4 y)
+{
+    return make_uint4(h16_pack_sat(h16_lo(x.x) + h16_lo(y.x), h16_hi(x.x) + h16_hi(y.x)), h16_pack_sat(h16_lo(x.y) + h16_lo(y.y), h16_hi(x.y) + h16_hi(y.y)),
+                      h16_pack_sat(h16_lo(x.z) + h16_lo(y.z), h16_hi(x.z) + h16_hi(y.z)), h16_pack_sat(h16_lo(x.w) + h16_lo(y.w), h16_hi(x.w) + h16_hi(y.w)));
+}
+
 // dst[p][:] = bf16(dst + add) element-wise (fp32 add, one rounding: what gags_decoder_layer does with two sources)
 // dst += add in LDS, and the sum's tile to its place in a pixel-major [P, 256] tensor: the residual sums x1 + x2 and
 // x3 + x4 are what layers 3 and 6 read AND what their weight gradients contract -- kept instead of x2 / x4 (whose ReLU
@@ -200,8 +194,7 @@ __device__ __forceinline__ void add_store_tile(Tile dst, Tile add, unsigned shor
     for (int q = 0; q < 8; ++q) {
         const int id = tid + NT * q, row = id >> 5, c = (id & 31) * 8;
         const uint4 x = *reinterpret_cast<const uint4 *>(&dst[row][c]), y = *reinterpret_cast<const uint4 *>(&add[row][c]);
-        const uint4 sum = make_uint4(fpack(flo(x.x) + flo(y.x), fhi(x.x) + fhi(y.x)), fpack(flo(x.y) + flo(y.y), fhi(x.y) + fhi(y.y)),
-                                     fpack(flo(x.z) + flo(y.z), fhi(x.z) + fhi(y.z)), fpack(flo(x.w) + flo(y.w), fhi(x.w) + fhi(y.w)));
+        const uint4 sum = add_sat_h16x8(x, y);
         *reinterpret_cast<uint4 *>(&dst[row][c]) = sum;
         if (keep && p0 + row < P && !(GAGS_ABL & (1 | 128))) stream_store(reinterpret_cast<uint4 *>(keep + (size_t)(p0 + row) * FH + c), sum);
     }
@@ -213,9 +206,7 @@ __device__ __forceinline__ void add_tile(Tile dst, Tile add, int tid)
     for (int q = 0; q < 8; ++q) {
         const int id = tid + NT * q, row = id >> 5, c = (id & 31) * 8;
         const uint4 x = *reinterpret_cast<const uint4 *>(&dst[row][c]), y = *reinterpret_cast<const uint4 *>(&add[row][c]);
-        *reinterpret_cast<uint4 *>(&dst[row][c]) =
-            make_uint4(fpack(flo(x.x) + flo(y.x), fhi(x.x) + fhi(y.x)), fpack(flo(x.y) + flo(y.y), fhi(x.y) + fhi(y.y)),
-                       fpack(flo(x.z) + flo(y.z), fhi(x.z) + fhi(y.z)), fpack(flo(x.w) + flo(y.w), fhi(x.w) + fhi(y.w)));
+        *reinterpret_cast<uint4 *>(&dst[row][c]) = add_sat_h16x8(x, y);
     }
 }
 
@@ -268,7 +259,7 @@ __global__ __launch_bounds__(256 * PH, 2 / PH) void decoder_fwd_fused_kernel(Fwd
             const int e = tid + NT * q, row = e >> 5, c = e & 31;
             const int64_t p = p0 + row;
             const float v = (p < a.P && c < a.c_in) ? xv[q] : 0.f;
-            const unsigned short hv = (unsigned short)(fpack(v, 0.f) & 0xffffu);
+            const unsigned short hv = (unsigned short)(h16_pack_sat(v, 0.f) & 0xffffu);
             bufB[row][c] = hv;
             if (a.act[0] && p < a.P) a.act[0][p * 32 + c] = hv;
         }
@@ -326,7 +317,7 @@ __global__ __launch_bounds__(256 * PH, 2 / PH) void decoder_fwd_fused_kernel(Fwd
     __syncthreads();
     store_tile<NT>(a.act[8], p0, a.P, bufB, tid);
     // L8: t7 (B) -> fp32 logits [P, n_last], 256 channels per pass.  Stored straight from the accumulators every
-    // instruction would scatter 32-byte pieces 4 n_last bytes apart and HBM sees partial lines (csrc/decoder.hip measured
+    // instruction would scatter 32-byte pieces 4 n_last bytes apart and HBM sees partial lines (csrc/decoder_gemm.hip measured
     // 2.4 x the bytes for that pattern); instead the two halves of a pass go through bufA (free by now: 64 pixels x 128
     // fp32 channels) and leave as whole 512-byte rows, 16 bytes per lane.
     float (*patch)[FLD / 2] = reinterpret_cast<float (*)[FLD / 2]>(&bufA[0][0]);  // [TP][132] floats, same 528-byte pitch
@@ -434,9 +425,9 @@ __device__ __forceinline__ void epilogue_dgrad(const f32x16 (&acc)[2][2], int n_
                 float v0 = acc[i][j][4 * g], v1 = acc[i][j][4 * g + 1], v2 = acc[i][j][4 * g + 2], v3 = acc[i][j][4 * g + 3];
                 if constexpr (ADD) {
                     const uint2 e = keep[i][g][j];
-                    v0 += flo(e.x); v1 += fhi(e.x); v2 += flo(e.y); v3 += fhi(e.y);
+                    v0 += h16_lo(e.x); v1 += h16_hi(e.x); v2 += h16_lo(e.y); v3 += h16_hi(e.y);
                 }
-                const unsigned u0 = fpack(v0, v1), u1 = fpack(v2, v3);
+                const unsigned u0 = h16_pack_sat(v0, v1), u1 = h16_pack_sat(v2, v3);
                 if constexpr (KEEP) keep[i][g][j] = make_uint2(u0, u1);
                 // the ReLU decisions applied to the PACKED pairs: the pair's two bits sit 16 apart in the word -> the halves'
                 // multipliers {0, 1} by one shift + one and -> v_pk_mul_lo_u16 (a bf16 times 1 or 0 as integers is itself or +0)
@@ -550,7 +541,7 @@ __global__ __launch_bounds__(256 * PH, 2 / PH) void decoder_bwd_fused_kernel(Bwd
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int ch = 8 * g + 4 * (lane >> 5) + e;
-                    if (ch < a.c_in) a.gin[pg * a.c_in + ch] = flo(fpack(c[4 * g + e], 0.f)) * gs;
+                    if (ch < a.c_in) a.gin[pg * a.c_in + ch] = h16_lo(h16_pack_sat(c[4 * g + e], 0.f)) * gs;
                 }
         }
     }

@@ -1,5 +1,5 @@
 // CNN_scale_decoder (models/networks.py:220-248: 16 -> 64 -> 128 -> 64 -> 32 -> 16 -> 3, ReLU between) as ONE kernel per
-// direction in the fast bf16 mode.  Layer by layer (csrc/decoder.hip) the six small GEMMs are bound by the HBM traffic of
+// direction in the fast bf16 mode.  Layer by layer (csrc/decoder_gemm.hip) the six small GEMMs are bound by the HBM traffic of
 // their activations (0.6 KB per pixel and direction): 1.05 ms forward, ~1.6 ms for the input-gradient chain at 1080p.
 // All its matrices together are 40 KB, so here a WAVE owns a tile of 32 pixels and walks the six layers alone: activations
 // ping-pong between two LDS buffers of its own (no workgroup barrier anywhere), weights arrive in MFMA-fragment order
@@ -10,15 +10,10 @@
 // rounding to bf16): BIT-IDENTICAL to the layer-by-layer chain (tests/test_decoders_gpu.py).
 // Padded widths (gags_amd/decoders.py: _pack_weights, every dimension to a multiple of 32):
 //   K = 32, 64, 128, 64, 32, 32   N = 64, 128, 64, 32, 32, 32   (real: 16 -> 64 -> 128 -> 64 -> 32 -> 16 -> 3)
-#include "common.h"
-#include "half16.h"
-#include "gags_next.h"
+#include "decoder_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-using gags_h16::h16_mfma;
 typedef float sf32x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int SP = 32;          // pixels per tile = per wave
@@ -82,9 +77,8 @@ __device__ __forceinline__ void stile_store(unsigned short *__restrict__ dst, in
     for (int q = 0; q < SP * C8 / 64; ++q) {
         const int id = lane + 64 * q, row = id / C8, c = (id - row * C8) * 8;
         if (p0 + row < P) {  // (streaming store: read next by a weight-gradient kernel, from HBM either way)
-            typedef unsigned nt_u4 __attribute__((ext_vector_type(4)));
             const uint4 v = *reinterpret_cast<const uint4 *>(&src[row][c]);
-            __builtin_nontemporal_store(nt_u4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_u4 *>(dst + (size_t)(p0 + row) * N + c));
+            nt_store(reinterpret_cast<uint4 *>(dst + (size_t)(p0 + row) * N + c), v);
         }
     }
 }
@@ -189,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void sdec_fwd_fused_kernel(SFwdArgs a)
             if (a.soft) {
                 // CNN_scale_decoder's head (models/networks.py:248, softmax over the 3 channels) on the accumulator itself: the
                 // three real logits of pixel p sit in lane p (h == 0), elements 0..2.  Same operations in the same order as
-                // head_small_kernel (csrc/decoder.hip) on the stored logits: the same bits, without writing 128 B per pixel
+                // head_small_kernel (csrc/decoder_head.hip) on the stored logits: the same bits, without writing 128 B per pixel
                 // of padded fp32 logits and reading them back (round 6)
                 if (h == 0 && p0 + p < a.P) {
                     const float e0 = acc[0][0] + bias_s[SBOFF[5]], e1 = acc[0][1] + bias_s[SBOFF[5] + 1], e2 = acc[0][2] + bias_s[SBOFF[5] + 2];

@@ -1,4 +1,5 @@
-// The 16-bit operand type of the decoder kernels (decoder.hip, decoder_fused.hip, decoder_scale.hip).  Each of those files is
+// The 16-bit operand type of the decoder kernels (decoder_gemm.hip, decoder_wgrad.hip, decoder_head.hip, decoder_pack.hip,
+// decoder_fused.hip, decoder_scale.hip; shared names: decoder_common.h).  Each of those files is
 // compiled TWICE from the same source:
 //   default        bfloat16: the "bf16" mode (8 significand bits; entry points gags_decoder_*, gags_scale_decoder_*)
 //   -DGAGS_H16     IEEE half: the "f16" tier (11 significand bits -- exactly the TF32 significand the reference's convolutions
@@ -72,6 +73,6 @@ __device__ __forceinline__ f32x16v h16_mfma(s16x8v a, s16x8v b, f32x16v c)
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 #endif
-__device__ __forceinline__ unsigned short h16_from(float f) { return (unsigned short)(h16_pack(f, 0.f) & 0xffffu); }
+__device__ __forceinline__ unsigned short h16_from(float f) { return (unsigned short)(h16_pack(f, 0.f) & 0xffffu); }  // (NaN stays NaN, round to nearest even)
 __device__ __forceinline__ float h16_to(unsigned short h) { return h16_lo((unsigned)h); }
 }  // namespace gags_h16

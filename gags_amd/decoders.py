@@ -1,7 +1,7 @@
 """The per-pixel decoders of the reference, same class names, constructor arguments, parameter
 names (`decoder.<i>.weight` / `.bias`: a reference state_dict loads unchanged) and outputs as
 models/networks.py:109-218 `CNN_decoder` and :220-248 `CNN_scale_decoder`, computed by hand-written bf16 matrix-core
-GEMM kernels (include/gags_next.h N1, csrc/decoder.hip) instead of cuDNN 1x1 convolutions.
+GEMM kernels (include/gags_next.h N1, csrc/decoder_*.hip) instead of cuDNN 1x1 convolutions.
 
     CNN_decoder(16, 512):       x [16,H,W] -> 9 x (1x1 conv, 256 hidden, ReLU), x3 = x1 + x2, x5 = x3 + x4 -> F.normalize(dim=0)
     CNN_scale_decoder(16, 3):   x [16,H,W] -> 16-64-128-64-32-16-3 (ReLU between) -> softmax(dim=0)
