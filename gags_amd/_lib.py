@@ -182,6 +182,10 @@ SIGNATURES = {
     # N13: crop statistics for SAM's depth-aware prompt grids (csrc/promptgrid.hip)
     "gags_promptgrid_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "gags_promptgrid_stats": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # N14: CLIP tiles from SAM masks (csrc/tilecut.hip)
+    "gags_tilecut_side": (_i32, []),
+    "gags_tilecut": (_i32, [_i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_tilecut_boxes": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

@@ -42,3 +42,15 @@ __device__ __forceinline__ void gags_block_minmax(unsigned kmin, unsigned kmax, 
         if (dst_max) atomicMax(dst_max, max(max(red[1][0], red[1][1]), max(red[1][2], red[1][3])));
     }
 }
+
+// wave64 min / max of an int over all lanes (a __shfl_xor butterfly: every lane holds the result)
+__device__ __forceinline__ int gags_wave_min(int v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ int gags_wave_max(int v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+    return v;
+}

@@ -578,6 +578,39 @@ int gags_promptgrid_stats(int n_cams, int h, int w, int n_per_side, int crop_w, 
                           const float *samples, const int32_t *tab, double *depth_sum, int32_t *depth_count, double *sample_sum,
                           int32_t *sample_count, int32_t *sub_count, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- N14: CLIP tiles from SAM masks (preprocess.py:356-371 get_seg_img / pad_img, :476-489 mask2segmap's tile cut with
+ * cv2.resize(..., (224, 224)), :487 the float conversion; csrc/tilecut.hip) ------------------------------------------------------
+ * image[H, W, 3] uint8, HWC as cv2.imread gives it.  bits[M, nw] exactly as gags_masks_pack writes them (N10): pixel
+ * p = r W + c is bit (p & 63) of word (p >> 6).  index[K] int32 names the mask of each tile (any order, repeats allowed);
+ * boxes[K, 4] int32 = (x, y, w, h), SAM's bbox.  bgr is 0 or 1.  All integer arithmetic below is exact.
+ * Crop.  The box is clipped as a numpy slice clips it: w' = min(x + w, W) - x, h' = min(y + h, H) - y.  A tile whose box has
+ *   x outside [0, W), y outside [0, H), w' < 1 or h' < 1, or whose index is outside [0, M), is written as all zeros (the Python
+ *   layer raises ValueError instead); the kernel never reads outside image or bits.
+ * Pad (pad_img, its `if h > w` / `else` exactly).  l = max(w', h'); ox = (l - w') / 2 when h' > w', else 0; oy = (l - h') / 2
+ *   when h' <= w', else 0 (floor).  The square S[v, u, c], i = v - oy, j = u - ox:
+ *     S[v, u, c] = image[y + i, x + j, c']  when 0 <= i < h', 0 <= j < w' and the mask's bit at pixel (y + i) W + x + j is set,
+ *     S[v, u, c] = 0 otherwise;  c' = 2 - c when bgr (the reference's COLOR_BGR2RGB at :465), else c' = c.
+ * Resize to 224 (8-bit INTER_LINEAR as OpenCV's generic path computes it; restated from memory, not pinned: DESIGN.md N14).
+ *   scale = l / 224 in float64.  For d in 0 .. 223: f = (float)((d + 0.5) scale - 0.5) (a float64 product, then a float64
+ *   subtraction, unfused); s = floor(f); f -= s (fp32); s < 0: s = 0, f = 0; s >= l - 1: s = l - 1, f = 0;
+ *   a0 = rint((1.0f - f) * 2048.0f), a1 = rint(f * 2048.0f) (nearest even); taps s and min(s + 1, l - 1).  One table for both
+ *   axes.  Horizontal: h = S0 a0 + S1 a1 (int).  Vertical: out = ((b0 (h0 >> 4) >> 16) + (b1 (h1 >> 4) >> 16) + 2) >> 2.
+ *   l = 224 is the identity and l = 448 the 2 x 2 mean (s00 + s01 + s10 + s11 + 2) >> 2 (where OpenCV switches to its area
+ *   path): the arithmetic above gives both.
+ * Outputs: tiles_u8[K, 224, 224, 3]; tiles_f32[K, 3, 224, 224] = (float)u8 / 255.0f by an IEEE division (torch's
+ *   x.float() / 255.0 on the host, where preprocess.py:487 divides, bit for bit; on a GPU tensor torch multiplies by the
+ *   rounded reciprocal instead).  Either may be NULL, not both.  Output offsets are 64-bit.
+ * gags_tilecut_boxes (named outside gags_masks_*, N10's closed set of eight entries): boxes[M, 4] int32 = (x0, y0, x1, y1), the
+ *   inclusive tight bounds of every mask's set pixels; an empty mask gives (0, 0, -1, -1).  Bits at or beyond pixel H W are
+ *   ignored.
+ * Limits are N10's: 1 <= H W < 2^24 and 0 <= K, M <= gags_masks_max_count(); a count of 0 launches nothing (gags_tilecut with
+ * K > 0 needs M >= 1).  GAGS_EINVAL otherwise, for bgr outside {0, 1} and for a null pointer, before any launch.  No atomics;
+ * every pointer is a device pointer. */
+int gags_tilecut_side(void);
+int gags_tilecut(int n_tiles, int height, int width, const unsigned char *image, int bgr, int n_masks, const void *bits,
+                 const int32_t *index, const int32_t *boxes, unsigned char *tiles_u8, float *tiles_f32, void *stream);
+int gags_tilecut_boxes(int n_masks, int height, int width, const void *bits, int32_t *boxes, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
