@@ -127,7 +127,7 @@ SIGNATURES = {
                                         "gags_decoder_head_bwd",
                                         "gags_decoder_unpack_grad", "gags_decoder_fwd_fused", "gags_decoder_bwd_fused", "gags_decoder_bwd_fused_scaled",
                                         "gags_scale_decoder_fwd_fused", "gags_scale_decoder_bwd_fused", "gags_scale_decoder_fwd_fused_head",
-                                        "gags_softmax_head_bwd_y")},
+                                        "gags_softmax_head_bwd_y", "gags_decoder_query_fused")},
     "gags_pow2_scale": (_i32, [_vp, _f32, _f32, _vp, _vp]),
     "gags_decoder_head_distill_bwd_h16": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_relevancy": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -186,6 +186,8 @@ SIGNATURES = {
     "gags_tilecut_side": (_i32, []),
     "gags_tilecut": (_i32, [_i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_tilecut_boxes": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
+    # N15: the query head, CNN_decoder + relevancy in one kernel (csrc/decoder_query.hip)
+    "gags_decoder_query_fused": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)

@@ -328,6 +328,24 @@ def _fusable(wb, c_in):
             and shapes[8][1] == 256 and shapes[8][0] % 256 == 0)
 
 
+QUERY_MAX_PHRASES = 32  # positives + negatives of one CNN_decoder.query call (gags_relevancy's cap, csrc/activate.hip)
+
+
+def _query_phrases(head, device):
+    """The phrase operand of gags_decoder_query_fused: [n_pos + n_neg, C] fp32, positives first.  Kept on the head and rebuilt
+    when either embedding tensor is another object (RelevancyHead.set_positives) or was written in place (its version
+    counter moved), the way _pack_weights follows the parameters.  (The direct head reads the phrases as they are: nothing
+    here depends on the decoder's weights.)"""
+    pos, neg = head.pos_embeds, head.neg_embeds
+    hit = getattr(head, "_gags_query_pack", None)
+    if (hit is not None and hit[0] is pos and hit[1] is neg and hit[2] == (pos._version, neg._version)
+            and hit[3].device == device):
+        return hit[3]
+    text = torch.cat([pos.detach().float(), neg.detach().float()]).to(device).contiguous()
+    head._gags_query_pack = (pos, neg, (pos._version, neg._version), text)
+    return text
+
+
 _SCALE_SHAPES = [(64, 32), (128, 64), (64, 128), (32, 64), (32, 32), (32, 32)]  # CNN_scale_decoder, padded to 32s
 
 
@@ -594,6 +612,57 @@ class CNN_decoder(_Stack):
         params = [t for m in self.convs() for t in (m.weight, m.bias)]
         l1, mask = _DecoderDistillFn.apply(x, img_embed, seg_map, scale_map, self.output_dim, self.precision, *params)
         return l1, (mask != 0)[None]
+
+    @torch.no_grad()
+    def query(self, x, head, pairs=False):
+        """The open-vocabulary query of one view (evaluate_iou_loc.py:258-288, compute_relvancy.py:243-269) in one call --
+        defined as
+            head.get_max_across(self(x).permute(1, 2, 0)[None])[0]          -> [n_pos, H, W] positive probabilities
+        or, with pairs=True, head._all(self(x).permute(1, 2, 0).reshape(H * W, -1)) -> [n_pos, H * W, 2] (both entries of the
+        winning softmax pair, what get_relevancy returns per phrase).  x: [C_in, H, W] on the GPU; a permuted view of
+        pixel-major [H, W, C_in] memory (the rasterizer's output; `f.t()[..., None]` of a per-Gaussian [N, C_in] table) is read
+        without a copy.  head: a gags_amd.relevancy.RelevancyHead whose embeddings are `output_dim` wide.  Runs under no_grad.
+
+        In the 16-bit tiers ("bf16", "f16"), for the reference's decoder shape (c_in <= 32, output_dim a multiple of 256) this
+        is ONE kernel (csrc/decoder_query.hip, N15): the nine layers per 64-pixel tile in LDS with the bits of the training
+        forward, the normalisation and the relevancy of every phrase inside the tile; no activation, logits or normalised map
+        is written -- the result is the only allocation.  It equals the composition up to fp32 summation order in the head
+        (tests/test_decoder_query_gpu.py: within 4x the composition's own error against float64).  In every other case -- the
+        "exact" and "bf16x2" tiers, other shapes, decoders.FUSED = False -- it runs exactly the composition above, and the
+        result is bit-identical to what those two calls return.
+
+        Raises ValueError when the head's width is not output_dim, when it has no positive or no negative phrase or more than
+        32 phrases in all (gags_relevancy's cap: the composition would fail the same way), RuntimeError on CPU tensors.  (The
+        composition has a second limit the kernel does not: gags_relevancy holds its phrases in 60000 bytes of LDS, so 32
+        phrases 512 wide run fused and raise in the tiers that compose.)"""
+        pos, neg = head.pos_embeds, head.neg_embeds
+        if pos.dim() != 2 or neg.dim() != 2 or pos.shape[0] == 0 or neg.shape[0] == 0:
+            raise ValueError(f"CNN_decoder.query: the head needs at least one positive and one negative phrase, got "
+                             f"{tuple(pos.shape)} and {tuple(neg.shape)}")
+        if pos.shape[1] != self.output_dim or neg.shape[1] != self.output_dim:
+            raise ValueError(f"CNN_decoder.query: phrase embeddings are {pos.shape[1]} / {neg.shape[1]} wide, the decoder's "
+                             f"output {self.output_dim}")
+        if pos.shape[0] + neg.shape[0] > QUERY_MAX_PHRASES:
+            raise ValueError(f"CNN_decoder.query: {pos.shape[0]} + {neg.shape[0]} phrases, at most {QUERY_MAX_PHRASES} per call")
+        if x.dim() != 3:
+            raise ValueError(f"CNN_decoder.query: x must be [C_in, H, W], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError("gags_amd.decoders: tensors must live on the GPU (there is no CPU path)")
+        tier = _tier(self.precision)
+        if tier.fused and FUSED and self.output_dim % 256 == 0:
+            wb = tier.weights([t for m in self.convs() for t in (m.weight, m.bias)])
+            xp, h, w = _pixel_major(x)
+            if _fusable(wb, xp.shape[1]) and wb[-1][0].shape[0] == self.output_dim:
+                text = _query_phrases(head, xp.device)
+                arr = ctypes.c_void_p * 9
+                probs = torch.empty(pos.shape[0], h * w, 2, device=xp.device)
+                check(tier.fn("gags_decoder_query_fused")(h * w, xp.shape[1], self.output_dim, ptr(xp),
+                                                          arr(*[_frag_layout(wgt).data_ptr() for wgt, _ in wb]),
+                                                          arr(*[b.data_ptr() for _, b in wb]), ptr(text), pos.shape[0], neg.shape[0],
+                                                          ptr(probs), _st()), "gags_decoder_query_fused")
+                return probs if pairs else probs[..., 0].reshape(-1, h, w).contiguous()
+        feat = self(x).permute(1, 2, 0)
+        return head._all(feat.reshape(-1, feat.shape[-1])) if pairs else head.get_max_across(feat[None])[0]
 
 
 class CNN_scale_decoder(_Stack):

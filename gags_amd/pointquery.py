@@ -63,8 +63,9 @@ def smooth_point_mask(mask, xyz, radius=0.1, threshold=10, return_counts=False):
     return (out, counts.reshape(mask.shape)) if return_counts else out
 
 
-def _point_probs(semantic_feature, decoder, head, chunk):
-    """[n_pos, N, 2] relevancy pairs of the decoded features, `chunk` Gaussians per decoder call."""
+def _point_probs(semantic_feature, decoder, head, chunk, fused=False):
+    """[n_pos, N, 2] relevancy pairs of the decoded features, `chunk` Gaussians per decoder call; fused=True: all N in one
+    CNN_decoder.query call (nothing per layer is held, so nothing is chunked)."""
     _on_gpu(semantic_feature)
     if semantic_feature.dim() != 2:
         raise ValueError(f"semantic_feature must be [N, C], got {tuple(semantic_feature.shape)}")
@@ -72,6 +73,8 @@ def _point_probs(semantic_feature, decoder, head, chunk):
         raise ValueError("chunk must be positive")
     f = semantic_feature.float()  # (the fp16 tables of precision="f16" training: exact upcast)
     n = f.shape[0]
+    if fused:  # [C, N, 1] over the table's own pixel-major memory: read in place
+        return decoder.query(f.t()[..., None], head, pairs=True)
     probs = torch.empty(head.pos_embeds.shape[0], n, 2, device=f.device)
     with torch.no_grad():
         for s in range(0, n, chunk):
@@ -87,22 +90,26 @@ def _point_probs(semantic_feature, decoder, head, chunk):
     return probs
 
 
-def point_relevancy(semantic_feature, decoder, head, chunk=1_000_000):
+def point_relevancy(semantic_feature, decoder, head, chunk=1_000_000, fused=False):
     """compute_relvancy.py:333-361: for every positive phrase j of `head`, get_relevancy(decoder(f)[N, 512], j)[:, 0]
     -> [n_pos, N].  semantic_feature [N, 16] on the GPU (fp32 or fp16); decoded under no_grad, `chunk` Gaussians at a
-    time (the decoder holds every layer's activations of a call)."""
-    return _point_probs(semantic_feature, decoder, head, chunk)[..., 0].contiguous()
+    time (the decoder holds every layer's activations of a call).  fused=True: one CNN_decoder.query call over all N
+    (N15: decoder and relevancy in one kernel in the 16-bit tiers, no chunking; equal up to the head's fp32 summation
+    order); the default is the path every earlier result came from."""
+    return _point_probs(semantic_feature, decoder, head, chunk, fused)[..., 0].contiguous()
 
 
 @torch.no_grad()
-def query_points(semantic_feature, xyz, decoder, head, rel_thresh=0.4, radius=0.05, threshold=20, chunk=1_000_000):
+def query_points(semantic_feature, xyz, decoder, head, rel_thresh=0.4, radius=0.05, threshold=20, chunk=1_000_000,
+                 fused=False):
     """pcd_relvancy (compute_relvancy.py:273-394, its constants as defaults) for all positive phrases of `head` in one call.
     Returns a dict of [n_pos, N] device tensors: relevancy (fp32), normalized (clip((r - min) / (max - min + 1e-9) * 2 - 1,
-    0, 1)), mask_raw (normalized > rel_thresh) and mask (after smooth_pcd_mask(mask_raw, xyz, radius, threshold))."""
+    0, 1)), mask_raw (normalized > rel_thresh) and mask (after smooth_pcd_mask(mask_raw, xyz, radius, threshold)).  fused: as
+    point_relevancy's."""
     _on_gpu(semantic_feature, xyz)
     if xyz.shape != (semantic_feature.shape[0], 3):
         raise ValueError(f"xyz must be [N, 3] with N = {semantic_feature.shape[0]}, got {tuple(xyz.shape)}")
-    probs = _point_probs(semantic_feature, decoder, head, chunk)
+    probs = _point_probs(semantic_feature, decoder, head, chunk, fused)
     k, n = probs.shape[0], probs.shape[1]
     normalized = torch.empty(k, n, device=probs.device)
     mask_raw = torch.empty(k, n, dtype=torch.uint8, device=probs.device)
@@ -161,10 +168,10 @@ def _write_ply_table(path, data):
 
 @torch.no_grad()
 def query_ply(path, decoder, head, prompts=None, rel_thresh=0.4, radius=0.05, threshold=20, bg_color="mix",
-              chunk=1_000_000, save_dir=None, device="cuda"):
+              chunk=1_000_000, save_dir=None, device="cuda", fused=False):
     """pcd_relvancy from point_cloud.ply: reads x y z, semantic_* and f_dc_*, runs query_points, and with `save_dir` writes
     <name>_<prompt>.ply per phrase (`prompts`: one name per positive phrase of `head`) with only f_dc_0..2 changed
-    (recolor_dc).  Returns query_points' dict, plus "paths" when files were written."""
+    (recolor_dc).  Returns query_points' dict, plus "paths" when files were written.  fused: as point_relevancy's."""
     names, table = read_ply_table(path)
     sem_cols = sorted([nm for nm in names if nm.startswith("semantic_")], key=lambda s: int(s.split("_")[-1]))
     if not sem_cols:
@@ -172,7 +179,7 @@ def query_ply(path, decoder, head, prompts=None, rel_thresh=0.4, radius=0.05, th
     col = lambda nm: np.asarray(table[nm], np.float32)  # noqa: E731
     xyz = torch.from_numpy(np.stack([col("x"), col("y"), col("z")], axis=1)).to(device)
     feat = torch.from_numpy(np.stack([col(nm) for nm in sem_cols], axis=1)).to(device)
-    res = query_points(feat, xyz, decoder, head, rel_thresh, radius, threshold, chunk)
+    res = query_points(feat, xyz, decoder, head, rel_thresh, radius, threshold, chunk, fused)
     if save_dir is not None:
         k = res["mask"].shape[0]
         if prompts is None or len(prompts) != k:

@@ -611,6 +611,22 @@ int gags_tilecut(int n_tiles, int height, int width, const unsigned char *image,
                  const int32_t *index, const int32_t *boxes, unsigned char *tiles_u8, float *tiles_f32, void *stream);
 int gags_tilecut_boxes(int n_masks, int height, int width, const void *bits, int32_t *boxes, void *stream);
 
+/* ---- N15: the query head -- phrase relevancy straight from the rasterized features (evaluate_iou_loc.py:258-288,
+ * compute_relvancy.py:243-269, 333-361; csrc/decoder_query.hip) ---------------------------------------------------------------
+ * One forward-only kernel:  x[n_pix, c_in] fp32 (pixel-major, the rasterizer's layout) -> CNN_decoder's nine layers per
+ * 64-pixel tile in LDS, arithmetic and bits of gags_decoder_fwd_fused (same operands: w_bf16[9] in MFMA-fragment order, bias[9]
+ * padded fp32) -> fp32 logits z[n_last] per pixel, which never leave the chip ->
+ *     sim_j = z . t_j / max(||z||, 1e-12)     for the n_pos + n_neg rows t_j of phrases[n_pos + n_neg, n_last] (fp32, positives
+ *                                             first, 16-byte aligned; unit rows, as OpenCLIPNetwork holds them)
+ *     probs[j, pixel, 0..1] = softmax(10 (sim_j, sim_(n_pos + k)))  of the negative k with the smallest first component (the
+ *                                             first such k), for every positive j:  gags_relevancy's output, probs[n_pos, n_pix, 2].
+ * Equal to gags_decoder_fwd_fused -> gags_decoder_head (normalize) -> gags_relevancy up to fp32 summation order; nothing but
+ * probs is written.  n_pix == 0 launches nothing.  GAGS_EINVAL: n_pix < 0, c_in outside 1 .. 32, n_last <= 0 or not a multiple
+ * of 256, n_pos <= 0, n_neg <= 0, n_pos + n_neg > 32 (gags_relevancy's cap), a null pointer (x and probs may be null when
+ * n_pix == 0), misaligned phrases / probs. */
+int gags_decoder_query_fused(int64_t n_pix, int c_in, int n_last, const float *x, const void *const *w_bf16,
+                             const float *const *bias, const float *phrases, int n_pos, int n_neg, float *probs, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
@@ -643,6 +659,7 @@ int gags_decoder_head_distill_bwd_h16(int c, int ld, int H, int W, int h, int w,
 int gags_scale_decoder_fwd_fused_h16(int64_t n_pix, int c_in, const float *x, const void *const *w_bf16, const float *const *bias, void *const *acts_bf16, void *masks, float *logits, void *stream);
 int gags_scale_decoder_fwd_fused_head_h16(int64_t n_pix, int c_in, const float *x, const void *const *w_bf16, const float *const *bias, void *const *acts_bf16, void *masks, float *logits, float *softmax3, void *stream);
 int gags_softmax_head_bwd_y_h16(int64_t n_pix, int c, int ld, const float *y, const float *g, void *dz_bf16, void *stream);
+int gags_decoder_query_fused_h16(int64_t n_pix, int c_in, int n_last, const float *x, const void *const *w_bf16, const float *const *bias, const float *phrases, int n_pos, int n_neg, float *probs, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
