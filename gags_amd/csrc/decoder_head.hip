@@ -147,6 +147,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int64_t P, int C, int ld,
 {
     __shared__ float tile[64][65];
     __shared__ float stat[64][3];
+    __shared__ float dotp[4][64];  // <y, g> of a pixel's four channel groups: summed in group order below (no atomics)
     const int64_t p0 = (int64_t)blockIdx.x * 64;
     const int tid = threadIdx.x;
     // pass 1a: norm / (max, Z) per pixel from the logits
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int64_t P, int C, int ld,
         const int px = tid >> 2, q = tid & 3;
         float s0, s1;
         head_strided_stats(x, min(p0 + px, P - 1), C, ld, q, mode, s0, s1);
-        if (q == 0) { stat[px][0] = s0; stat[px][1] = s1; stat[px][2] = 0.f; }
+        if (q == 0) { stat[px][0] = s0; stat[px][1] = s1; }
     }
     __syncthreads();
     // pass 1b: <y, g> per pixel (G is channel-major: transpose block-wise through LDS)
@@ -176,7 +177,11 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int64_t P, int C, int ld,
         }
         __syncthreads();
     }
-    atomicAdd(&stat[tid & 63][2], part);  // (the order in which a pixel's four partial sums are added is NOT fixed)
+    // (an LDS atomic add per thread here left the order of a pixel's four partial sums to the hardware: the gradient of a head
+    // wider than 512 channels, and every gradient behind it, changed in the last bit from run to run)
+    dotp[tid >> 6][tid & 63] = part;
+    __syncthreads();
+    if (tid < 64) stat[tid][2] = ((dotp[0][tid] + dotp[1][tid]) + dotp[2][tid]) + dotp[3][tid];
     __syncthreads();
     // pass 2: dz, pixel-major
     for (int cb = 0; cb < ld; cb += 64) {

@@ -1,6 +1,8 @@
 """N15 on the GPU: CNN_decoder.query -- decoder + relevancy head in one kernel (csrc/decoder_query.hip) -- against the float64
 head applied to the fp32 logits gags_decoder_fwd_fused writes for the same inputs and tier.  That truth isolates the new code:
 the hidden layers are the training forward's (csrc/decoder_tile.h), so any deviation there shows up as error in the head.
+That forward is itself checked at these c_in and widths: bit for bit against the layer-by-layer chain
+(tests/test_decoders_gpu.py), whose layer kernel is held to float64 per element (tests/test_decoder_layer_gpu.py).
 
 The bound.  Measured on an MI355X against that truth over the cases below (docs/LAB_NOTES.md "Query head (N15)"): the existing
 composition decoder(x) -> get_max_across is within COMPOSITION_ERR = 6.3e-7 of it (worst case, both tiers: 6.286e-7 at

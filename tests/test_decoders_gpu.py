@@ -266,6 +266,30 @@ def test_head_kernels_against_torch(c, ld, layout, mode):
     assert torch.count_nonzero(dz[:, c:]).item() == 0
 
 
+@pytest.mark.parametrize("sfx,dtype", [pytest.param("", torch.bfloat16, id="bf16"), pytest.param("_h16", torch.float16, id="f16")])
+@pytest.mark.parametrize("c,ld,mode", [(768, 768, 0), (520, 544, 0), (100, 128, 1)])
+def test_general_head_backward_is_bit_reproducible(c, ld, mode, sfx, dtype):
+    """The general head backward (rows wider than 512 channels, or not a multiple of 32) sums a pixel's four partial <y, g> in a
+    fixed order: three calls give the same bits.  (It added them with an LDS atomic, in whatever order the hardware served: a
+    768-wide CNN_decoder's logits gradient, and every gradient behind it, changed in the last bit from run to run -- found by
+    the 1 x 768 case of the fused / layer-by-layer test below, which compares two backward passes.)"""
+    from gags_amd import _lib
+    from gags_amd.decoders import _st
+    from gags_amd._lib import check, ptr
+    fn = getattr(_lib.load(), "gags_decoder_head_bwd" + sfx)
+    p = 20000 + 11
+    g = torch.Generator(device="cuda").manual_seed(c + mode)
+    x = torch.zeros(p, ld, device="cuda")
+    x[:, :c] = torch.randn(p, c, device="cuda", generator=g) * 2
+    G = torch.randn(c, p, device="cuda", generator=g)
+    runs = []
+    for _ in range(3):
+        dz = torch.full((p, ld), 7.0, device="cuda", dtype=dtype)
+        check(fn(p, c, ld, mode, ptr(x), ptr(G), ptr(dz), 0, _st()), "head_bwd")
+        runs.append(dz.view(torch.int16))
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
+
+
 @pytest.mark.parametrize("n,k,two", [(256, 256, False), (256, 256, True), (512, 256, False), (128, 256, True),
                                      (256, 32, False), (64, 128, True), (32, 64, False), (128, 64, False), (64, 32, True),
                                      (32, 32, False), (48, 32, False), (512, 64, False)])
@@ -416,21 +440,40 @@ def test_exact_head_backward_against_float64(c, ldx, layout, mode):
     assert ((dz.double() - xr.grad).norm() / xr.grad.norm()).item() <= 2e-6
 
 
-@pytest.mark.parametrize("precision", ["bf16", "f16"])
-def test_fused_decoder_kernels_are_bit_identical_to_the_layer_by_layer_chain(precision):
+def _fused_cases(shapes):
+    """Both 16-bit tiers x the shapes; the first shape (the golden-weight case) keeps the tier's name alone as its id."""
+    return [pytest.param(precision, *sh, id=precision if i == 0 else precision + "-" + "x".join(str(v) for v in sh))
+            for precision in ("bf16", "f16") for i, sh in enumerate(shapes)]
+
+
+def _seeded_default_init(model):
+    """nn.Conv2d's default initialisation, seeded (as tests/test_decoder_query_gpu.py's _decoder)."""
+    torch.manual_seed(0)
+    return model().cuda()
+
+
+# every c_in and output width _fusable admits that the query and the training step use, at P = 6231, 1, 63, 65, 209 and 64:
+# below, at and above the 64-pixel tile.  tests/test_decoder_query_gpu.py takes the fused forward at these shapes as its truth.
+@pytest.mark.parametrize("precision,c_in,out_dim,H,W", _fused_cases([(16, 512, 67, 93), (3, 256, 1, 1), (3, 512, 7, 9), (32, 256, 5, 13),
+                                                                   (1, 768, 11, 19), (16, 256, 8, 8)]))
+def test_fused_decoder_kernels_are_bit_identical_to_the_layer_by_layer_chain(precision, c_in, out_dim, H, W):
     """bf16 / f16 modes: CNN_decoder's forward as ONE kernel (activations resident in LDS, csrc/decoder_fused.hip) and its input-
     gradient chain as one kernel against the same chain run layer by layer through gags_decoder_layer: the arithmetic is
     the same (bf16 operands, fp32 accumulation in ascending k, one rounding per activation), so every output, every kept
-    activation and every gradient must be IDENTICAL; ragged pixel count (not a multiple of the 64-pixel tile)."""
+    activation and every gradient must be IDENTICAL; ragged pixel counts (not a multiple of the 64-pixel tile), one pixel, and
+    every input and output width the fused kernels accept in use.  The layer-by-layer chain is itself held to float64 per
+    element by tests/test_decoder_layer_gpu.py."""
     from gags_amd import decoders as D
     from make_golden_next import decoder_weights
-    wd, _ = decoder_weights(0)
-    dec = _load(D.CNN_decoder(16, 512, precision), wd)
+    if (c_in, out_dim) == (16, 512):
+        wd, _ = decoder_weights(0)
+        dec = _load(D.CNN_decoder(16, 512, precision), wd)
+    else:
+        dec = _seeded_default_init(lambda: D.CNN_decoder(c_in, out_dim, precision))
     mode = D._F16 if precision == "f16" else D._BF16
     g = torch.Generator(device="cuda").manual_seed(21)
-    H, W = 67, 93
-    x = torch.randn(H, W, 16, device="cuda", generator=g).permute(2, 0, 1)
-    G = torch.randn(512, H, W, device="cuda", generator=g)
+    x = torch.randn(H, W, c_in, device="cuda", generator=g).permute(2, 0, 1)
+    G = torch.randn(out_dim, H, W, device="cuda", generator=g)
     res = []
     for fused in (True, False):
         D.FUSED = fused
@@ -438,7 +481,8 @@ def test_fused_decoder_kernels_are_bit_identical_to_the_layer_by_layer_chain(pre
             xi = x.clone().requires_grad_(True)
             dec.zero_grad(set_to_none=True)
             params = [t for m in dec.convs() for t in (m.weight, m.bias)]
-            logits, acts, wb, h, w, c_in = D._chain_forward(xi.detach(), "decoder", params, mode)
+            logits, acts, wb, h, w, _ = D._chain_forward(xi.detach(), "decoder", params, mode)
+            assert len(acts) == (10 if fused else 9)  # (the fused forward ran, and keeps its masks; or it did not)
             y = dec(xi)
             (y * G).sum().backward()
             res.append((logits.clone(), [a.clone() for a in acts], y.detach().clone(), xi.grad.clone(),
@@ -456,20 +500,22 @@ def test_fused_decoder_kernels_are_bit_identical_to_the_layer_by_layer_chain(pre
         assert torch.equal(u, v)
 
 
-@pytest.mark.parametrize("precision", ["bf16", "f16"])
-def test_fused_scale_decoder_kernels_are_bit_identical_to_the_layer_by_layer_chain(precision):
+@pytest.mark.parametrize("precision,c_in,H,W", _fused_cases([(16, 61, 97), (3, 1, 1), (32, 5, 13), (3, 1, 33)]))
+def test_fused_scale_decoder_kernels_are_bit_identical_to_the_layer_by_layer_chain(precision, c_in, H, W):
     """bf16 / f16 modes: CNN_scale_decoder's six layers as ONE kernel, a wave per 32-pixel tile (csrc/decoder_scale.hip), against
     the same chain run layer by layer: logits, every kept activation, the softmax output, the input gradient and every
-    weight / bias gradient IDENTICAL; ragged pixel count (not a multiple of the tile), and the ReLU bit masks the fused
-    forward leaves behind equal [activation > 0]."""
+    weight / bias gradient IDENTICAL; ragged pixel counts (not a multiple of the tile), one pixel, one pixel more than a tile,
+    the narrowest and the widest input, and the ReLU bit masks the fused forward leaves behind equal [activation > 0]."""
     from gags_amd import decoders as D
     from make_golden_next import decoder_weights
-    _, ws = decoder_weights(0)
-    sdec = _load(D.CNN_scale_decoder(16, 3, precision), ws)
+    if c_in == 16:
+        _, ws = decoder_weights(0)
+        sdec = _load(D.CNN_scale_decoder(16, 3, precision), ws)
+    else:
+        sdec = _seeded_default_init(lambda: D.CNN_scale_decoder(c_in, 3, precision))
     mode = D._F16 if precision == "f16" else D._BF16
     g = torch.Generator(device="cuda").manual_seed(22)
-    H, W = 61, 97
-    x = torch.randn(H, W, 16, device="cuda", generator=g).permute(2, 0, 1)
+    x = torch.randn(H, W, c_in, device="cuda", generator=g).permute(2, 0, 1)
     G = torch.randn(3, H, W, device="cuda", generator=g)
     res = []
     for fused in (True, False):
@@ -478,7 +524,7 @@ def test_fused_scale_decoder_kernels_are_bit_identical_to_the_layer_by_layer_cha
             xi = x.clone().requires_grad_(True)
             sdec.zero_grad(set_to_none=True)
             params = [t for m in sdec.convs() for t in (m.weight, m.bias)]
-            logits, acts, wb, h, w, c_in = D._chain_forward(xi.detach(), "scale", params, mode)
+            logits, acts, wb, h, w, _ = D._chain_forward(xi.detach(), "scale", params, mode)
             y = sdec(xi)
             (y * G).sum().backward()
             res.append((logits.clone(), [a.clone() for a in acts], y.detach().clone(), xi.grad.clone(),
