@@ -275,3 +275,22 @@ def check(code, what):
 def ptr(t):
     """Raw device pointer of a tensor (or NULL)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+# What every binding module needs around a call; used as attributes of this module (_lib.scratch(...)) so that a test
+# can substitute one.
+def stream(device=None):
+    """The current HIP stream of `device` (default: the current device) as the `void *stream` of the C entries."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def on_gpu(module, *tensors):
+    """Refuse anything that is not a GPU tensor, in the name of gags_amd.<module>."""
+    for t in tensors:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"gags_amd.{module}: tensors must live on the GPU (there is no CPU path)")
+
+
+def scratch(nbytes, device):
+    """A uint8 buffer for a C entry's `scratch`; the caller passes the library's own byte count as `scratch_bytes`."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)

@@ -7,6 +7,7 @@
 #include "box_mean.h"
 #include "common.h"
 #include "gags_next.h"
+#include "launch.h"
 #include "reduce.h"
 
 namespace {
@@ -127,7 +128,21 @@ __global__ __launch_bounds__(256) void majority_kernel(int h, int w, int s, cons
     out[((size_t)k * h + i) * w + j] = total == 0 ? mask[((size_t)k * h + i) * w + j] : (2 * ones > total ? 1 : 0);
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
+// (base NULL: sizes only)
+struct ActivateScratch {
+    double *rowsum;
+    unsigned *keys;
+    int64_t total;
+};
+ActivateScratch activate_carve(void *base, int n_phrases, int h, int w)
+{
+    GagsCarve c(base);
+    ActivateScratch L;
+    L.rowsum = c.take<double>((int64_t)n_phrases * h * w);
+    L.keys = c.take<unsigned>((int64_t)n_phrases * 3);
+    L.total = c.total();
+    return L;
+}
 
 }  // namespace
 
@@ -148,7 +163,7 @@ extern "C" int gags_relevancy(int64_t n_pix, int c, int n_pos, int n_neg, const 
 extern "C" int64_t gags_relevancy_activate_scratch_bytes(int n_phrases, int h, int w)
 {
     if (n_phrases <= 0 || h <= 0 || w <= 0) return 0;
-    return al256((int64_t)n_phrases * h * w * 8) + al256((int64_t)n_phrases * 3 * 4);
+    return activate_carve(nullptr, n_phrases, h, w).total;
 }
 
 extern "C" int gags_relevancy_activate(int n_phrases, int h, int w, const float *valid_map, float thresh, int box,
@@ -160,10 +175,11 @@ extern "C" int gags_relevancy_activate(int n_phrases, int h, int w, const float 
     if (n_phrases <= 0 || h <= 0 || w <= 0 || box <= 0 || box > 1024 || smooth_scale < 0 || n_phrases > 65535 || h > 65535)
         return GAGS_EINVAL;
     if (!valid_map || !avg || !blended || !output || !mask_pred || !mask_smooth || !stats || !scratch) return GAGS_EINVAL;
-    if (scratch_bytes < gags_relevancy_activate_scratch_bytes(n_phrases, h, w)) return GAGS_ESCRATCH;
+    const ActivateScratch L = activate_carve(scratch, n_phrases, h, w);
+    if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
-    double *rowsum = (double *)scratch;
-    unsigned *keys = (unsigned *)((char *)scratch + al256((int64_t)n_phrases * h * w * 8));
+    double *rowsum = L.rowsum;
+    unsigned *keys = L.keys;
     const dim3 grid((w + 255) / 256, h, n_phrases);
     hipLaunchKernelGGL(keys_init_kernel, dim3((3 * n_phrases + 63) / 64), dim3(64), 0, st, n_phrases, keys);
     hipLaunchKernelGGL(box_rows_kernel, grid, dim3(256), (size_t)(256 + box) * 4, st, h, w, box, valid_map, rowsum);

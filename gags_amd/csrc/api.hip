@@ -6,21 +6,24 @@
 #include "scan.h"
 
 namespace {
+// the split forward's scratch, written by gags_raster_fwd and read by the backward entries (base NULL: sizes only)
 struct FwdScratch {
-    int64_t wt, gid, sidx, hit, tbuf, total;
+    float *wt, *tbuf;
+    int32_t *gid, *sidx, *hit;
+    int64_t total;
 };
 // slot space: gags_slot_count() slots of 64 weights (common.h)
-inline FwdScratch fwd_layout(int64_t n_isects, int width, int height)
+inline FwdScratch fwd_carve(const void *base, int64_t n_isects, int width, int height)
 {
     const int64_t slots = gags_slot_count(n_isects, gags_tiles(width, height).n);
+    GagsCarve c(base);
     FwdScratch L;
-    int64_t o = 0;
-    L.wt = o; o += al256(slots * 256);
-    L.gid = o; o += al256(slots * 4);
-    L.sidx = o; o += al256(slots * 4);
-    L.hit = o; o += al256((n_isects + 1) * 4);
-    L.tbuf = o; o += al256((int64_t)width * height * 4);
-    L.total = o;
+    L.wt = c.take<float>(slots * 64);
+    L.gid = c.take<int32_t>(slots);
+    L.sidx = c.take<int32_t>(slots);
+    L.hit = c.take<int32_t>(n_isects + 1);
+    L.tbuf = c.take<float>((int64_t)width * height);
+    L.total = c.total();
     return L;
 }
 inline bool fused_width(int d) { return d >= 32 && d % 32 == 0; }  // single-kernel forward / atomic backward
@@ -48,7 +51,7 @@ extern "C" int gags_pack_isects(int n, int64_t n_isects, const int32_t *flatten_
 extern "C" int64_t gags_raster_fwd_scratch_bytes(int64_t n_isects, int width, int height)
 {
     if (n_isects < 0 || width <= 0 || height <= 0) return 0;
-    return fwd_layout(n_isects, width, height).total;
+    return fwd_carve(nullptr, n_isects, width, height).total;
 }
 
 namespace {
@@ -82,12 +85,10 @@ extern "C" int gags_raster_fwd(int d, int n, int width, int height, const float 
     }
     if (!(flags & GAGS_FWD_NO_MFMA) && (split || fused_width(d)) && (packed || n_isects == 0) && n > 0) {
         if (split) {  // split forward: weights once, then the feature stream
-            const FwdScratch L = fwd_layout(n_isects, width, height);
+            const FwdScratch L = fwd_carve(scratch, n_isects, width, height);
             if (scratch_bytes < L.total) return GAGS_ESCRATCH;
-            char *sb = (char *)scratch;
-            float *wt = (float *)(sb + L.wt);
-            int32_t *gid_s = (int32_t *)(sb + L.gid);
-            float *tbuf = (float *)(sb + L.tbuf);
+            float *wt = L.wt, *tbuf = L.tbuf;
+            int32_t *gid_s = L.gid;
             int rc = GAGS_OK;
             // an fp32 table of exactly 16 channels (the reference's own width, train.py:68): the feature pass rides along with
             // the weights pass (bit-identical to the feature kernel: raster_weights.hip); the two ONLY_* flags keep the passes apart
@@ -95,8 +96,8 @@ extern "C" int gags_raster_fwd(int d, int n, int width, int height, const float 
                                 !(reinterpret_cast<uintptr_t>(render_colors) & 15) && !fwd_d16_unfused();
             if (!(flags & GAGS_FWD_ONLY_FEATURES))
                 rc = gags_raster_weights_launch(width, height, n, packed, (flags & GAGS_RECS_BY_GAUSSIAN) ? 1 : 0, isect_offsets, flatten_ids, (int)n_isects, wt,
-                                                gid_s, (int32_t *)(sb + L.sidx), (int32_t *)(sb + L.hit), blk_rows, tbuf,
-                                                render_alphas, last_ids, st, fuse16 ? colors : nullptr, backgrounds, render_colors);
+                                                gid_s, L.sidx, L.hit, blk_rows, tbuf, render_alphas, last_ids, st,
+                                                fuse16 ? colors : nullptr, backgrounds, render_colors);
             if (rc != GAGS_OK || (flags & GAGS_FWD_ONLY_WEIGHTS) || fuse16) return rc;
             return gags_raster_fwd_feat_launch(d, width, height, n, colors, (flags & GAGS_FEAT_F16) ? ((flags & GAGS_FWD_F16MFMA) ? 2 : 1) : 0,
                                                (flags & GAGS_FWD_EXACT) ? 1 : 0, backgrounds, isect_offsets, (int)n_isects,
@@ -201,18 +202,17 @@ extern "C" int gags_bwd_rowmap(int64_t n_isects, int width, int height, const in
         !isect_offsets || !blk_rows)
         return GAGS_EINVAL;
     if (rowmap_elems < gags_bwd_rowmap_elems(n_isects, width, height)) return GAGS_ESCRATCH;
-    const FwdScratch L = fwd_layout(n_isects, width, height);
+    const FwdScratch L = fwd_carve(fwd_scratch, n_isects, width, height);
     if (fwd_scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
     int32_t *trow = rowmap;
     if (hipMemsetAsync(trow, 0, sizeof(int32_t), st) != hipSuccess) return GAGS_ELAUNCH;
     if (n_isects == 0) return hipMemsetAsync(total, 0, sizeof(int32_t), st) == hipSuccess ? GAGS_OK : GAGS_ELAUNCH;
     if (!scratch || scratch_bytes < gags_scan::scratch_bytes(n_isects)) return GAGS_ESCRATCH;
-    const char *fs = (const char *)fwd_scratch;
-    gags_scan::launch<false>((int)n_isects, (const int32_t *)(fs + L.hit), trow + 1, total, (int32_t *)scratch, st);
+    gags_scan::launch<false>((int)n_isects, L.hit, trow + 1, total, (int32_t *)scratch, st);
     GAGS_CHECK_LAUNCH();
     return gags_bwd_slot_rows_launch(width, height, (int)n_isects, isect_offsets, blk_rows,
-                                     (const int32_t *)(fs + L.sidx), trow, rowmap + rowmap_slot_off(n_isects), st);
+                                     L.sidx, trow, rowmap + rowmap_slot_off(n_isects), st);
 }
 
 extern "C" int64_t gags_raster_bwd_geom_scratch_bytes(int64_t n_isects, int width, int height, int n, int d, int64_t n_rows)
@@ -232,16 +232,12 @@ extern "C" int gags_raster_bwd_geom(int d, int n, int width, int height, const f
     if (n == 0) return GAGS_OK;
     if (!colors || !isect_offsets || !packed || !v_render_colors || !blk_rows || !fwd_scratch || !scratch || !v_geo)
         return GAGS_EINVAL;
-    const FwdScratch L = fwd_layout(n_isects, width, height);
+    const FwdScratch L = fwd_carve(fwd_scratch, n_isects, width, height);
     if (fwd_scratch_bytes < L.total) return GAGS_ESCRATCH;
-    const char *fs = (const char *)fwd_scratch;
     return gags_raster_bwd_geom_launch(d, n, width, height, colors, backgrounds, isect_offsets, (int)n_isects, packed,
-                                       v_render_colors, v_render_alphas, blk_rows, (const float *)(fs + L.wt),
-                                       (const int32_t *)(fs + L.gid), (const int32_t *)(fs + L.sidx),
-                                       (const float *)(fs + L.tbuf), scratch, scratch_bytes, v_geo,
-                                       (flags & GAGS_RECS_BY_GAUSSIAN) ? 1 : 0, row_base, n_rows,
-                                       (const int32_t *)(fs + L.hit), flatten_ids, (flags & GAGS_GEOM_F32MFMA) ? 1 : 0,
-                                       (hipStream_t)stream);
+                                       v_render_colors, v_render_alphas, blk_rows, L.wt, L.gid, L.sidx, L.tbuf, scratch,
+                                       scratch_bytes, v_geo, (flags & GAGS_RECS_BY_GAUSSIAN) ? 1 : 0, row_base, n_rows, L.hit,
+                                       flatten_ids, (flags & GAGS_GEOM_F32MFMA) ? 1 : 0, (hipStream_t)stream);
 }
 
 extern "C" int gags_blended_mask(int64_t n_isects, int width, int height, int n, const int32_t *flatten_ids,
@@ -253,10 +249,9 @@ extern "C" int gags_blended_mask(int64_t n_isects, int width, int height, int n,
     if (hipMemsetAsync(mask, 0, (size_t)n, (hipStream_t)stream) != hipSuccess) return GAGS_ELAUNCH;
     if (n_isects == 0) return GAGS_OK;
     if (!flatten_ids || !fwd_scratch) return GAGS_EINVAL;
-    const FwdScratch L = fwd_layout(n_isects, width, height);
+    const FwdScratch L = fwd_carve(fwd_scratch, n_isects, width, height);
     if (fwd_scratch_bytes < L.total) return GAGS_ESCRATCH;
-    return gags_blended_mask_launch((int)n_isects, (const int32_t *)((const char *)fwd_scratch + L.hit), flatten_ids, mask,
-                                    (hipStream_t)stream);
+    return gags_blended_mask_launch((int)n_isects, L.hit, flatten_ids, mask, (hipStream_t)stream);
 }
 
 extern "C" int gags_raster_bwd_colors_staged(int d, int n, int width, int height, const int32_t *isect_offsets,
@@ -278,11 +273,10 @@ extern "C" int gags_raster_bwd_colors_staged(int d, int n, int width, int height
         return GAGS_EINVAL;
     // (the rows kernel reads a tile's four slot counts as ONE 16-byte scalar load)
     if (reinterpret_cast<uintptr_t>(blk_rows) & 15) return GAGS_EINVAL;
-    const FwdScratch L = fwd_layout(n_isects, width, height);
+    const FwdScratch L = fwd_carve(fwd_scratch, n_isects, width, height);
     if (fwd_scratch_bytes < L.total) return GAGS_ESCRATCH;
-    const char *fs = (const char *)fwd_scratch;
     return gags_raster_bwd_staged_launch(d, width, height, n, isect_offsets, (int)n_isects, v_render_colors, blk_rows,
-                                         rowmap, rows, (const float *)(fs + L.wt), (const int32_t *)(fs + L.gid),
-                                         rowmap + rowmap_slot_off(n_isects), scratch, scratch_bytes, v_colors, stage,
-                                         ch_begin, ch_count, rows_dev, wire_pos, wire, keep_prev, keep_cur, (hipStream_t)stream);
+                                         rowmap, rows, L.wt, L.gid, rowmap + rowmap_slot_off(n_isects), scratch, scratch_bytes,
+                                         v_colors, stage, ch_begin, ch_count, rows_dev, wire_pos, wire, keep_prev, keep_cur,
+                                         (hipStream_t)stream);
 }

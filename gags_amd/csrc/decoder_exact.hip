@@ -20,6 +20,7 @@
 // reference's nn.Conv2d stacks in by default on the GPU its README names -- at half the matrix work and two thirds of the
 // split / LDS work of the exact tier.  fp32 tensors in memory, fp32 accumulation, the same deterministic reductions.
 #include "decoder_common.h"
+#include "launch.h"
 #ifdef GAGS_H16
 #error "decoder_exact.hip splits fp32 into bfloat16 terms: it is compiled once, without -DGAGS_H16"
 #endif
@@ -450,7 +451,6 @@ __global__ __launch_bounds__(256) void head_bwd_exact_kernel(int64_t P, int C, i
     }
 }
 
-inline int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int64_t wgrad_chunk(int64_t n_pix)
 {
     // ~512 pixel chunks (two workgroups per CU), whole 32-pixel steps

@@ -2,6 +2,7 @@
 // 256 inputs, general -- each leaving one partial matrix per pixel chunk in scratch, and the fixed-order sum of those
 // partials into the parameter's own shape.  The plan (which kernel, how many chunks) is the same for both operand types.
 #include "decoder_common.h"
+#include "launch.h"
 
 namespace {
 
@@ -509,7 +510,7 @@ inline int64_t wgrad_scratch_bytes(int64_t n_pix, int n_out, int k_in)
     if (n_pix <= 0 || n_out <= 0 || k_in <= 0) return 0;
     int64_t parts;
     wgrad_plan(n_pix, n_out, k_in, parts);
-    return (parts * ((int64_t)n_out * k_in + n_out) * 4 + 255) / 256 * 256;
+    return al256(parts * ((int64_t)n_out * k_in + n_out) * 4);
 }
 
 int wgrad_impl(int64_t n_pix, int n_out, int k_in, const void *dz, const void *a1, const void *a2, float *d_w, float *d_b, int co,

@@ -18,6 +18,7 @@
 #include <cmath>
 #include "common.h"
 #include "gags_next.h"
+#include "launch.h"
 
 namespace {
 
@@ -128,8 +129,6 @@ __global__ __launch_bounds__(256) void finalise_kernel(int c0, int64_t hw, const
     samples[(c0 + cc) * hw + px] = wi >= 0 ? min_depth[wi] : 0.f;
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
-
 // cameras per launch: their depth maps (and the scatter's winner maps) within CACHE_BUDGET, at least 1
 inline int chunk_cams(int n_cams, int h, int w)
 {
@@ -144,16 +143,20 @@ bool bad_sizes(int64_t n, int n_cams, int h, int w, int cut_bound)
            (int64_t)h * w > INT32_MAX || cut_bound < 0;
 }
 
-struct Layout {
-    int64_t cams, winner, total;
+// packed camera constants, one chunk's winner maps (base NULL: sizes only)
+struct Scratch {
+    float *cams;
+    int *winner;
+    int64_t total;
 };
 
-Layout layout(int n_cams, int h, int w)
+Scratch carve(void *base, int n_cams, int h, int w)
 {
-    Layout L;
-    L.cams = 0;
-    L.winner = al256((int64_t)n_cams * CAM_FLOATS * 4);
-    L.total = L.winner + al256((int64_t)chunk_cams(n_cams, h, w) * h * w * 4);
+    GagsCarve c(base);
+    Scratch L;
+    L.cams = c.take<float>((int64_t)n_cams * CAM_FLOATS);
+    L.winner = c.take<int>((int64_t)chunk_cams(n_cams, h, w) * h * w);
+    L.total = c.total();
     return L;
 }
 
@@ -162,7 +165,7 @@ Layout layout(int n_cams, int h, int w)
 extern "C" int64_t gags_depthsample_scratch_bytes(int64_t n, int n_cams, int h, int w)
 {
     if (bad_sizes(n, n_cams, h, w, 0) || n == 0) return 0;
-    return layout(n_cams, h, w).total;
+    return carve(nullptr, n_cams, h, w).total;
 }
 
 extern "C" int gags_depthsample_map(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats,
@@ -174,10 +177,10 @@ extern "C" int gags_depthsample_map(int64_t n, int n_cams, int h, int w, const f
     if (bad_sizes(n, n_cams, h, w, cut_bound)) return GAGS_EINVAL;
     if (n == 0) return GAGS_OK;
     if (!xyz || !viewmats || !Ks || !depths || !min_depth || !scratch) return GAGS_EINVAL;
-    const Layout L = layout(n_cams, h, w);
+    const Scratch L = carve(scratch, n_cams, h, w);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
-    float *cams = (float *)((char *)scratch + L.cams);
+    float *cams = L.cams;
     hipLaunchKernelGGL(pack_cams_kernel, dim3((n_cams + 63) / 64), dim3(64), 0, st, n_cams, viewmats, Ks, cams);
     const int chunk = chunk_cams(n_cams, h, w);
     const unsigned nb = (unsigned)((n + 255) / 256);
@@ -205,10 +208,10 @@ extern "C" int gags_depthsample_scatter(int64_t n, int n_cams, int h, int w, con
         return GAGS_OK;
     }
     if (!xyz || !viewmats || !Ks || !depths || !min_depth || !scratch) return GAGS_EINVAL;
-    const Layout L = layout(n_cams, h, w);
+    const Scratch L = carve(scratch, n_cams, h, w);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
-    float *cams = (float *)((char *)scratch + L.cams);
-    int *winner = (int *)((char *)scratch + L.winner);
+    float *cams = L.cams;
+    int *winner = L.winner;
     hipLaunchKernelGGL(pack_cams_kernel, dim3((n_cams + 63) / 64), dim3(64), 0, st, n_cams, viewmats, Ks, cams);
     const int chunk = chunk_cams(n_cams, h, w);
     const unsigned nb = (unsigned)((n + 255) / 256), nbp = (unsigned)((hw + 255) / 256);

@@ -310,30 +310,37 @@ inline bool featvis_args_ok(int c, int64_t n_pix, int layout)
 inline int64_t samples_of(int64_t n_pix) { return (n_pix + 2) / 3; }
 inline int64_t chunks_of(int64_t n_pix) { return (samples_of(n_pix) + ROW_CHUNK - 1) / ROW_CHUNK; }
 
+// (both carves: base NULL = sizes only)
 struct MomentsScratch {
-    int64_t nrm, partial, psum, total;
+    float *nrm, *partial;
+    double *psum;
+    int64_t total;
 };
-inline MomentsScratch moments_scratch(int c, int64_t n_pix)
+inline MomentsScratch moments_carve(void *base, int c, int64_t n_pix)
 {
+    GagsCarve v(base);
     MomentsScratch m;
     const int64_t nch = chunks_of(n_pix);
-    m.nrm = 0;
-    m.partial = al256(samples_of(n_pix) * 4);
-    m.psum = m.partial + al256(nch * c * c * 4);
-    m.total = m.psum + al256(nch * c * 8);
+    m.nrm = v.take<float>(samples_of(n_pix));
+    m.partial = v.take<float>(nch * c * c);
+    m.psum = v.take<double>(nch * c);
+    m.total = v.total();
     return m;
 }
 
 struct SelectScratch {
-    int64_t hist, bin_hi, resid, total;
+    unsigned *hist, *bin_hi;
+    long long *resid;
+    int64_t total;
 };
-inline SelectScratch select_scratch(int n_ranks)
+inline SelectScratch select_carve(void *base, int n_ranks)
 {
+    GagsCarve v(base);
     SelectScratch s;
-    s.hist = 0;
-    s.bin_hi = al256((int64_t)(1 + n_ranks) * BINS * 4);
-    s.resid = s.bin_hi + 256;
-    s.total = s.resid + 256;
+    s.hist = v.take<unsigned>((int64_t)(1 + n_ranks) * BINS);
+    s.bin_hi = v.take<unsigned>(MAX_RANKS);
+    s.resid = v.take<long long>(MAX_RANKS);
+    s.total = v.total();
     return s;
 }
 
@@ -343,7 +350,7 @@ extern "C" int gags_featvis_row_chunk(void) { return ROW_CHUNK; }
 
 extern "C" int64_t gags_featvis_moments_scratch_bytes(int c, int64_t n_pix)
 {
-    return featvis_args_ok(c, n_pix, 0) ? moments_scratch(c, n_pix).total : 0;
+    return featvis_args_ok(c, n_pix, 0) ? moments_carve(nullptr, c, n_pix).total : 0;
 }
 
 extern "C" int gags_featvis_moments(int c, int64_t n_pix, const float *x, int layout, double *sum, double *gram, void *scratch,
@@ -351,13 +358,13 @@ extern "C" int gags_featvis_moments(int c, int64_t n_pix, const float *x, int la
 {
     GAGS_CLEAR_ERR();
     if (!featvis_args_ok(c, n_pix, layout) || samples_of(n_pix) < 4 || !x || !sum || !gram || !scratch) return GAGS_EINVAL;
-    const MomentsScratch m = moments_scratch(c, n_pix);
+    const MomentsScratch m = moments_carve(scratch, c, n_pix);
     if (scratch_bytes < m.total) return GAGS_ESCRATCH;
     const hipStream_t st = (hipStream_t)stream;
     const int64_t S = samples_of(n_pix);
     const int nch = (int)chunks_of(n_pix), nt = (c + MT - 1) / MT;
-    float *nrm = (float *)((char *)scratch + m.nrm), *partial = (float *)((char *)scratch + m.partial);
-    double *psum = (double *)((char *)scratch + m.psum);
+    float *nrm = m.nrm, *partial = m.partial;
+    double *psum = m.psum;
     const dim3 grid(nt * (nt + 1) / 2, nch);
     if (layout == 1) {
         hipLaunchKernelGGL(sample_norm_kernel<1>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, c, n_pix, S, x, nrm);
@@ -387,7 +394,7 @@ extern "C" int gags_featvis_project(int c, int64_t n_pix, const float *x, int la
 
 extern "C" int64_t gags_featvis_select_scratch_bytes(int n_ranks)
 {
-    return n_ranks >= 1 && n_ranks <= MAX_RANKS ? select_scratch(n_ranks).total : 0;
+    return n_ranks >= 1 && n_ranks <= MAX_RANKS ? select_carve(nullptr, n_ranks).total : 0;
 }
 
 extern "C" int gags_featvis_select(int64_t n, const float *values, int64_t group, int64_t stride, int n_ranks, const int64_t *ranks,
@@ -402,11 +409,11 @@ extern "C" int gags_featvis_select(int64_t n, const float *values, int64_t group
         if (ranks[j] < 0 || ranks[j] >= n) return GAGS_EINVAL;
         r.k[j] = ranks[j];
     }
-    const SelectScratch s = select_scratch(n_ranks);
+    const SelectScratch s = select_carve(scratch, n_ranks);
     if (scratch_bytes < s.total) return GAGS_ESCRATCH;
     const hipStream_t st = (hipStream_t)stream;
-    unsigned *hist = (unsigned *)((char *)scratch + s.hist), *bin_hi = (unsigned *)((char *)scratch + s.bin_hi);
-    long long *resid = (long long *)((char *)scratch + s.resid);
+    unsigned *hist = s.hist, *bin_hi = s.bin_hi;
+    long long *resid = s.resid;
     if (hipMemsetAsync(hist, 0, (size_t)(1 + n_ranks) * BINS * 4, st) != hipSuccess) return GAGS_ELAUNCH;
     const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(select_hist_kernel<0>, dim3(blocks), dim3(256), 0, st, n, values, group, stride, n_ranks,

@@ -197,23 +197,30 @@ __global__ __launch_bounds__(KNN_BOX) void knn_query_kernel(int n, int n_boxes, 
 
 inline unsigned grid_stride_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 2048); }
 
-struct KnnLayout {
-    int64_t bbox, keys_in, keys, order, pts, aabb, sort, total;
+struct KnnScratch {
+    unsigned *bbox;
+    uint32_t *keys_in, *keys;
+    int32_t *order;
+    float4 *pts, *aabb;
+    void *sort;
+    int64_t sort_bytes, total;
 };
 
-KnnLayout knn_layout(int64_t n)
+// (base NULL: sizes only)
+KnnScratch knn_carve(void *base, int64_t n)
 {
     const int64_t n_boxes = (n + KNN_BOX - 1) / KNN_BOX;
-    KnnLayout L;
-    int64_t o = 0;
-    L.bbox = o; o += al256(6 * 4);
-    L.keys_in = o; o += al256(n * 4);
-    L.keys = o; o += al256(n * 4);
-    L.order = o; o += al256(n * 4);
-    L.pts = o; o += al256(n * 16);
-    L.aabb = o; o += al256(n_boxes * 32);
-    L.sort = o; o += al256(gags_sort_u32_scratch_bytes(n));
-    L.total = o;
+    GagsCarve c(base);
+    KnnScratch L;
+    L.bbox = c.take<unsigned>(6);
+    L.keys_in = c.take<uint32_t>(n);
+    L.keys = c.take<uint32_t>(n);
+    L.order = c.take<int32_t>(n);
+    L.pts = c.take<float4>(n);
+    L.aabb = c.take<float4>(n_boxes * 2);
+    L.sort = c.take_bytes(gags_sort_u32_scratch_bytes(n));
+    L.sort_bytes = c.last();
+    L.total = c.total();
     return L;
 }
 
@@ -224,7 +231,7 @@ inline bool knn_count_ok(int64_t n) { return n >= 4 && n < (1ll << 31); }
 extern "C" int64_t gags_knn3_dist2_scratch_bytes(int64_t n)
 {
     if (!knn_count_ok(n)) return 0;
-    return knn_layout(n).total;
+    return knn_carve(nullptr, n).total;
 }
 
 extern "C" int gags_knn3_dist2(int64_t n, const float *xyz, float *dist2, void *scratch, int64_t scratch_bytes, void *stream)
@@ -232,21 +239,20 @@ extern "C" int gags_knn3_dist2(int64_t n, const float *xyz, float *dist2, void *
     GAGS_CLEAR_ERR();
     if (!knn_count_ok(n)) return GAGS_EINVAL;  // fewer than three neighbours (the reference's infinite scale), or past int32 positions
     if (!xyz || !dist2 || !scratch) return GAGS_EINVAL;
-    const KnnLayout L = knn_layout(n);
+    const KnnScratch L = knn_carve(scratch, n);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
-    char *sb = (char *)scratch;
-    unsigned *bbox = (unsigned *)(sb + L.bbox);
-    uint32_t *keys_in = (uint32_t *)(sb + L.keys_in), *keys = (uint32_t *)(sb + L.keys);
-    int32_t *order = (int32_t *)(sb + L.order);
-    float4 *pts = (float4 *)(sb + L.pts), *aabb = (float4 *)(sb + L.aabb);
+    unsigned *bbox = L.bbox;
+    uint32_t *keys_in = L.keys_in, *keys = L.keys;
+    int32_t *order = L.order;
+    float4 *pts = L.pts, *aabb = L.aabb;
     const unsigned nb = (unsigned)((n + 255) / 256), n_boxes = (unsigned)((n + KNN_BOX - 1) / KNN_BOX);
 
     hipLaunchKernelGGL(knn_bbox_init_kernel, dim3(1), dim3(64), 0, st, bbox);
     hipLaunchKernelGGL(knn_bbox_kernel, dim3(grid_stride_blocks(n), 3), dim3(256), 0, st, n, xyz, bbox);
     hipLaunchKernelGGL(knn_key_kernel, dim3(nb), dim3(256), 0, st, n, xyz, bbox, keys_in);
     GAGS_CHECK_LAUNCH();
-    const int rc = gags_sort_pairs_u32(n, 30, keys_in, nullptr, keys, order, sb + L.sort, L.total - L.sort, st);  // (argsort)
+    const int rc = gags_sort_pairs_u32(n, 30, keys_in, nullptr, keys, order, L.sort, L.sort_bytes, st);  // (argsort)
     if (rc != GAGS_OK) return rc;
     hipLaunchKernelGGL(knn_gather_kernel, dim3(nb), dim3(256), 0, st, n, xyz, order, pts);
     hipLaunchKernelGGL(knn_box_kernel, dim3(n_boxes), dim3(KNN_BOX), 0, st, n, pts, aabb);

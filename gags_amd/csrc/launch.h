@@ -9,6 +9,28 @@
 // scratch regions start on 256-byte boundaries
 inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
+// A scratch layout, written once: a cursor that hands out the regions of a buffer in order and adds up what they take.
+// A driver's layout function carves with the caller's buffer as `base` and its *_scratch_bytes export with NULL, which only
+// counts (offsets are integers; a pointer is formed from a real base alone).  `base` is const so that an entry which only
+// reads an earlier call's scratch can carve it too.
+class GagsCarve {
+    char *base_;
+    int64_t off_ = 0, last_ = 0;
+
+public:
+    explicit GagsCarve(const void *base) : base_((char *)base) {}
+    void *take_bytes(int64_t bytes)
+    {
+        void *p = base_ ? base_ + off_ : nullptr;
+        off_ += last_ = al256(bytes);
+        return p;
+    }
+    template <class T>
+    T *take(int64_t count) { return (T *)take_bytes(count * (int64_t)sizeof(T)); }
+    int64_t last() const { return last_; }   // bytes of the region taken last (a sub-scratch handed on to another driver)
+    int64_t total() const { return off_; }
+};
+
 // the 16x16 tiles of a width x height image: tiles across, tiles down, tiles in all
 struct GagsTiles {
     int w, h, n;

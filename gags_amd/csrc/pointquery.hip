@@ -174,25 +174,32 @@ __global__ __launch_bounds__(256) void vote_kernel(int64_t n, int n_masks, const
 
 inline unsigned grid_stride_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 2048); }
 
-struct SmoothLayout {
-    int64_t bbox, pcell, ckeys_in, ckeys, csrc, cxyz, qcell, qorder, sort, total;
+struct SmoothScratch {
+    unsigned *bbox;
+    uint64_t *pcell, *ckeys_in, *ckeys, *qcell;
+    int32_t *csrc, *qorder;
+    float *cxyz;
+    void *sort;
+    int64_t sort_bytes, total;
 };
 
-SmoothLayout smooth_layout(int n_masks, int64_t n)
+// (base NULL: sizes only)
+SmoothScratch smooth_carve(void *base, int n_masks, int64_t n)
 {
     const int64_t nk = (int64_t)n_masks * n;
-    SmoothLayout L;
-    int64_t o = 0;
-    L.bbox = o; o += al256(3 * 4);
-    L.pcell = o; o += al256(n * 8);
-    L.ckeys_in = o; o += al256(nk * 8);
-    L.ckeys = o; o += al256(nk * 8);
-    L.csrc = o; o += al256(nk * 4);
-    L.cxyz = o; o += al256(nk * 12);
-    L.qcell = o; o += al256(n * 8);
-    L.qorder = o; o += al256(n * 4);
-    L.sort = o; o += al256(gags_sort_u64_scratch_bytes(std::max(nk, n)));
-    L.total = o;
+    GagsCarve c(base);
+    SmoothScratch L;
+    L.bbox = c.take<unsigned>(3);
+    L.pcell = c.take<uint64_t>(n);
+    L.ckeys_in = c.take<uint64_t>(nk);
+    L.ckeys = c.take<uint64_t>(nk);
+    L.csrc = c.take<int32_t>(nk);
+    L.cxyz = c.take<float>(nk * 3);
+    L.qcell = c.take<uint64_t>(n);
+    L.qorder = c.take<int32_t>(n);
+    L.sort = c.take_bytes(gags_sort_u64_scratch_bytes(std::max(nk, n)));
+    L.sort_bytes = c.last();
+    L.total = c.total();
     return L;
 }
 
@@ -225,7 +232,7 @@ extern "C" int gags_point_relevancy_mask(int n_phrases, int64_t n, const float *
 extern "C" int64_t gags_point_mask_smooth_scratch_bytes(int n_masks, int64_t n)
 {
     if (n_masks <= 0 || n <= 0 || n_masks > MAX_MASKS || (int64_t)n_masks * n >= (1ll << 31)) return 0;
-    return smooth_layout(n_masks, n).total;
+    return smooth_carve(nullptr, n_masks, n).total;
 }
 
 extern "C" int gags_point_mask_smooth(int n_masks, int64_t n, const float *xyz, const unsigned char *mask, double radius,
@@ -239,17 +246,15 @@ extern "C" int gags_point_mask_smooth(int n_masks, int64_t n, const float *xyz, 
     const int64_t nk = (int64_t)n_masks * n;
     if (nk >= (1ll << 31)) return GAGS_EINVAL;  // the radix sort's limit (and int32 source positions)
     if (!xyz || !mask || !out || !scratch) return GAGS_EINVAL;
-    const SmoothLayout L = smooth_layout(n_masks, n);
+    const SmoothScratch L = smooth_carve(scratch, n_masks, n);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
-    char *sb = (char *)scratch;
-    unsigned *bbox = (unsigned *)(sb + L.bbox);
-    uint64_t *pcell = (uint64_t *)(sb + L.pcell), *ckeys_in = (uint64_t *)(sb + L.ckeys_in), *ckeys = (uint64_t *)(sb + L.ckeys);
-    int32_t *csrc = (int32_t *)(sb + L.csrc), *qorder = (int32_t *)(sb + L.qorder);
-    float *cxyz = (float *)(sb + L.cxyz);
-    uint64_t *qcell = (uint64_t *)(sb + L.qcell);
-    void *sort_scratch = sb + L.sort;
-    const int64_t sort_bytes = L.total - L.sort;
+    unsigned *bbox = L.bbox;
+    uint64_t *pcell = L.pcell, *ckeys_in = L.ckeys_in, *ckeys = L.ckeys, *qcell = L.qcell;
+    int32_t *csrc = L.csrc, *qorder = L.qorder;
+    float *cxyz = L.cxyz;
+    void *sort_scratch = L.sort;
+    const int64_t sort_bytes = L.sort_bytes;
 
     const double cell = radius * (1.0 + 0x1p-20);
     const int64_t cap = std::max<int64_t>((int64_t)threshold + 1, 10);  // counts past cap change nothing

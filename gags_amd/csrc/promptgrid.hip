@@ -24,6 +24,7 @@
 #include <algorithm>
 #include "common.h"
 #include "gags_next.h"
+#include "launch.h"
 
 namespace {
 
@@ -55,21 +56,23 @@ Shape shape(int n_cams, int n, int crop_h)
     return s;
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
-
-struct Layout {
-    int64_t dsum, ssum, scount, sub, total;
+// the per-slab partial sums (base NULL: sizes only); a single slab writes the outputs themselves and needs no scratch
+struct Scratch {
+    double *dsum, *ssum;
+    int *scount, *sub;
+    int64_t total;
 };
 
-Layout layout(const Shape &s)
+Scratch carve(void *base, const Shape &s)
 {
     const int64_t parts = s.blocks * s.slabs;
-    Layout L;
-    L.dsum = 0;
-    L.ssum = L.dsum + al256(parts * 8);
-    L.scount = L.ssum + al256(parts * 8);
-    L.sub = L.scount + al256(parts * 4);
-    L.total = s.slabs > 1 ? L.sub + al256(parts * NSUB * 4) : 0;
+    GagsCarve c(base);
+    Scratch L;
+    L.dsum = c.take<double>(parts);
+    L.ssum = c.take<double>(parts);
+    L.scount = c.take<int>(parts);
+    L.sub = c.take<int>(parts * NSUB);
+    L.total = s.slabs > 1 ? c.total() : 0;
     return L;
 }
 
@@ -233,7 +236,7 @@ __global__ __launch_bounds__(128) void finish_kernel(int slabs, bool has_s, cons
 extern "C" int64_t gags_promptgrid_scratch_bytes(int n_cams, int h, int w, int n_per_side, int crop_h)
 {
     if (bad_sizes(n_cams, h, w, n_per_side, 0, crop_h)) return 0;
-    return layout(shape(n_cams, n_per_side, crop_h)).total;
+    return carve(nullptr, shape(n_cams, n_per_side, crop_h)).total;
 }
 
 extern "C" int gags_promptgrid_stats(int n_cams, int h, int w, int n_per_side, int crop_w, int crop_h, const float *depths,
@@ -246,15 +249,14 @@ extern "C" int gags_promptgrid_stats(int n_cams, int h, int w, int n_per_side, i
     if (!depths || !tab || !depth_sum || !depth_count) return GAGS_EINVAL;
     if (samples && (!sample_sum || !sample_count || !sub_count)) return GAGS_EINVAL;
     const Shape s = shape(n_cams, n_per_side, crop_h);
-    const Layout L = layout(s);
+    const Scratch L = carve(scratch, s);
     if (L.total > 0 && (!scratch || scratch_bytes < L.total)) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
     const bool slabbed = s.slabs > 1;
-    char *sc = (char *)scratch;
-    double *pd = slabbed ? (double *)(sc + L.dsum) : depth_sum;
-    double *ps = slabbed ? (double *)(sc + L.ssum) : sample_sum;
-    int *pc = slabbed ? (int *)(sc + L.scount) : sample_count;
-    int *psub = slabbed ? (int *)(sc + L.sub) : sub_count;
+    double *pd = slabbed ? L.dsum : depth_sum;
+    double *ps = slabbed ? L.ssum : sample_sum;
+    int *pc = slabbed ? L.scount : sample_count;
+    int *psub = slabbed ? L.sub : sub_count;
     const dim3 grid((unsigned)(s.blocks * s.slabs));
     if (samples)
         hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(THREADS), 0, st, n_per_side, s.slabs, s.rows_per_slab, h, w, crop_w,

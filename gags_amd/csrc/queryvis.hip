@@ -14,6 +14,7 @@
 #include "box_mean.h"
 #include "common.h"
 #include "gags_next.h"
+#include "launch.h"
 
 namespace {
 
@@ -176,7 +177,6 @@ __global__ __launch_bounds__(256) void loss_maps_kernel(int c, int64_t n_pix, co
     mean_abs_gt[p] = (float)(sg / (double)c);
 }
 
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
 inline bool query_dims_ok(int n_maps, int n_frames, int h, int w)
 {

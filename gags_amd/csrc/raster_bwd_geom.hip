@@ -573,39 +573,49 @@ __global__ __launch_bounds__(64) void raster_bwd_geom(int width, int height, int
 }
 
 namespace {
-struct GeomLayout {
-    int64_t S, bgdot, grow, key, idx, key_s, idx_s, seg, table, rinv, mask, sort, total;
+struct GeomScratch {
+    float *S, *bgdot, *grow, *rinv;
+    size_t s_stride, bg_stride;  // floats from one pass's S / bgdot buffer to the next
+    uint32_t *key, *key_s;
+    int32_t *idx, *idx_s, *seg;
+    uint4 *table;
+    unsigned char *mask;
+    void *sort;
+    int64_t sort_bytes, total;
 };
-// n_rows < 0: one row per slot of the sparse slot space; else the compact row count (sum of blk_rows)
-inline GeomLayout geom_layout(int64_t n_isects, int width, int height, int n_gauss, int d, int64_t n_rows)
+// n_rows < 0: one row per slot of the sparse slot space; else the compact row count (sum of blk_rows).  base NULL: sizes only
+inline GeomScratch geom_carve(void *base, int64_t n_isects, int width, int height, int n_gauss, int d, int64_t n_rows)
 {
     const int64_t slots = gags_slot_count(n_isects, gags_tiles(width, height).n);
     const int64_t rows = n_rows < 0 ? slots : (n_rows > 0 ? n_rows : 1);
-    GeomLayout L;
-    int64_t o = 0;
+    GagsCarve c(base);
+    GeomScratch L;
     const int64_t n_pass = std::max(1, (d + SD_MAXCH - 1) / SD_MAXCH);  // the split-f16 dot pass: one S / bgdot buffer per pass
-    L.S = o; o += n_pass * al256((rows + 64) * 256);  // numbered like the per-slot rows: compact (n_rows) or the sparse slot space
-    L.bgdot = o; o += n_pass * al256((int64_t)width * height * 4);
-    L.grow = o; o += al256(rows * 32);
-    L.key = o; o += al256(rows * 4);
-    L.idx = o; o += al256(rows * 4);
-    L.key_s = o; o += al256(rows * 4);
-    L.idx_s = o; o += al256(rows * 4);
-    L.seg = o; o += al256(((int64_t)n_gauss + 2) * 4);
+    L.s_stride = (size_t)al256((rows + 64) * 256) / 4;  // numbered like the per-slot rows: compact (n_rows) or the sparse slot space
+    L.bg_stride = (size_t)al256((int64_t)width * height * 4) / 4;
+    L.S = c.take<float>(n_pass * (int64_t)L.s_stride);
+    L.bgdot = c.take<float>(n_pass * (int64_t)L.bg_stride);
+    L.grow = c.take<float>(rows * 8);
+    L.key = c.take<uint32_t>(rows);
+    L.idx = c.take<int32_t>(rows);
+    L.key_s = c.take<uint32_t>(rows);
+    L.idx_s = c.take<int32_t>(rows);
+    L.seg = c.take<int32_t>((int64_t)n_gauss + 2);
     // split feature table of one pass (<= 256 channels: 6 bytes per channel), 1 / row scale, blended mask
     const int64_t ks = (std::min(d, SD_MAXCH) + 31) / 32;  // 32-channel steps, 192 bytes each
-    L.table = o; o += al256((int64_t)n_gauss * ks * 192);
-    L.rinv = o; o += al256((int64_t)n_gauss * 4);
-    L.mask = o; o += al256((int64_t)n_gauss);
-    L.sort = o; o += al256(gags_sort_u32_scratch_bytes(rows));
-    L.total = o;
+    L.table = c.take<uint4>((int64_t)n_gauss * ks * 12);
+    L.rinv = c.take<float>(n_gauss);
+    L.mask = c.take<unsigned char>(n_gauss);
+    L.sort = c.take_bytes(gags_sort_u32_scratch_bytes(rows));
+    L.sort_bytes = c.last();
+    L.total = c.total();
     return L;
 }
 }  // namespace
 
 int64_t gags_raster_bwd_geom_scratch_bytes_impl(int64_t n_isects, int width, int height, int n_gauss, int d, int64_t n_rows)
 {
-    return geom_layout(n_isects, width, height, n_gauss, d, n_rows).total;
+    return geom_carve(nullptr, n_isects, width, height, n_gauss, d, n_rows).total;
 }
 
 int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const float *colors, const float *backgrounds,
@@ -618,14 +628,13 @@ int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const
     GAGS_CLEAR_ERR();
     if (d < 16 || d % 8 != 0) return 1;
     if (!row_base) n_rows = -1;
-    const GeomLayout L = geom_layout(n_isects, width, height, n_gauss, d, n_rows);
+    const GeomScratch L = geom_carve(scratch, n_isects, width, height, n_gauss, d, n_rows);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     const int tile_w = gags_tiles(width, height).w, n_tiles = gags_tiles(width, height).n;
     const int64_t slots = n_rows < 0 ? gags_slot_count(n_isects, n_tiles) : n_rows;  // rows to sort
-    char *sb = (char *)scratch;
-    float *S = (float *)(sb + L.S), *bgdot = backgrounds ? (float *)(sb + L.bgdot) : nullptr, *grow = (float *)(sb + L.grow);
-    uint32_t *key = (uint32_t *)(sb + L.key), *key_s = (uint32_t *)(sb + L.key_s);
-    int32_t *idx = (int32_t *)(sb + L.idx), *idx_s = (int32_t *)(sb + L.idx_s), *seg = (int32_t *)(sb + L.seg);
+    float *S = L.S, *bgdot = backgrounds ? L.bgdot : nullptr, *grow = L.grow;
+    uint32_t *key = L.key, *key_s = L.key_s;
+    int32_t *idx = L.idx, *idx_s = L.idx_s, *seg = L.seg;
     // unused slots of the sparse slot space sort behind every Gaussian (the compact numbering has none)
     if (n_rows < 0 && hipMemsetD32Async((hipDeviceptr_t)key, n_gauss, (size_t)slots, st) != hipSuccess) return GAGS_ELAUNCH;
     static bool raised[GAGS_MAX_DEVICES];
@@ -633,17 +642,16 @@ int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const
         return GAGS_ELAUNCH;
     const bool split16 = !f32mfma && hit && flatten_ids;
     // the split-f16 dot pass writes one S / bgdot buffer per 256-channel pass (the fp32 one accumulates in the first)
-    const int64_t s_rows = (n_rows < 0 ? gags_slot_count(n_isects, n_tiles) : (n_rows > 0 ? n_rows : 1)) + 64;
-    const size_t s_stride = (size_t)al256(s_rows * 256) / 4, bg_stride = (size_t)al256((int64_t)width * height * 4) / 4;
+    const size_t s_stride = L.s_stride, bg_stride = L.bg_stride;
     const int n_pass = split16 ? (d + SD_MAXCH - 1) / SD_MAXCH : 1;
     if (split16) {
         static bool raised16[GAGS_MAX_DEVICES];
         if (!gags_raise_dynamic_lds(raised16, {(const void *)raster_bwd_sdot_f16<SD_MAXCH / 32>, (const void *)raster_bwd_sdot_f16<0>},
                                     2 * 64 * (SD_MAXCH + SF_PADH) * 2))
             return GAGS_ELAUNCH;
-        unsigned char *mask = (unsigned char *)(sb + L.mask);
-        uint4 *table = (uint4 *)(sb + L.table);
-        float *rinv = (float *)(sb + L.rinv);
+        unsigned char *mask = L.mask;
+        uint4 *table = L.table;
+        float *rinv = L.rinv;
         if (hipMemsetAsync(mask, 0, (size_t)n_gauss, st) != hipSuccess) return GAGS_ELAUNCH;
         if (n_isects > 0) {
             const int rc = gags_blended_mask_launch(n_isects, hit, flatten_ids, mask, st);
@@ -678,7 +686,7 @@ int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const
                        n_gauss, reinterpret_cast<const GRec *>(packed), offsets, n_isects, blk_rows, wt, gid_s, sidx_s, S, Tbuf,
                        v_alphas, bgdot, grow, key, idx, by_gauss, row_base, n_pass, s_stride, bg_stride);
     GAGS_CHECK_LAUNCH();
-    int rc = gags_rows_group_launch(slots, n_gauss, nullptr, key, idx, key_s, idx_s, seg, sb + L.sort, L.total - L.sort, st);
+    int rc = gags_rows_group_launch(slots, n_gauss, nullptr, key, idx, key_s, idx_s, seg, L.sort, L.sort_bytes, st);
     if (rc != GAGS_OK) return rc;
     rc = gags_rows_reduce_launch(n_gauss, 8, 0, 8, seg, idx_s, grow, 8, v_geo, false, st);
     if (rc != GAGS_OK) return rc;

@@ -487,21 +487,28 @@ __global__ __launch_bounds__(64) void slot_rows_kernel(int n_tiles, int n_isects
     }
 }
 
-struct StagedLayout {
-    int64_t key, idx, key_s, idx_s, seg, sort, prow, total;
+// the staged backward's scratch (base NULL: sizes only)
+struct StagedScratch {
+    uint32_t *key, *key_s;
+    int32_t *idx, *idx_s, *seg;
+    void *sort;
+    int64_t sort_bytes;
+    float *prow;
+    int64_t total;
 };
-inline StagedLayout staged_layout(int64_t rows, int n_gauss, int d)
+inline StagedScratch staged_carve(void *base, int64_t rows, int n_gauss, int d)
 {
-    StagedLayout L;
-    int64_t o = 0;
-    L.key = o; o += al256(rows * 4);
-    L.idx = o; o += al256(rows * 4);
-    L.key_s = o; o += al256(rows * 4);
-    L.idx_s = o; o += al256(rows * 4);
-    L.seg = o; o += al256(((int64_t)n_gauss + 2) * 4);
-    L.sort = o; o += al256(gags_sort_u32_scratch_bytes(rows));
-    L.prow = o; o += al256(rows * (int64_t)d * 4);
-    L.total = o;
+    GagsCarve c(base);
+    StagedScratch L;
+    L.key = c.take<uint32_t>(rows);
+    L.idx = c.take<int32_t>(rows);
+    L.key_s = c.take<uint32_t>(rows);
+    L.idx_s = c.take<int32_t>(rows);
+    L.seg = c.take<int32_t>((int64_t)n_gauss + 2);
+    L.sort = c.take_bytes(gags_sort_u32_scratch_bytes(rows));
+    L.sort_bytes = c.last();
+    L.prow = c.take<float>(rows * (int64_t)d);
+    L.total = c.total();
     return L;
 }
 
@@ -509,7 +516,7 @@ inline StagedLayout staged_layout(int64_t rows, int n_gauss, int d)
 
 int64_t gags_bwd_staged_scratch_bytes_impl(int64_t rows, int n_gauss, int d)
 {
-    return staged_layout(rows > 0 ? rows : 1, n_gauss, d).total;
+    return staged_carve(nullptr, rows > 0 ? rows : 1, n_gauss, d).total;
 }
 
 int gags_bwd_slot_rows_launch(int width, int height, int n_isects, const int32_t *offsets, const int32_t *blk_rows,
@@ -553,12 +560,11 @@ int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, con
     // range by range through a scratch a quarter (an eighth ...) the size -- what lets heavy views fit (C5H: 80 M rows)
     const bool narrow = (stage_flags & GAGS_STAGED_RANGE_SCRATCH) != 0;
     const int pp = narrow ? ((ch_count + 3) & ~3) : d;
-    const StagedLayout L = staged_layout(rows > 0 ? rows : 1, n_gauss, pp);
+    const StagedScratch L = staged_carve(scratch, rows > 0 ? rows : 1, n_gauss, pp);
     if (scratch_bytes < L.total) return GAGS_ESCRATCH;
-    char *sb = (char *)scratch;
-    uint32_t *key = (uint32_t *)(sb + L.key), *key_s = (uint32_t *)(sb + L.key_s);
-    int32_t *idx = (int32_t *)(sb + L.idx), *idx_s = (int32_t *)(sb + L.idx_s), *seg = (int32_t *)(sb + L.seg);
-    float *prow = (float *)(sb + L.prow) - (narrow ? ch_begin : 0);  // (indexed by absolute channel)
+    uint32_t *key = L.key, *key_s = L.key_s;
+    int32_t *idx = L.idx, *idx_s = L.idx_s, *seg = L.seg;
+    float *prow = L.prow - (narrow ? ch_begin : 0);  // (indexed by absolute channel)
     if (rows > 0 && sA) {
         // 128-channel slices, then 64, then 32-channel slices (the last one ragged when the range ends at an odd d)
 #define GAGS_ROWS_LAUNCH(KERNEL, CH0, NSL)                                                                           \
@@ -583,7 +589,7 @@ int gags_raster_bwd_staged_launch(int d, int width, int height, int n_gauss, con
 #undef GAGS_ROWS_LAUNCH
     }
     if (sS) {
-        const int rc = gags_rows_group_launch(rows, n_gauss, rows_dev, key, idx, key_s, idx_s, seg, sb + L.sort, L.prow - L.sort, st);
+        const int rc = gags_rows_group_launch(rows, n_gauss, rows_dev, key, idx, key_s, idx_s, seg, L.sort, L.sort_bytes, st);
         if (rc != GAGS_OK) return rc;
     }
     if (sR) {

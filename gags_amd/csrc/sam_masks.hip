@@ -20,6 +20,7 @@
 #include <algorithm>
 #include "common.h"
 #include "gags_next.h"
+#include "launch.h"
 
 namespace {
 
@@ -184,7 +185,22 @@ __global__ __launch_bounds__(256) void paint_kernel(int M, int64_t hw, int64_t n
 
 bool bad_sizes(int M, int64_t hw) { return M < 0 || M > MAX_MASKS || hw < 1 || hw >= MAX_PIXELS; }
 inline int64_t words(int64_t hw) { return (hw + 63) / 64; }
-inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
+
+// the NMS driver's scratch: the packed masks and the M x M intersection counts (base NULL: sizes only)
+struct NmsScratch {
+    void *bits;
+    int *inter;
+    int64_t total;
+};
+NmsScratch nms_carve(void *base, int M, int64_t hw)
+{
+    GagsCarve c(base);
+    NmsScratch L;
+    L.bits = c.take<unsigned long long>((int64_t)M * words(hw));
+    L.inter = c.take<int>((int64_t)M * M);
+    L.total = c.total();
+    return L;
+}
 
 int launch_pack(int M, int64_t hw, const unsigned char *masks, void *bits, int *area, hipStream_t st)
 {
@@ -274,7 +290,7 @@ extern "C" int gags_masks_paint(int n_masks, int64_t n_pixels, const void *bits,
 extern "C" int64_t gags_masks_nms_scratch_bytes(int n_masks, int64_t n_pixels)
 {
     if (bad_sizes(n_masks, n_pixels) || n_masks == 0) return 0;
-    return al256((int64_t)n_masks * words(n_pixels) * 8) + al256((int64_t)n_masks * n_masks * 4);
+    return nms_carve(nullptr, n_masks, n_pixels).total;
 }
 
 extern "C" int gags_masks_nms_colmax(int n_masks, int64_t n_pixels, const unsigned char *masks, const int32_t *order,
@@ -284,11 +300,12 @@ extern "C" int gags_masks_nms_colmax(int n_masks, int64_t n_pixels, const unsign
     if (bad_sizes(n_masks, n_pixels)) return GAGS_EINVAL;
     if (n_masks == 0) return GAGS_OK;
     if (!masks || !order || !area || !colmax || !scratch) return GAGS_EINVAL;
-    if (scratch_bytes < gags_masks_nms_scratch_bytes(n_masks, n_pixels)) return GAGS_ESCRATCH;
+    const NmsScratch L = nms_carve(scratch, n_masks, n_pixels);
+    if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nw = words(n_pixels);
-    void *bits = scratch;
-    int *inter = (int *)((char *)scratch + al256((int64_t)n_masks * nw * 8));
+    void *bits = L.bits;
+    int *inter = L.inter;
     int rc = launch_pack(n_masks, n_pixels, masks, bits, area, st);
     if (rc != GAGS_OK) return rc;
     rc = launch_pairs(n_masks, nw, bits, inter, st);

@@ -174,14 +174,32 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter(int64_t n, int shift, c
     }
 }
 
+// the sort's scratch: the ping-pong copies of keys and values, the per-block histograms, the 256 digit totals
+// (base NULL: sizes only)
 template <typename K>
-int64_t sort_scratch_bytes_t(int64_t n_in)
+struct SortScratch {
+    K *ktmp;
+    int32_t *vtmp;
+    uint32_t *hist, *totals;
+    int64_t total;
+};
+template <typename K>
+SortScratch<K> sort_carve(void *base, int64_t n)
 {
-    const int64_t n = n_in > 0 ? n_in : 1;
     const int64_t nblocks = (n + RS_TILE - 1) / RS_TILE;
-    const int64_t keys = ((n * (int64_t)sizeof(K) + 255) / 256) * 256, vals = ((n * 4 + 255) / 256) * 256;
-    const int64_t hist = ((nblocks * RS_RADIX * 4 + 255) / 256) * 256;
-    return keys + vals + hist + RS_RADIX * 4;  // + the 256 digit totals
+    GagsCarve c(base);
+    SortScratch<K> L;
+    L.ktmp = c.take<K>(n);
+    L.vtmp = c.take<int32_t>(n);
+    L.hist = c.take<uint32_t>(nblocks * RS_RADIX);
+    L.totals = c.take<uint32_t>(RS_RADIX);
+    L.total = c.total();
+    return L;
+}
+template <typename K>
+int64_t sort_scratch_bytes_t(int64_t n)
+{
+    return sort_carve<K>(nullptr, n > 0 ? n : 1).total;
 }
 
 // stable LSD sort of (key, value) pairs on key bits [first_bit, first_bit + nbits); ping-pongs through
@@ -194,14 +212,12 @@ int sort_pairs_t(int64_t n, int first_bit, int nbits, const K *keys_in, const in
     if (n < 0 || n >= (1ll << 31) || nbits <= 0 || first_bit < 0 || first_bit + nbits > (int)(8 * sizeof(K)))
         return GAGS_EINVAL;
     if (!keys_in || !keys_out || !vals_out || !scratch) return GAGS_EINVAL;  // (vals_in may be NULL: argsort)
-    if (scratch_bytes < sort_scratch_bytes_t<K>(n)) return GAGS_ESCRATCH;
+    const SortScratch<K> L = sort_carve<K>(scratch, n);
+    if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     const int nblocks = (int)((n + RS_TILE - 1) / RS_TILE);
-    const int64_t keys_b = ((n * (int64_t)sizeof(K) + 255) / 256) * 256, vals_b = ((n * 4 + 255) / 256) * 256;
-    K *ktmp = (K *)scratch;
-    int32_t *vtmp = (int32_t *)((char *)scratch + keys_b);
-    uint32_t *hist = (uint32_t *)((char *)scratch + keys_b + vals_b);
-    const int64_t hist_b = (((int64_t)nblocks * RS_RADIX * 4 + 255) / 256) * 256;
-    uint32_t *totals = (uint32_t *)((char *)scratch + keys_b + vals_b + hist_b);
+    K *ktmp = L.ktmp;
+    int32_t *vtmp = L.vtmp;
+    uint32_t *hist = L.hist, *totals = L.totals;
     const int passes = (nbits + 7) / 8;
     const K *src_k = keys_in;
     const int32_t *src_v = vals_in;
@@ -261,7 +277,23 @@ __global__ __launch_bounds__(256) void gather_i32_kernel(int n, const int32_t *_
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) dst[i] = src[idx[i]];
 }
-inline int64_t al256s(int64_t x) { return (x + 255) / 256 * 256; }
+// the depth order's scratch (base NULL: sizes only); its first region, n keys, is not used
+struct OrderScratch {
+    uint32_t *keys_sorted;
+    void *sort;
+    int64_t sort_bytes, total;
+};
+OrderScratch order_carve(void *base, int64_t n)
+{
+    GagsCarve c(base);
+    OrderScratch L;
+    c.take<uint32_t>(n);
+    L.keys_sorted = c.take<uint32_t>(n);
+    L.sort = c.take_bytes(sort_scratch_bytes_t<uint32_t>(n));
+    L.sort_bytes = c.last();
+    L.total = c.total();
+    return L;
+}
 }  // namespace
 
 // K7a: depth order of the Gaussians (stable argsort of the depth bits: depths of visible Gaussians are
@@ -269,8 +301,7 @@ inline int64_t al256s(int64_t x) { return (x + 255) / 256 * 256; }
 // tile counts in that order.  N elements instead of n_isects: the per-intersection sort then only groups by tile.
 extern "C" int64_t gags_depth_order_scratch_bytes(int n)
 {
-    const int64_t m = n > 0 ? n : 1;
-    return 2 * al256s(m * 4) + sort_scratch_bytes_t<uint32_t>(m);
+    return order_carve(nullptr, n > 0 ? n : 1).total;
 }
 
 extern "C" int gags_depth_order(int n, const float *depths, const int32_t *tiles_per_gauss, int32_t *order,
@@ -280,14 +311,12 @@ extern "C" int gags_depth_order(int n, const float *depths, const int32_t *tiles
     if (n < 0) return GAGS_EINVAL;
     if (n == 0) return GAGS_OK;
     if (!depths || !order || !scratch || (tiles_ordered && !tiles_per_gauss)) return GAGS_EINVAL;
-    if (scratch_bytes < gags_depth_order_scratch_bytes(n)) return GAGS_ESCRATCH;
+    const OrderScratch L = order_carve(scratch, n);
+    if (scratch_bytes < L.total) return GAGS_ESCRATCH;
     hipStream_t st = (hipStream_t)stream;
-    char *sb = (char *)scratch;
-    uint32_t *keys_sorted = (uint32_t *)(sb + al256s((int64_t)n * 4));
-    void *sort_scratch = sb + 2 * al256s((int64_t)n * 4);
     // argsort: the first pass numbers the inputs itself (no iota kernel, no index array read)
-    const int rc = sort_pairs_t<uint32_t>(n, 0, 32, reinterpret_cast<const uint32_t *>(depths), nullptr, keys_sorted, order,
-                                          sort_scratch, sort_scratch_bytes_t<uint32_t>(n), st);
+    const int rc = sort_pairs_t<uint32_t>(n, 0, 32, reinterpret_cast<const uint32_t *>(depths), nullptr, L.keys_sorted, order,
+                                          L.sort, L.sort_bytes, st);
     if (rc != GAGS_OK) return rc;
     if (tiles_ordered)  // (optional: gags_cumsum_gather_i32 scans tiles_per_gauss[order[.]] without this copy)
         hipLaunchKernelGGL(gather_i32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, order, tiles_per_gauss,

@@ -49,9 +49,7 @@ from torch import nn
 from . import _lib
 from ._lib import check, ptr
 
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_st = _lib.stream  # (the name the tests call)
 
 
 # f16 tier: the gradient entering a backward chain is multiplied by a power of two S such that S * max|cotangent proxy| is
@@ -66,7 +64,7 @@ def _pow2_scale(amax, target_log2=F16_TARGET_LOG2, div=1.0):
     a = amax.detach().reshape(1)
     a = a if a.dtype == torch.float32 else a.float()
     out = torch.empty(2, device=a.device)
-    check(_lib.load().gags_pow2_scale(ptr(a), float(div), float(target_log2), ptr(out), _st()), "gags_pow2_scale")
+    check(_lib.load().gags_pow2_scale(ptr(a), float(div), float(target_log2), ptr(out), _lib.stream()), "gags_pow2_scale")
     return out[0:1], out[1:2]
 
 
@@ -108,7 +106,7 @@ class _SplitTier:
     def head_bwd(self, p, c, head, logits, g, layout):
         dz = torch.empty(p, c, device=g.device)
         check(_lib.load().gags_decoder_head_bwd_exact(p, c, logits.shape[1], head, ptr(logits), ptr(g), layout, ptr(dz), c,
-                                                      _st()), "gags_decoder_head_bwd_exact")
+                                                      _lib.stream()), "gags_decoder_head_bwd_exact")
         return dz
 
     def input_grad(self, gin, h, w, c_in):
@@ -133,7 +131,7 @@ class _HalfTier:
 
     def first_activation(self, p, xp, k):
         a0 = torch.empty(p, k, dtype=self.dtype, device=xp.device)
-        check(self.fn("gags_decoder_pack_input")(p, xp.shape[1], k, ptr(xp), ptr(a0), _st()), "gags_decoder_pack_input")
+        check(self.fn("gags_decoder_pack_input")(p, xp.shape[1], k, ptr(xp), ptr(a0), _lib.stream()), "gags_decoder_pack_input")
         return a0
 
     def layer(self, p, w, b, a1, a2=None, **kw):
@@ -152,13 +150,13 @@ class _HalfTier:
 
     def head_bwd(self, p, c, head, logits, g, layout):
         dz = torch.empty(p, logits.shape[1], dtype=self.dtype, device=g.device)
-        check(self.fn("gags_decoder_head_bwd")(p, c, logits.shape[1], head, ptr(logits), ptr(g), ptr(dz), layout, _st()),
+        check(self.fn("gags_decoder_head_bwd")(p, c, logits.shape[1], head, ptr(logits), ptr(g), ptr(dz), layout, _lib.stream()),
               "gags_decoder_head_bwd")
         return dz
 
     def input_grad(self, gin, h, w, c_in):
         gx = torch.empty(h, w, c_in, device=gin.device)
-        check(self.fn("gags_decoder_unpack_grad")(h * w, c_in, gin.shape[1], ptr(gin), ptr(gx), _st()), "gags_decoder_unpack_grad")
+        check(self.fn("gags_decoder_unpack_grad")(h * w, c_in, gin.shape[1], ptr(gin), ptr(gx), _lib.stream()), "gags_decoder_unpack_grad")
         return gx.permute(2, 0, 1)
 
 
@@ -197,7 +195,7 @@ def _layer(n_pix, w, b, a1, a2=None, relu=True, f32=False, mask_src=None, residu
     yf = torch.empty(n_pix, n, device=dev) if f32 else None
     ypre = torch.empty(n_pix, n, dtype=tier.dtype, device=dev) if premask else None
     check(tier.fn("gags_decoder_layer")(n_pix, n, k, ptr(a1), ptr(a2), ptr(w), ptr(b), int(relu), ptr(mask_src),
-                                        ptr(residual), ptr(y), ptr(ypre), ptr(yf), _st()), "gags_decoder_layer")
+                                        ptr(residual), ptr(y), ptr(ypre), ptr(yf), _lib.stream()), "gags_decoder_layer")
     out = yf if f32 else y
     return (out, ypre) if premask else out
 
@@ -210,9 +208,9 @@ def _wgrad(n_pix, dz, a1, a2, n, k, tier=_BF16, shape=None, scale=None):
     dw = torch.empty((co, ci) if shape is None else shape, device=dz.device)
     db = torch.empty(co, device=dz.device)
     nb = tier.fn("gags_decoder_wgrad_scratch_bytes")(n_pix, n, k)
-    scratch = torch.empty(max(nb, 4), dtype=torch.uint8, device=dz.device)  # partial matrices per pixel chunk
+    scratch = _lib.scratch(max(nb, 4), dz.device)  # partial matrices per pixel chunk
     check(tier.fn("gags_decoder_wgrad_out")(n_pix, n, k, ptr(dz), ptr(a1), ptr(a2), ptr(dw), ptr(db), co, ci, ptr(scale),
-                                            ptr(scratch), nb, _st()), "gags_decoder_wgrad_out")
+                                            ptr(scratch), nb, _lib.stream()), "gags_decoder_wgrad_out")
     return dw, db
 
 
@@ -256,7 +254,7 @@ def _pack_weights(weights, biases, tier=_BF16):
             m, ints(*[d[0] for d in dims[sl]]), ints(*[d[1] for d in dims[sl]]), ptrs(*[t.data_ptr() for t in srcs[sl]]),
             ptrs(*[t.data_ptr() for t in bsrcs[sl]]), ptrs(*[w.data_ptr() for w, _ in out[sl]]),
             ptrs(*[w._gags_t.data_ptr() for w, _ in out[sl]]), ptrs(*[w._gags_frag.data_ptr() for w, _ in out[sl]]),
-            ptrs(*[w._gags_t._gags_frag.data_ptr() for w, _ in out[sl]]), ptrs(*[b.data_ptr() for _, b in out[sl]]), _st()),
+            ptrs(*[w._gags_t._gags_frag.data_ptr() for w, _ in out[sl]]), ptrs(*[b.data_ptr() for _, b in out[sl]]), _lib.stream()),
             "gags_decoder_pack_layers")
     if len(_PACK_CACHE) > 16:
         _PACK_CACHE.clear()
@@ -286,7 +284,7 @@ def _xlayer(n_pix, w, b, a1, a2=None, relu=True, mask_src=None, residual=None, p
     y = (torch.zeros if ldy > n else torch.empty)(n_pix, ldy, device=dev)
     ypre = torch.empty(n_pix, ldy, device=dev) if premask else None
     check(_lib.load().gags_decoder_layer_split(n_pix, n, k, ptr(a1), ptr(a2), a1.shape[1], ptr(w), ptr(b), int(relu),
-                                               ptr(mask_src), ptr(residual), ptr(y), ptr(ypre), ldy, terms, _st()),
+                                               ptr(mask_src), ptr(residual), ptr(y), ptr(ypre), ldy, terms, _lib.stream()),
           "gags_decoder_layer_split")
     return (y, ypre) if premask else y
 
@@ -297,9 +295,9 @@ def _xwgrad(n_pix, dz, a1, a2, n, k, want_bias=True, terms=3):
     dw = torch.empty(n, k, device=dev)
     db = torch.empty(n, device=dev) if want_bias else None
     nb = lib.gags_decoder_wgrad_exact_scratch_bytes(n_pix, n, k)
-    scratch = torch.empty(max(nb, 4), dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(max(nb, 4), dev)
     check(lib.gags_decoder_wgrad_split(n_pix, n, k, ptr(dz), dz.shape[1], ptr(a1), ptr(a2), a1.shape[1], ptr(dw), ptr(db),
-                                       ptr(scratch), nb, terms, _st()), "gags_decoder_wgrad_split")
+                                       ptr(scratch), nb, terms, _lib.stream()), "gags_decoder_wgrad_split")
     return dw, db
 
 
@@ -380,12 +378,12 @@ def _fused_forward(tier, kind, p, xp, wb, head_out):
         # 8 layers x whole 64-pixel groups x 8 words (an opaque buffer: the two kernels' own layout)
         masks = torch.empty(8, (p + 63) // 64 * 64, 8, dtype=torch.int32, device=dev)
         check(tier.fn("gags_decoder_fwd_fused")(p, xp.shape[1], logits.shape[1], ptr(xp), wfs, bs, ats, ptr(masks), ptr(logits),
-                                                 _st()), "gags_decoder_fwd_fused")
+                                                 _lib.stream()), "gags_decoder_fwd_fused")
     else:
         logits = torch.empty(p, 32, device=dev) if head_out is None else None
         masks = torch.empty(p, 11, dtype=torch.int32, device=dev)
         check(tier.fn("gags_scale_decoder_fwd_fused_head")(p, xp.shape[1], ptr(xp), wfs, bs, ats, ptr(masks), ptr(logits),
-                                                            ptr(head_out), _st()), "gags_scale_decoder_fwd_fused_head")
+                                                            ptr(head_out), _lib.stream()), "gags_scale_decoder_fwd_fused_head")
     return logits, acts + [masks]
 
 
@@ -431,11 +429,11 @@ def _chain_backward(dz, acts, wb, kind, h, w, c_in, shapes, need_x, need_w, tier
             gx = torch.empty(h, w, c_in, device=dev) if need_x else None
             check(tier.fn("gags_decoder_bwd_fused_scaled")(p, c_in, dz.shape[1], ptr(dz), arr(*[t.data_ptr() for t in wtf]),
                                                            ptr(masks), arr_dz(*[t.data_ptr() for t in dzs]), ptr(gx), ptr(scale),
-                                                           _st()), "gags_decoder_bwd_fused_scaled")
+                                                           _lib.stream()), "gags_decoder_bwd_fused_scaled")
             gx = None if gx is None else gx.permute(2, 0, 1)
         else:
             check(tier.fn("gags_scale_decoder_bwd_fused")(p, ptr(dz), arr(None, *[t.data_ptr() for t in wtf[1:]]), ptr(masks),
-                                                          arr_dz(*[t.data_ptr() for t in dzs]), _st()), "gags_scale_decoder_bwd_fused")
+                                                          arr_dz(*[t.data_ptr() for t in dzs]), _lib.stream()), "gags_scale_decoder_bwd_fused")
         for i in reversed(range(len(wb))):
             wg(i, dzs[i] if i < len(dzs) else dz, acts[i])
         if kind == "scale" and need_x:
@@ -490,7 +488,7 @@ class _DecoderFn(torch.autograd.Function):
         pm = kind == "decoder" and c_out % 4 == 0 and logits.shape[1] <= 512 and logits.shape[1] % 32 == 0
         out = torch.empty((h, w, c_out) if pm else (c_out, h, w), device=x.device)
         check(_lib.load().gags_decoder_head(p, c_out, logits.shape[1], 0 if kind == "decoder" else 1, ptr(logits), ptr(out),
-                                            1 if pm else 0, _st()), "gags_decoder_head")
+                                            1 if pm else 0, _lib.stream()), "gags_decoder_head")
         if pm:
             out = out.permute(2, 0, 1)
         ctx.save_for_backward(logits, *acts)
@@ -509,7 +507,7 @@ class _DecoderFn(torch.autograd.Function):
         g = g if s is None else g * s
         if ctx.from_output:  # `logits` is the softmax output y [3, H, W]: dz = y (g - <y, g>) (gags_softmax_head_bwd_y)
             dz = torch.empty(p, 32, dtype=tier.dtype, device=g.device)
-            check(tier.fn("gags_softmax_head_bwd_y")(p, c, 32, ptr(logits), ptr(g), ptr(dz), _st()), "gags_softmax_head_bwd_y")
+            check(tier.fn("gags_softmax_head_bwd_y")(p, c, 32, ptr(logits), ptr(g), ptr(dz), _lib.stream()), "gags_softmax_head_bwd_y")
         else:
             dz = tier.head_bwd(p, c, 0 if ctx.kind == "decoder" else 1, logits, g, 1 if pm else 0)
         need_x, need_w = _needs(ctx, 4)
@@ -534,7 +532,7 @@ class _DecoderDistillFn(torch.autograd.Function):
         l1 = torch.empty(h, w, device=x.device)
         mask = torch.empty(h, w, device=x.device)
         check(_lib.load().gags_decoder_head_distill_fwd(c_out, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0],
-                                                        ptr(logits), ptr(e), ptr(seg), ptr(sc), ptr(l1), ptr(mask), _st()),
+                                                        ptr(logits), ptr(e), ptr(seg), ptr(sc), ptr(l1), ptr(mask), _lib.stream()),
               "gags_decoder_head_distill_fwd")
         ctx.tier, ctx.c_out, ctx.hw, ctx.c_in, ctx.wb = tier, c_out, (h, w), c_in, wb
         ctx.shapes = [tuple(t.shape) for t in params[0::2]]
@@ -556,7 +554,7 @@ class _DecoderDistillFn(torch.autograd.Function):
         dz = torch.empty(h * w, logits.shape[1], dtype=tier.dtype, device=logits.device)
         check(getattr(_lib.load(), tier.distill_bwd)(c, logits.shape[1], h, w, seg.shape[1], seg.shape[2], e.shape[0], ptr(logits),
                                                      ptr(e), ptr(seg), ptr(sc), ptr(vm), ptr(dz), *([] if s is None else [ptr(s)]),
-                                                     ptr(vs), _st()), tier.distill_bwd)
+                                                     ptr(vs), _lib.stream()), tier.distill_bwd)
         need_x, need_w = _needs(ctx, 6)
         gx, grads = _chain_backward(dz, acts, ctx.wb, "decoder", h, w, ctx.c_in, ctx.shapes, need_x, need_w, tier, inv)
         return (gx, None, None, vs, None, None, *grads)
@@ -582,8 +580,7 @@ class _Stack(nn.Module):
         return [m for m in self.decoder if isinstance(m, nn.Conv2d)]
 
     def forward(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("gags_amd.decoders: tensors must live on the GPU (there is no CPU path)")
+        _lib.on_gpu("decoders", x)
         params = [t for m in self.convs() for t in (m.weight, m.bias)]
         return _DecoderFn.apply(x, self.kind, self.output_dim, self.precision, *params)
 
@@ -603,8 +600,7 @@ class CNN_decoder(_Stack):
         (l1_map [H,W], mask [1,H,W] bool); gradients reach x, the decoder's parameters and scale_map.  Not part of the
         reference's module: an optional fast path (every precision tier: the fp32-tensor tiers keep the logits' gradient
         in fp32, the bf16 mode rounds it to bf16)."""
-        if not x.is_cuda:
-            raise RuntimeError("gags_amd.decoders: tensors must live on the GPU (there is no CPU path)")
+        _lib.on_gpu("decoders", x)
         if self.output_dim != 512:
             # other widths: the decoder, then the fused ground-truth assembly + L1 map
             l1, mask = __import__("gags_amd.losses", fromlist=["distill_l1_map"]).distill_l1_map(self(x), img_embed, seg_map, scale_map)
@@ -646,8 +642,7 @@ class CNN_decoder(_Stack):
             raise ValueError(f"CNN_decoder.query: {pos.shape[0]} + {neg.shape[0]} phrases, at most {QUERY_MAX_PHRASES} per call")
         if x.dim() != 3:
             raise ValueError(f"CNN_decoder.query: x must be [C_in, H, W], got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("gags_amd.decoders: tensors must live on the GPU (there is no CPU path)")
+        _lib.on_gpu("decoders", x)
         tier = _tier(self.precision)
         if tier.fused and FUSED and self.output_dim % 256 == 0:
             wb = tier.weights([t for m in self.convs() for t in (m.weight, m.bias)])
@@ -659,7 +654,7 @@ class CNN_decoder(_Stack):
                 check(tier.fn("gags_decoder_query_fused")(h * w, xp.shape[1], self.output_dim, ptr(xp),
                                                           arr(*[_frag_layout(wgt).data_ptr() for wgt, _ in wb]),
                                                           arr(*[b.data_ptr() for _, b in wb]), ptr(text), pos.shape[0], neg.shape[0],
-                                                          ptr(probs), _st()), "gags_decoder_query_fused")
+                                                          ptr(probs), _lib.stream()), "gags_decoder_query_fused")
                 return probs if pairs else probs[..., 0].reshape(-1, h, w).contiguous()
         feat = self(x).permute(1, 2, 0)
         return head._all(feat.reshape(-1, feat.shape[-1])) if pairs else head.get_max_across(feat[None])[0]

@@ -25,10 +25,6 @@ GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"
 STATS = ("xyz_gradient_accum", "denom", "max_radii2D")
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _need_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
@@ -81,7 +77,7 @@ def stats(model, grad, radii, update_filter, visibility_filter, width, height):
         _lib.check(_lib.load().gags_densify_stats(
             n, _lib.ptr(grad), _lib.ptr(radii), _lib.ptr(uf), _lib.ptr(vf), float(width * 0.5), float(height * 0.5),
             _lib.ptr(model.xyz_gradient_accum), _lib.ptr(model.denom),
-            _lib.ptr(model.max_radii2D if radii is not None else None), _stream(dev)), "gags_densify_stats")
+            _lib.ptr(model.max_radii2D if radii is not None else None), _lib.stream(dev)), "gags_densify_stats")
 
 
 def accumulate(model, render_pkg):
@@ -111,11 +107,11 @@ def plan_from_flags(flags, classes=(0, 1, 2, 3)):
     lib = _lib.load()
     n, dev = flags.shape[1], flags.device
     with torch.cuda.device(dev):
-        st = _stream(dev)
+        st = _lib.stream(dev)
         cum = torch.empty_like(flags) if len(classes) == 4 else torch.zeros_like(flags)
         totals = torch.zeros(4, dtype=torch.int32, device=dev)
         nbytes = int(lib.gags_scan_scratch_bytes(n))
-        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        scratch = _lib.scratch(nbytes, dev)
         for k in (classes if n else ()):
             _lib.check(lib.gags_cumsum_i32(n, _lib.ptr(flags[k]), _lib.ptr(cum[k]), _lib.ptr(totals[k:]), _lib.ptr(scratch),
                                            nbytes, st), "gags_cumsum_i32")
@@ -151,7 +147,7 @@ def gather(n_out, src, kind, items):
             part = descs[k:k + _lib.GAGS_GATHER_MAX_DESC]
             table = (_lib.GatherDesc * len(part))(*part)
             _lib.check(lib.gags_densify_gather(n_out, _lib.ptr(src), _lib.ptr(kind), len(part),
-                                               ctypes.cast(table, ctypes.c_void_p), _stream(dev)), "gags_densify_gather")
+                                               ctypes.cast(table, ctypes.c_void_p), _lib.stream(dev)), "gags_densify_gather")
     return outs
 
 
@@ -225,7 +221,7 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, gen
         _lib.check(lib.gags_densify_decide(
             n, _lib.ptr(model.xyz_gradient_accum), _lib.ptr(model.denom), _lib.ptr(scaling), _lib.ptr(opacity),
             float(max_grad), float(model.percent_dense * extent), float(min_opacity), float(0.1 * extent),
-            float(max_screen_size) if max_screen_size else 0.0, 1 if max_screen_size else 0, _lib.ptr(flags), _stream(dev)),
+            float(max_screen_size) if max_screen_size else 0.0, 1 if max_screen_size else 0, _lib.ptr(flags), _lib.stream(dev)),
             "gags_densify_decide")
     plan = plan_from_flags(flags)
     n_z = 2 * plan.n_split
@@ -243,7 +239,7 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, gen
         with torch.cuda.device(dev):
             _lib.check(lib.gags_densify_children(
                 plan.n_out, plan.first_child, n, _lib.ptr(plan.src), _lib.ptr(plan.zrow), _lib.ptr(xyz), _lib.ptr(scal),
-                _lib.ptr(rot), _lib.ptr(z), n_z, _lib.ptr(model._xyz), _lib.ptr(model._scaling), _stream(dev)),
+                _lib.ptr(rot), _lib.ptr(z), n_z, _lib.ptr(model._xyz), _lib.ptr(model._scaling), _lib.stream(dev)),
                 "gags_densify_children")
     return plan
 
@@ -272,7 +268,7 @@ def reset_opacity(model):
     m1 = state.get("exp_avg") if state else None
     m2 = state.get("exp_avg_sq") if state else None
     with torch.cuda.device(dev):
-        _lib.check(lib.gags_reset_opacity(new.numel(), _lib.ptr(new), _lib.ptr(m1), _lib.ptr(m2), _stream(dev)),
+        _lib.check(lib.gags_reset_opacity(new.numel(), _lib.ptr(new), _lib.ptr(m1), _lib.ptr(m2), _lib.stream(dev)),
                    "gags_reset_opacity")
     if group is not None:
         stored = model.optimizer.state.pop(old, None)

@@ -17,7 +17,6 @@ Deviations from the reference, all deliberate: several visible Gaussians on one 
 reference's result under single-threaded torch; with threads its index_put_ keeps any of them); depth files are paired with
 cameras by name (the reference pairs sorted file names with cameras sorted by image_name, which differ when one name is a
 prefix of another); every camera and depth map must share one (H, W)."""
-import ctypes
 import os
 
 import numpy as np
@@ -26,16 +25,6 @@ import torch
 from . import _lib
 from ._lib import check, ptr
 from .gaussian_renderer import _intrinsics, render
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _on_gpu(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("gags_amd.depthsample: tensors must live on the GPU (there is no CPU path)")
 
 
 @torch.no_grad()
@@ -54,7 +43,7 @@ def camera_matrices(cameras, device="cuda"):
 
 
 def _args(xyz, viewmats, Ks, depths, cut_bound):
-    _on_gpu(xyz, viewmats, Ks, depths)
+    _lib.on_gpu("depthsample", xyz, viewmats, Ks, depths)
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise ValueError(f"xyz must be [N, 3], got {tuple(xyz.shape)}")
     if depths.dim() != 3:
@@ -73,7 +62,7 @@ def _args(xyz, viewmats, Ks, depths, cut_bound):
 
 def _scratch(lib, n, c, h, w, device):
     nb = lib.gags_depthsample_scratch_bytes(n, c, h, w)
-    return torch.empty(max(nb, 1), dtype=torch.uint8, device=device), nb
+    return _lib.scratch(nb, device), nb
 
 
 def _map(xyz, viewmats, Ks, depths, vis_thresh, cut_bound, dense):
@@ -86,7 +75,7 @@ def _map(xyz, viewmats, Ks, depths, vis_thresh, cut_bound, dense):
     lib = _lib.load()
     scratch, nb = _scratch(lib, n, c, h, w, dev)
     check(lib.gags_depthsample_map(n, c, h, w, ptr(xyz), ptr(viewmats), ptr(Ks), ptr(depths), float(vis_thresh),
-                                   int(cut_bound), ptr(min_depth), ptr(mapping), ptr(visible), ptr(scratch), nb, _st()),
+                                   int(cut_bound), ptr(min_depth), ptr(mapping), ptr(visible), ptr(scratch), nb, _lib.stream()),
           "gags_depthsample_map")
     return min_depth, mapping, visible
 
@@ -117,7 +106,7 @@ def depth_samples(xyz, viewmats, Ks, depths, vis_thresh=0.25, cut_bound=0, retur
     lib = _lib.load()
     scratch, nb = _scratch(lib, n, c, h, w, xyz.device)
     check(lib.gags_depthsample_scatter(n, c, h, w, ptr(xyz), ptr(viewmats), ptr(Ks), ptr(depths), float(vis_thresh),
-                                       int(cut_bound), ptr(min_depth), ptr(samples), ptr(scratch), nb, _st()),
+                                       int(cut_bound), ptr(min_depth), ptr(samples), ptr(scratch), nb, _lib.stream()),
           "gags_depthsample_scatter")
     return (samples, min_depth) if return_min_depth else samples
 

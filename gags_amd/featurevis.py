@@ -31,10 +31,6 @@ from ._lib import check, ptr
 from .losses import _pixel_major, read_sam_clip_feature
 
 
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def row_chunk():
     """Sampled pixels one workgroup of the moments kernel reduces; more are split across workgroups."""
     return int(_lib.load().gags_featvis_row_chunk())
@@ -42,8 +38,7 @@ def row_chunk():
 
 def _map(feature):
     """(tensor whose memory the kernels read, layout, C, H, W)."""
-    if not torch.is_tensor(feature) or not feature.is_cuda:
-        raise RuntimeError("gags_amd.featurevis: tensors must live on the GPU (there is no CPU path)")
+    _lib.on_gpu("featurevis", feature)
     if feature.dim() != 3:
         raise ValueError(f"feature must be [C, H, W], got {tuple(feature.shape)}")
     C, H, W = feature.shape
@@ -73,8 +68,8 @@ def feature_moments(feature):
     s = torch.empty(C, dtype=torch.float64, device=x.device)
     g = torch.empty(C, C, dtype=torch.float64, device=x.device)
     nb = lib.gags_featvis_moments_scratch_bytes(C, P)
-    scratch = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    check(lib.gags_featvis_moments(C, P, ptr(x), layout, ptr(s), ptr(g), ptr(scratch), nb, _st()), "gags_featvis_moments")
+    scratch = _lib.scratch(nb, x.device)
+    check(lib.gags_featvis_moments(C, P, ptr(x), layout, ptr(s), ptr(g), ptr(scratch), nb, _lib.stream()), "gags_featvis_moments")
     return s, g
 
 
@@ -100,7 +95,7 @@ def feature_project(feature, mean, components):
     if tuple(mean.shape) != (C,) or tuple(components.shape) != (3, C):
         raise ValueError(f"mean {tuple(mean.shape)} / components {tuple(components.shape)} do not fit {C} channels")
     t = torch.empty(H * W, 3, device=x.device)
-    check(_lib.load().gags_featvis_project(C, H * W, ptr(x), layout, ptr(mean), ptr(components), ptr(t), _st()),
+    check(_lib.load().gags_featvis_project(C, H * W, ptr(x), layout, ptr(mean), ptr(components), ptr(t), _lib.stream()),
           "gags_featvis_project")
     return t
 
@@ -109,8 +104,7 @@ def feature_project(feature, mean, components):
 def order_statistics(values, ranks, group=1, stride=1, n=None):
     """float32 tensor [len(ranks)] on the device: the ranks[j]-th smallest (0-based) of the pooled values, exactly.  The pool is
     element i = values.flatten()[(i // group) * stride + i % group] for i < n (default: the whole tensor)."""
-    if not values.is_cuda:
-        raise RuntimeError("gags_amd.featurevis: tensors must live on the GPU (there is no CPU path)")
+    _lib.on_gpu("featurevis", values)
     v = values if (values.is_contiguous() and values.dtype == torch.float32) else values.contiguous().float()
     n = v.numel() if n is None else int(n)
     ranks = [int(k) for k in ranks]
@@ -121,9 +115,9 @@ def order_statistics(values, ranks, group=1, stride=1, n=None):
     lib = _lib.load()
     out = torch.empty(len(ranks), device=v.device)
     nb = lib.gags_featvis_select_scratch_bytes(len(ranks))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=v.device)
+    scratch = _lib.scratch(nb, v.device)
     karr = (ctypes.c_int64 * len(ranks))(*ranks)
-    check(lib.gags_featvis_select(n, ptr(v), int(group), int(stride), len(ranks), karr, ptr(out), ptr(scratch), nb, _st()),
+    check(lib.gags_featvis_select(n, ptr(v), int(group), int(stride), len(ranks), karr, ptr(out), ptr(scratch), nb, _lib.stream()),
           "gags_featvis_select")
     return out
 
@@ -199,7 +193,7 @@ def feature_colour(t, q1, q99, H, W, return_uint8=False):
     vis = torch.empty(H, W, 3, device=t.device)
     u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=t.device) if return_uint8 else None
     sub, div = float(np.float32(q1)), float(np.float32(np.float64(q99) - np.float64(q1)))
-    check(_lib.load().gags_featvis_colour(3 * H * W, ptr(t), sub, div, ptr(vis), ptr(u8), _st()), "gags_featvis_colour")
+    check(_lib.load().gags_featvis_colour(3 * H * W, ptr(t), sub, div, ptr(vis), ptr(u8), _lib.stream()), "gags_featvis_colour")
     return (vis, u8) if return_uint8 else vis
 
 

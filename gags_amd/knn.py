@@ -7,7 +7,6 @@ becomes the initial scale of each Gaussian.
 The result is defined to the bit: for point i over all j != i, d2 = (dx*dx + dy*dy) + dz*dz in float32 without FMA, the three
 smallest values b0 <= b1 <= b2, dist2[i] = ((b0 + b1) + b2) / 3 -- equal to a float32 brute force (tests/knn_ref.py).
 There is no CPU path."""
-import ctypes
 
 import torch
 
@@ -32,10 +31,9 @@ def dist2(points):
     out = torch.empty(n, dtype=torch.float32, device=p.device)
     lib = _lib.load()
     nb = lib.gags_knn3_dist2_scratch_bytes(n)
-    scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
+    scratch = _lib.scratch(nb, p.device)
     with torch.cuda.device(p.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib.gags_knn3_dist2(n, ptr(p), ptr(out), ptr(scratch), nb, st), "gags_knn3_dist2")
+        check(lib.gags_knn3_dist2(n, ptr(p), ptr(out), ptr(scratch), nb, _lib.stream()), "gags_knn3_dist2")
     return out
 
 

@@ -30,13 +30,8 @@ from . import _lib
 from ._lib import check, ptr
 
 
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _f(t):
-    if not t.is_cuda:
-        raise RuntimeError("gags_amd.losses: tensors must live on the GPU (there is no CPU path)")
+    _lib.on_gpu("losses", t)
     return t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
 
 
@@ -90,7 +85,7 @@ class _Entropy(torch.autograd.Function):
     def forward(ctx, scale_map):
         s = _f(scale_map)
         acc = torch.zeros(1, dtype=torch.float64, device=s.device)
-        check(_lib.load().gags_entropy_fwd(s.numel(), ptr(s), ptr(acc), _st()), "gags_entropy_fwd")
+        check(_lib.load().gags_entropy_fwd(s.numel(), ptr(s), ptr(acc), _lib.stream()), "gags_entropy_fwd")
         ctx.save_for_backward(s)
         return (acc[0] / s.numel()).float()
 
@@ -99,7 +94,7 @@ class _Entropy(torch.autograd.Function):
         (s,) = ctx.saved_tensors
         vs = torch.empty_like(s)
         vd = v.detach().reshape(1).float().contiguous()  # (read on the device: no readback inside the backward pass)
-        check(_lib.load().gags_entropy_bwd_dev(s.numel(), ptr(s), ptr(vd), ptr(vs), _st()), "gags_entropy_bwd_dev")
+        check(_lib.load().gags_entropy_bwd_dev(s.numel(), ptr(s), ptr(vd), ptr(vs), _lib.stream()), "gags_entropy_bwd_dev")
         return vs
 
 
@@ -124,14 +119,14 @@ def _segment_copies(x, seg_map, n_seg, pixel_major=False):
         s2 = torch.empty_like(s1)
         cnt = torch.empty(k, n_seg, dtype=torch.int32, device=x.device)
         check(lib.gags_segment_stats_runs(n_pix, c, ptr(x), ptr(seg_map), n_seg, k, ptr(s1), ptr(s2), ptr(cnt),
-                                          1 if pixel_major else 0, _st()), "gags_segment_stats_runs")
+                                          1 if pixel_major else 0, _lib.stream()), "gags_segment_stats_runs")
         return s1, s2, cnt
     k = _STAT_COPIES if n_seg * c * _STAT_COPIES <= (1 << 22) else 1
     s1 = torch.zeros(k, n_seg, c, dtype=torch.float64, device=x.device)
     s2 = torch.zeros_like(s1)
     cnt = torch.zeros(k, n_seg, dtype=torch.int32, device=x.device)
     check(lib.gags_segment_stats_multi(n_pix, c, ptr(x), ptr(seg_map), n_seg, k, ptr(s1), ptr(s2), ptr(cnt),
-                                       1 if pixel_major else 0, _st()), "gags_segment_stats_multi")
+                                       1 if pixel_major else 0, _lib.stream()), "gags_segment_stats_multi")
     return s1, s2, cnt
 
 
@@ -155,7 +150,7 @@ def _segment_loss(mode, x, seg_map, n_seg, pixel_major=False):
     coef = torch.empty(n_seg, device=dev)
     mean = torch.empty(n_seg, c, device=dev) if mode == 1 else None
     check(_lib.load().gags_segment_loss(mode, n_seg, c, k, seg_map.numel(), ptr(s1c), ptr(s2c), ptr(cntc), ptr(s1), ptr(s2),
-                                        ptr(cnt), ptr(loss), ptr(coef), ptr(mean), _st()), "gags_segment_loss")
+                                        ptr(cnt), ptr(loss), ptr(coef), ptr(mean), _lib.stream()), "gags_segment_loss")
     return loss, coef, mean
 
 
@@ -173,7 +168,7 @@ class _ScaleBalance(torch.autograd.Function):
     def backward(ctx, v):
         seg, coef = ctx.saved_tensors
         out = torch.empty_like(seg)
-        check(_lib.load().gags_gather_seg_coef(seg.numel(), ptr(seg), ctx.n_seg, ptr((coef * v).contiguous()), ptr(out), _st()),
+        check(_lib.load().gags_gather_seg_coef(seg.numel(), ptr(seg), ctx.n_seg, ptr((coef * v).contiguous()), ptr(out), _lib.stream()),
               "gags_gather_seg_coef")
         return out, None
 
@@ -209,7 +204,7 @@ class _RegionVar(torch.autograd.Function):
         x, seg, mean, coef = ctx.saved_tensors
         vx = torch.empty_like(x)  # (pixel-major input: [H,W,C] memory, returned as the [C,H,W] view of it)
         check(_lib.load().gags_region_var_bwd_layout(seg.numel(), ctx.c, ptr(x), ptr(seg), ctx.n_seg, ptr(mean),
-                                                     ptr((coef * v).contiguous()), ptr(vx), 1 if ctx.pm else 0, _st()),
+                                                     ptr((coef * v).contiguous()), ptr(vx), 1 if ctx.pm else 0, _lib.stream()),
               "gags_region_var_bwd_layout")
         return (vx.permute(2, 0, 1) if ctx.pm else vx), None
 
@@ -236,7 +231,7 @@ class _RegionVarTee(torch.autograd.Function):
             return vx + g_next, None
         vx = torch.empty_like(x)
         check(_lib.load().gags_region_var_bwd_add(seg.numel(), ctx.c, ptr(x), ptr(seg), ctx.n_seg, ptr(mean),
-                                                  ptr((coef * v).contiguous()), ptr(gp), ptr(vx), _st()), "gags_region_var_bwd_add")
+                                                  ptr((coef * v).contiguous()), ptr(gp), ptr(vx), _lib.stream()), "gags_region_var_bwd_add")
         return vx.permute(2, 0, 1), None
 
 
@@ -261,7 +256,7 @@ def get_trained_seg(seg_map, scale_map, n_seg=None):
     seg, sc = _f(seg_map), _f(scale_map.detach())
     _, h, w = seg.shape
     out = torch.empty(h, w, device=seg.device)
-    check(_lib.load().gags_trained_seg(h, w, ptr(seg), ptr(sc), ptr(out), _st()), "gags_trained_seg")
+    check(_lib.load().gags_trained_seg(h, w, ptr(seg), ptr(sc), ptr(out), _lib.stream()), "gags_trained_seg")
     out._gags_n_seg = _n_seg(seg_map) if n_seg is None else max(int(n_seg), 1)  # (every id of the result is an id of seg_map)
     return out
 
@@ -274,7 +269,7 @@ class _SamFeature(torch.autograd.Function):
         feat = torch.empty(c, H, W, device=e.device)
         mask = torch.empty(H, W, device=e.device)
         check(_lib.load().gags_sam_clip_feature(c, H, W, h, w, e.shape[0], ptr(e), ptr(seg), ptr(sc), ptr(feat), ptr(mask),
-                                                _st()), "gags_sam_clip_feature")
+                                                _lib.stream()), "gags_sam_clip_feature")
         ctx.save_for_backward(e, seg)
         ctx.dims = (c, H, W, h, w)
         ctx.mark_non_differentiable(mask)
@@ -286,7 +281,7 @@ class _SamFeature(torch.autograd.Function):
         c, H, W, h, w = ctx.dims
         vs = torch.empty(3, H, W, device=e.device)
         check(_lib.load().gags_sam_clip_feature_bwd_scale(c, H, W, h, w, e.shape[0], ptr(e), ptr(seg), ptr(_f(v_feat)), ptr(vs),
-                                                          _st()), "gags_sam_clip_feature_bwd_scale")
+                                                          _lib.stream()), "gags_sam_clip_feature_bwd_scale")
         return None, None, vs
 
 
@@ -304,7 +299,7 @@ def read_sam_clip_feature(img_embed, seg_map, scale_map, max_mode=False, median_
             feat = torch.empty(c, H, W, device=e.device)
             mask = torch.empty(H, W, device=e.device)
             check(_lib.load().gags_sam_clip_feature_max(c, H, W, h, w, e.shape[0], ptr(e), ptr(seg), ptr(sc), ptr(feat),
-                                                        ptr(mask), _st()), "gags_sam_clip_feature_max")
+                                                        ptr(mask), _lib.stream()), "gags_sam_clip_feature_max")
         return feat, (mask != 0)[None]
     feat, mask = _SamFeature.apply(img_embed, seg_map, scale_map)
     return feat, (mask != 0)[None]
@@ -329,7 +324,7 @@ class _DistillL1(torch.autograd.Function):
         l1 = torch.empty(H, W, device=p.device)
         mask = torch.empty(H, W, device=p.device)
         check(_lib.load().gags_distill_l1_map_fwd(c, H, W, h, w, e.shape[0], ptr(p), ptr(e), ptr(seg), ptr(sc), ptr(l1),
-                                                  ptr(mask), 1 if pm else 0, _st()), "gags_distill_l1_map_fwd")
+                                                  ptr(mask), 1 if pm else 0, _lib.stream()), "gags_distill_l1_map_fwd")
         ctx.save_for_backward(p, e, seg, sc)
         ctx.dims = (c, H, W, h, w)
         ctx.pm = pm
@@ -344,7 +339,7 @@ class _DistillL1(torch.autograd.Function):
         vp = torch.empty(H, W, c, device=p.device).permute(2, 0, 1) if ctx.pm else torch.empty_like(p)
         vs = torch.empty(3, H, W, device=p.device)
         check(_lib.load().gags_distill_l1_map_bwd(c, H, W, h, w, e.shape[0], ptr(p), ptr(e), ptr(seg), ptr(sc), ptr(_f(v_map)),
-                                                  ptr(vp), ptr(vs), 1 if ctx.pm else 0, _st()), "gags_distill_l1_map_bwd")
+                                                  ptr(vp), ptr(vs), 1 if ctx.pm else 0, _lib.stream()), "gags_distill_l1_map_bwd")
         return vp, None, None, vs
 
 
@@ -371,8 +366,7 @@ def _photo_view(t):
     """(tensor, planes, images, h, w, element strides of plane / row / column) of a [C,H,W] or [B,C,H,W] float32 GPU tensor
     read where it lies: the planes must be equally spaced (a contiguous tensor, or the [C,H,W] view of the rasterizer's
     [H,W,C] memory); anything else is copied once."""
-    if not t.is_cuda:
-        raise RuntimeError("gags_amd.losses: tensors must live on the GPU (there is no CPU path)")
+    _lib.on_gpu("losses", t)
     if t.dim() not in (3, 4):
         raise ValueError(f"expected [C,H,W] or [B,C,H,W], got {tuple(t.shape)}")
     if t.dtype != torch.float32:
@@ -407,7 +401,7 @@ def _photo_forward(x, y, bias, wa, wb, reduce_all, need_grad):
     k = torch.empty(2, device=dev)
     dm = torch.empty(3, planes, h, w, device=dev) if need_grad else None
     check(lib.gags_photometric_fwd(planes, images, h, w, ptr(x), *xs, ptr(y), *ys, _WINDOW_C, bias, wa, wb, 1 if reduce_all else 0,
-                                   ptr(dm), None, ptr(partials), ptr(sums), ptr(out), ptr(k), _st()), "gags_photometric_fwd")
+                                   ptr(dm), None, ptr(partials), ptr(sums), ptr(out), ptr(k), _lib.stream()), "gags_photometric_fwd")
     return out, sums, k, dm, (x, xs, y, ys, planes, images, h, w)
 
 
@@ -433,7 +427,7 @@ class _Photometric(torch.autograd.Function):
         coef = (v.detach().reshape(-1, 1).float() * k).contiguous()
         vx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)  # written in x's own layout
         check(_lib.load().gags_photometric_bwd(planes, groups, h, w, ptr(x), *xs, ptr(y), *ys, _WINDOW_C, ptr(dm), ptr(coef),
-                                               ptr(vx), *xs, _st()), "gags_photometric_bwd")
+                                               ptr(vx), *xs, _lib.stream()), "gags_photometric_bwd")
         return vx, None, None, None, None, None
 
 

@@ -15,7 +15,6 @@ runs as a Python loop with one KD-tree ball query per point, as one grid + radix
 
 The distance rule is scipy's for three coordinates: ((dx*dx + dy*dy) + dz*dz) <= r*r in float64 from the float32
 coordinates.  The Open3D windows and mask_color="rel" (a matplotlib colormap) are out of scope."""
-import ctypes
 import os
 
 import numpy as np
@@ -29,23 +28,13 @@ C0 = 0.28209479177387814  # compute_relvancy.py:34
 MASK_RED = (1.0, 0.1, 0.05)  # mask_color="default" (:377)
 
 
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _on_gpu(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("gags_amd.pointquery: tensors must live on the GPU (there is no CPU path)")
-
-
 @torch.no_grad()
 def smooth_point_mask(mask, xyz, radius=0.1, threshold=10, return_counts=False):
     """utils/pcd_utils.py:204-219 smooth_pcd_mask (same defaults) for mask [N] or [K, N] (bool or 0 / 1) over xyz [N, 3]
     fp32: out_i = c_i > threshold, or mask_i when 10 <= c_i <= threshold, with c_i the masked points within `radius` of
     point i (itself included).  Returns the bool mask of mask's shape; with return_counts also the int32 counts
     min(c_i, max(threshold + 1, 10))."""
-    _on_gpu(mask, xyz)
+    _lib.on_gpu("pointquery", mask, xyz)
     m = mask.reshape(1, -1) if mask.dim() == 1 else mask
     if m.dim() != 2 or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] != m.shape[1]:
         raise ValueError(f"smooth_point_mask: mask {tuple(mask.shape)} and xyz {tuple(xyz.shape)} do not match ([K,] N and [N, 3])")
@@ -56,9 +45,9 @@ def smooth_point_mask(mask, xyz, radius=0.1, threshold=10, return_counts=False):
     counts = torch.empty(k, n, dtype=torch.int32, device=p.device) if return_counts else None
     lib = _lib.load()
     nb = lib.gags_point_mask_smooth_scratch_bytes(k, n)
-    scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
+    scratch = _lib.scratch(nb, p.device)
     check(lib.gags_point_mask_smooth(k, n, ptr(p), ptr(m8), float(radius), int(threshold), ptr(out), ptr(counts),
-                                     ptr(scratch), nb, _st()), "gags_point_mask_smooth")
+                                     ptr(scratch), nb, _lib.stream()), "gags_point_mask_smooth")
     out = out.bool().reshape(mask.shape)
     return (out, counts.reshape(mask.shape)) if return_counts else out
 
@@ -66,7 +55,7 @@ def smooth_point_mask(mask, xyz, radius=0.1, threshold=10, return_counts=False):
 def _point_probs(semantic_feature, decoder, head, chunk, fused=False):
     """[n_pos, N, 2] relevancy pairs of the decoded features, `chunk` Gaussians per decoder call; fused=True: all N in one
     CNN_decoder.query call (nothing per layer is held, so nothing is chunked)."""
-    _on_gpu(semantic_feature)
+    _lib.on_gpu("pointquery", semantic_feature)
     if semantic_feature.dim() != 2:
         raise ValueError(f"semantic_feature must be [N, C], got {tuple(semantic_feature.shape)}")
     if chunk <= 0:
@@ -106,7 +95,7 @@ def query_points(semantic_feature, xyz, decoder, head, rel_thresh=0.4, radius=0.
     Returns a dict of [n_pos, N] device tensors: relevancy (fp32), normalized (clip((r - min) / (max - min + 1e-9) * 2 - 1,
     0, 1)), mask_raw (normalized > rel_thresh) and mask (after smooth_pcd_mask(mask_raw, xyz, radius, threshold)).  fused: as
     point_relevancy's."""
-    _on_gpu(semantic_feature, xyz)
+    _lib.on_gpu("pointquery", semantic_feature, xyz)
     if xyz.shape != (semantic_feature.shape[0], 3):
         raise ValueError(f"xyz must be [N, 3] with N = {semantic_feature.shape[0]}, got {tuple(xyz.shape)}")
     probs = _point_probs(semantic_feature, decoder, head, chunk, fused)
@@ -115,9 +104,9 @@ def query_points(semantic_feature, xyz, decoder, head, rel_thresh=0.4, radius=0.
     mask_raw = torch.empty(k, n, dtype=torch.uint8, device=probs.device)
     lib = _lib.load()
     nb = lib.gags_point_relevancy_mask_scratch_bytes(k, n)
-    scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=probs.device)
+    scratch = _lib.scratch(nb, probs.device)
     check(lib.gags_point_relevancy_mask(k, n, ptr(probs), float(rel_thresh), ptr(normalized), ptr(mask_raw), ptr(scratch), nb,
-                                        _st()), "gags_point_relevancy_mask")
+                                        _lib.stream()), "gags_point_relevancy_mask")
     mask = smooth_point_mask(mask_raw, xyz, radius, threshold)
     return {"relevancy": probs[..., 0].contiguous(), "normalized": normalized, "mask_raw": mask_raw.bool(), "mask": mask}
 
@@ -133,7 +122,7 @@ def recolor_dc(features_dc, mask, bg_color="mix", mask_color="default"):
                                   "only mask_color='default' (red) is supported")
     if bg_color not in ("RGB", "gray", "mix"):
         raise ValueError(f"bg_color must be 'RGB', 'gray' or 'mix', got {bg_color!r}")
-    _on_gpu(features_dc, mask)
+    _lib.on_gpu("pointquery", features_dc, mask)
     fdc = features_dc.reshape(-1, 3).double()
     m = mask.bool()
     if m.shape[-1] != fdc.shape[0]:

@@ -35,7 +35,6 @@ Two behaviours of the reference worth knowing:
     rows of `visible` with any camera), so no infinite weight is formed.
 Crops leave gaps when W % n != 0, the last row and column of a crop belong to no sub-crop, and neighbouring sub-crops may
 share a pixel: all three are the reference's geometry and are kept."""
-import ctypes
 import math
 import os
 import random
@@ -111,13 +110,8 @@ def generate_crop_boxes(im_size, n_layers, overlap_ratio):
 
 # ---- GPU: the crop statistics ---------------------------------------------------------------------------------------------------
 
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _maps(depths, samples):
-    if not depths.is_cuda or (samples is not None and not samples.is_cuda):
-        raise RuntimeError("gags_amd.prompts: tensors must live on the GPU (there is no CPU path)")
+    _lib.on_gpu("prompts", depths, *(() if samples is None else (samples,)))
     if depths.dim() != 3 or min(depths.shape) < 1:
         raise ValueError(f"depths must be a non-empty [C, H, W], got {tuple(depths.shape)}")
     if samples is not None and samples.shape != depths.shape:
@@ -147,10 +141,10 @@ def crop_stats(depths, samples=None, n_per_side=8, layout=None):
         out["sub_count"] = torch.empty(c, n * n, SUB * SUB, dtype=torch.int32, device=dev)
     lib = _lib.load()
     nb = lib.gags_promptgrid_scratch_bytes(c, h, w, n, L["crop_h"])
-    scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(nb, dev)
     check(lib.gags_promptgrid_stats(c, h, w, n, L["crop_w"], L["crop_h"], ptr(depths), ptr(samples), ptr(tab),
                                     ptr(out["depth_sum"]), ptr(out["depth_count"]), ptr(out.get("sample_sum")),
-                                    ptr(out.get("sample_count")), ptr(out.get("sub_count")), ptr(scratch), nb, _st()),
+                                    ptr(out.get("sample_count")), ptr(out.get("sub_count")), ptr(scratch), nb, _lib.stream()),
           "gags_promptgrid_stats")
     return out
 

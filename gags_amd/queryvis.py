@@ -14,7 +14,6 @@ video, without leaving the device.
 8-bit copies follow THIS project's rule, trunc(clamp(x * 255 + 0.5, 0, 255)) (featurevis._save_image); the reference writes its
 PNGs through mediapy.  GPU tensors only: there is no CPU path.  Deliberately not here: lerf_composited_whitebg and the loss
 figure (matplotlib figures), the spline camera path of --video, the CLIP text encoder."""
-import ctypes
 import os
 
 import numpy as np
@@ -29,16 +28,6 @@ _LUT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "tu
 _lut_host = None
 _luts = {}
 IMAGE_KEYS = ("heatmap", "lerf_composited", "mask_composited")
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _need_gpu(*tensors):
-    for t in tensors:
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError("gags_amd.queryvis: tensors must live on the GPU (there is no CPU path)")
 
 
 def turbo_lut_host():
@@ -73,7 +62,7 @@ def colour_maps(act, image, lut=None, box=30, avg2=None, return_uint8=False):
     Returns {heatmap, lerf_composited, mask_composited: [M, h, w, 3] float32, avg2 [M, h, w]} and, with return_uint8, the
     same three as uint8 under '<name>_u8'."""
     heat, outp, mask, stats = act["heatmap"], act["output"], act["mask"], act["stats"]
-    _need_gpu(heat, outp, mask, stats, image)
+    _lib.on_gpu("queryvis", heat, outp, mask, stats, image)
     dev = heat.device
     M, h, w = heat.shape
     heat, outp, stats = heat.float().contiguous(), outp.float().contiguous(), stats.float().contiguous()
@@ -98,16 +87,16 @@ def colour_maps(act, image, lut=None, box=30, avg2=None, return_uint8=False):
     if avg2 is None:
         avg2 = torch.empty(M, h, w, device=dev)
         nb = lib.gags_query_images_scratch_bytes(M, h, w)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+        scratch = _lib.scratch(nb, dev)
         check(lib.gags_query_images(M, F, h, w, ptr(heat), ptr(outp), ptr(mask), ptr(stats), ptr(img), ptr(lut), int(box),
-                                    ptr(avg2), *rgb, ptr(scratch), nb, _st()), "gags_query_images")
+                                    ptr(avg2), *rgb, ptr(scratch), nb, _lib.stream()), "gags_query_images")
     else:
-        _need_gpu(avg2)
+        _lib.on_gpu("queryvis", avg2)
         avg2 = avg2.float().contiguous()
         if tuple(avg2.shape) != (M, h, w):
             raise ValueError("avg2 does not fit the heat maps")
         check(lib.gags_query_colour(M, F, h, w, ptr(heat), ptr(outp), ptr(mask), ptr(avg2), ptr(stats), ptr(img), ptr(lut),
-                                    *rgb, _st()), "gags_query_colour")
+                                    *rgb, _lib.stream()), "gags_query_colour")
     out["avg2"] = avg2
     if return_uint8:
         out.update({k + "_u8": u8[k] for k in IMAGE_KEYS})
@@ -120,7 +109,7 @@ def query_images(valid_map, image, thresh=0.4, lut=None, return_uint8=False):
     view: get_max_across(sem_map).squeeze(0)) and image [h, w, 3] or [F, h, w, 3].  Returns a dict of device tensors:
     heatmap, lerf_composited, mask_composited [M, h, w, 3] float32 (what the reference writes into the folders of those names)
     and mask [M, h, w] uint8 (the final mask_pred); with return_uint8 also '<image>_u8'."""
-    _need_gpu(valid_map, image)
+    _lib.on_gpu("queryvis", valid_map, image)
     act = activate_maps(valid_map, thresh=thresh)
     out = colour_maps(act, image, lut=lut, return_uint8=return_uint8)
     del out["avg2"]
@@ -133,7 +122,7 @@ def query_view(feature_map, cnn_decoder, head, image, thresh=0.4, lut=None, retu
     """compute_relvancy.py:265-269 for one view: the rendered [16, h, w] map through the decoder, the relevancy of every phrase
     of `head` (a relevancy.RelevancyHead) and query_images.  The stages are queued on the current stream one after the other:
     nothing is read back in between."""
-    _need_gpu(feature_map, image)
+    _lib.on_gpu("queryvis", feature_map, image)
     restored = cnn_decoder(feature_map)                          # [512, h, w]
     sem_map = restored.permute(1, 2, 0).unsqueeze(0)              # [1, h, w, 512]
     valid_map = head.get_max_across(sem_map).squeeze(0)           # [n_phrases, h, w]
@@ -183,7 +172,7 @@ def feature_loss_maps(feature_map, gt_feature_map, mask, pixel_major=False):
     the sums in float64, rounded once.  The maps are [C, H, W] -- channel-major memory or a permuted view of [H, W, C] memory
     (the decoders' output), each read as it lies -- or, with pixel_major=True, given as [H, W, C].  mask: [H, W] or [1, H, W], any
     dtype, used as 0 / 1 float.  Any combination of layouts gives the same bits."""
-    _need_gpu(feature_map, gt_feature_map, mask)
+    _lib.on_gpu("queryvis", feature_map, gt_feature_map, mask)
     f, lf, C, H, W = _loss_map(feature_map, pixel_major)
     g, lg, Cg, Hg, Wg = _loss_map(gt_feature_map, pixel_major)
     if (C, H, W) != (Cg, Hg, Wg):
@@ -192,7 +181,7 @@ def feature_loss_maps(feature_map, gt_feature_map, mask, pixel_major=False):
         raise ValueError(f"mask {tuple(mask.shape)} does not fit {H} x {W} pixels")
     m = mask.reshape(H, W).float().contiguous()
     l2, mp, mg = (torch.empty(H, W, device=f.device) for _ in range(3))
-    check(_lib.load().gags_feature_loss_maps(C, H * W, ptr(f), lf, ptr(g), lg, ptr(m), ptr(l2), ptr(mp), ptr(mg), _st()),
+    check(_lib.load().gags_feature_loss_maps(C, H * W, ptr(f), lf, ptr(g), lg, ptr(m), ptr(l2), ptr(mp), ptr(mg), _lib.stream()),
           "gags_feature_loss_maps")
     return l2, mp, mg
 

@@ -12,7 +12,6 @@ phrase and level through torch.mm + stack + softmax + gather).
 min-max normalise, clip, threshold, eval/utils.py:55-64 majority filter, IoU) and :163-176 (`lerf_localization`: box
 mean, arg-max, hit test against the annotated boxes), for all phrases in one call on the GPU.  The heat-map and
 composited images built from these tensors, and their PNG files, are gags_amd/queryvis.py (N12)."""
-import ctypes
 
 import torch
 
@@ -29,14 +28,13 @@ class RelevancyHead:
         self.pos_embeds = pos_embeds.float().contiguous()
 
     def _all(self, embed):
-        if not embed.is_cuda:
-            raise RuntimeError("gags_amd.relevancy: tensors must live on the GPU (there is no CPU path)")
+        _lib.on_gpu("relevancy", embed)
         e = embed.float().contiguous()
         n_pix, c = e.shape
         out = torch.empty(self.pos_embeds.shape[0], n_pix, 2, device=e.device)
         check(_lib.load().gags_relevancy(n_pix, c, self.pos_embeds.shape[0], self.neg_embeds.shape[0], ptr(e),
                                          ptr(self.pos_embeds), ptr(self.neg_embeds), ptr(out),
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gags_relevancy")
+                                         _lib.stream()), "gags_relevancy")
         return out
 
     @torch.no_grad()
@@ -57,8 +55,7 @@ def activate_maps(valid_map, thresh=0.5, box=30, smooth_scale=3):
     valid_map[k] and saves), output (normalised to [-1, 1], clipped to [0, 1]), mask_pred (output > thresh, uint8),
     mask (after the majority filter: the reference's final `mask_pred`), stats [n_phrases, 3] = (min, max of the heat
     map, max of avg)."""
-    if not valid_map.is_cuda:
-        raise RuntimeError("gags_amd.relevancy: tensors must live on the GPU (there is no CPU path)")
+    _lib.on_gpu("relevancy", valid_map)
     v = valid_map.float().contiguous()
     k, h, w = v.shape
     lib = _lib.load()
@@ -68,10 +65,10 @@ def activate_maps(valid_map, thresh=0.5, box=30, smooth_scale=3):
     mask = torch.empty_like(mask_pred)
     stats = torch.empty(k, 3, device=dev)
     nb = lib.gags_relevancy_activate_scratch_bytes(k, h, w)
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(nb, dev)
     check(lib.gags_relevancy_activate(k, h, w, ptr(v), float(thresh), int(box), int(smooth_scale), ptr(avg), ptr(heat),
                                       ptr(outp), ptr(mask_pred), ptr(mask), ptr(stats), ptr(scratch), nb,
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gags_relevancy_activate")
+                                      _lib.stream()), "gags_relevancy_activate")
     return {"avg": avg, "heatmap": heat, "output": outp, "mask_pred": mask_pred, "mask": mask, "stats": stats}
 
 

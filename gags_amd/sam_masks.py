@@ -23,23 +23,12 @@ Deviations from the reference, all deliberate:
   min_mask_region_area never emits one).  The kernels themselves tolerate such a mask.
 * Empty levels.  A level without masks yields no indices, a map of -1 and length 0; the reference cannot represent this.
 * Score ties.  The reference's unstable sort leaves their order unspecified; here the lower index comes first."""
-import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _on_gpu(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("gags_amd.sam_masks: tensors must live on the GPU (there is no CPU path)")
 
 
 def max_masks():
@@ -54,7 +43,7 @@ def pair_chunk_words():
 
 def _bytes(masks):
     """[M, H, W] bool / uint8 -> contiguous uint8 view (a bool tensor stores one byte per element)."""
-    _on_gpu(masks)
+    _lib.on_gpu("sam_masks", masks)
     if masks.dim() != 3:
         raise ValueError(f"masks must be [M, H, W], got {tuple(masks.shape)}")
     if masks.dtype not in (torch.bool, torch.uint8):
@@ -72,12 +61,12 @@ def pack_masks(masks):
     M, hw = m8.shape[0], m8.shape[1] * m8.shape[2]
     bits = torch.empty(M, (hw + 63) // 64, dtype=torch.int64, device=m8.device)
     area = torch.empty(M, dtype=torch.int32, device=m8.device)
-    check(_lib.load().gags_masks_pack(M, hw, ptr(m8), ptr(bits), ptr(area), _st()), "gags_masks_pack")
+    check(_lib.load().gags_masks_pack(M, hw, ptr(m8), ptr(bits), ptr(area), _lib.stream()), "gags_masks_pack")
     return bits, area
 
 
 def _bits(bits):
-    _on_gpu(bits)
+    _lib.on_gpu("sam_masks", bits)
     if bits.dim() != 2 or bits.dtype != torch.int64 or bits.shape[1] < 1:
         raise ValueError(f"bits must be [M, nw] int64 with nw >= 1, got {tuple(bits.shape)} {bits.dtype}")
     return bits.contiguous()
@@ -89,7 +78,7 @@ def pair_intersections(bits):
     bits = _bits(bits)
     M, nw = bits.shape
     inter = torch.empty(M, M, dtype=torch.int32, device=bits.device)
-    check(_lib.load().gags_masks_pairs(M, nw * 64 - 63, ptr(bits), ptr(inter), _st()), "gags_masks_pairs")
+    check(_lib.load().gags_masks_pairs(M, nw * 64 - 63, ptr(bits), ptr(inter), _lib.stream()), "gags_masks_pairs")
     return inter
 
 
@@ -97,14 +86,14 @@ def pair_intersections(bits):
 def column_maxima(inter, area, order):
     """colmax [3, M] fp32 (include/gags_next.h N10) from inter [M, M] int32, area [M] int32 and order [M] (mask indices by
     descending score)."""
-    _on_gpu(inter, area, order)
+    _lib.on_gpu("sam_masks", inter, area, order)
     M = area.shape[0]
     if tuple(inter.shape) != (M, M) or tuple(order.shape) != (M,):
         raise ValueError(f"inter {tuple(inter.shape)}, area {tuple(area.shape)} and order {tuple(order.shape)} disagree")
     inter, area = inter.to(torch.int32).contiguous(), area.to(torch.int32).contiguous()
     order = order.to(torch.int32).contiguous()
     colmax = torch.empty(3, M, dtype=torch.float32, device=area.device)
-    check(_lib.load().gags_masks_colmax(M, ptr(inter), ptr(area), ptr(order), ptr(colmax), _st()), "gags_masks_colmax")
+    check(_lib.load().gags_masks_colmax(M, ptr(inter), ptr(area), ptr(order), ptr(colmax), _lib.stream()), "gags_masks_colmax")
     return colmax
 
 
@@ -112,7 +101,7 @@ def _nms_device(masks, scores, iou_thr, score_thr, inner_thr):
     """Everything of mask_nms that stays on the device: (idx [M] int64 by descending score, keep [M] bool over ranks,
     the four keep vectors [4, M] before the final AND, any_zero_area 0-dim bool)."""
     m8 = _bytes(masks)
-    _on_gpu(scores)
+    _lib.on_gpu("sam_masks", scores)
     M, hw = m8.shape[0], m8.shape[1] * m8.shape[2]
     if tuple(scores.shape) != (M,):
         raise ValueError(f"scores must be [{M}], got {tuple(scores.shape)}")
@@ -123,8 +112,8 @@ def _nms_device(masks, scores, iou_thr, score_thr, inner_thr):
     colmax = torch.empty(3, M, dtype=torch.float32, device=dev)
     lib = _lib.load()
     nb = lib.gags_masks_nms_scratch_bytes(M, hw)
-    scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    check(lib.gags_masks_nms_colmax(M, hw, ptr(m8), ptr(order), ptr(area), ptr(colmax), ptr(scratch), nb, _st()),
+    scratch = _lib.scratch(nb, dev)
+    check(lib.gags_masks_nms_colmax(M, hw, ptr(m8), ptr(order), ptr(area), ptr(colmax), ptr(scratch), nb, _lib.stream()),
           "gags_masks_nms_colmax")
     top3 = torch.arange(M, device=dev) < 3
     keeps = torch.stack([colmax[0] <= iou_thr, s_sorted > score_thr,
@@ -182,7 +171,7 @@ def seg_map(bits, kept, H, W, offset=0):
     """[H, W] int32: offset + the largest k whose mask kept[k] covers the pixel ("later paint wins", mask2segmap), -1 where
     none does.  bits [M, nw] from pack_masks, kept [K] ascending mask indices (any integer dtype; K may be 0)."""
     bits = _bits(bits)
-    _on_gpu(kept)
+    _lib.on_gpu("sam_masks", kept)
     M, nw = bits.shape
     hw = int(H) * int(W)
     if (hw + 63) // 64 != nw:
@@ -191,7 +180,7 @@ def seg_map(bits, kept, H, W, offset=0):
         raise ValueError(f"kept must be [K], got {tuple(kept.shape)}")
     kept = kept.to(torch.int32).contiguous()
     seg = torch.empty(int(H), int(W), dtype=torch.int32, device=bits.device)
-    check(_lib.load().gags_masks_paint(M, hw, ptr(bits), kept.shape[0], ptr(kept), int(offset), ptr(seg), _st()),
+    check(_lib.load().gags_masks_paint(M, hw, ptr(bits), kept.shape[0], ptr(kept), int(offset), ptr(seg), _lib.stream()),
           "gags_masks_paint")
     return seg
 

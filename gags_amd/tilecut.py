@@ -24,7 +24,6 @@ Deviations from the reference, all deliberate:
   KeyError there (seg_images has no such key).
 * Channel order.  The reference converts the whole image once (COLOR_BGR2RGB, :465); bgr=True reads the channels in reverse
   per tap instead, which is the same values."""
-import ctypes
 
 import numpy as np
 import torch
@@ -35,23 +34,13 @@ from ._lib import check, ptr
 LEVELS = ("default", "s", "m", "l")   # the order of the rows of <image>_f.npy (preprocess.py:303, :344)
 
 
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _on_gpu(*ts):
-    for t in ts:
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError("gags_amd.tilecut: tensors must live on the GPU (there is no CPU path)")
-
-
 def side():
     """The tile side, 224 (CLIP's input size)."""
     return int(_lib.load().gags_tilecut_side())
 
 
 def _check_bits(bits, H, W):
-    _on_gpu(bits)
+    _lib.on_gpu("tilecut", bits)
     nw = (int(H) * int(W) + 63) // 64
     if bits.dim() != 2 or bits.dtype != torch.int64 or bits.shape[1] != nw:
         raise ValueError(f"bits must be [M, {nw}] int64 for {H} x {W} pixels, got {tuple(bits.shape)} {bits.dtype}")
@@ -66,7 +55,7 @@ def mask_boxes(bits, H, W):
         raise ValueError(f"the image must have at least one pixel, got {H} x {W}")
     bits = _check_bits(bits, H, W)
     boxes = torch.empty(bits.shape[0], 4, dtype=torch.int32, device=bits.device)
-    check(_lib.load().gags_tilecut_boxes(bits.shape[0], int(H), int(W), ptr(bits), ptr(boxes), _st()), "gags_tilecut_boxes")
+    check(_lib.load().gags_tilecut_boxes(bits.shape[0], int(H), int(W), ptr(bits), ptr(boxes), _lib.stream()), "gags_tilecut_boxes")
     return boxes
 
 
@@ -119,7 +108,7 @@ def cut_tiles(image, bits, boxes, index=None, bgr=False, dtype=torch.float32):
     if dtype not in (torch.float32, torch.uint8, None):
         raise ValueError(f"dtype must be torch.float32, torch.uint8 or None (both), got {dtype}")
     b = _host_boxes(boxes, H, W)
-    _on_gpu(image)
+    _lib.on_gpu("tilecut", image)
     bits = _check_bits(bits, H, W)
     M, dev = bits.shape[0], image.device
     K = b.shape[0]
@@ -142,7 +131,7 @@ def cut_tiles(image, bits, boxes, index=None, bgr=False, dtype=torch.float32):
         image = image.contiguous()
         dboxes = torch.from_numpy(np.ascontiguousarray(b, np.int32)).to(dev)   # (b may come in any memory order: row-major here)
         check(_lib.load().gags_tilecut(K, H, W, ptr(image), int(bool(bgr)), M, ptr(bits), ptr(idx), ptr(dboxes),
-                                       ptr(u8), ptr(f32), _st()), "gags_tilecut")
+                                       ptr(u8), ptr(f32), _lib.stream()), "gags_tilecut")
     return (u8, f32) if dtype is None else (u8 if dtype == torch.uint8 else f32)
 
 
@@ -165,7 +154,7 @@ def _level(lvl, H, W, dev):
 
 
 def _levels(image, levels):
-    _on_gpu(image)
+    _lib.on_gpu("tilecut", image)
     levels = list(levels)
     if len(levels) != len(LEVELS):
         raise ValueError(f"levels must be the four kept levels {LEVELS}, got {len(levels)}")

@@ -81,7 +81,7 @@ def main():
 
             def scatter():
                 DS.check(lib.gags_depthsample_scatter(n, c, h, w, DS.ptr(xyz), DS.ptr(vm), DS.ptr(K), DS.ptr(depths), 0.25,
-                                                      0, DS.ptr(md), DS.ptr(samples), DS.ptr(scratch), nb, DS._st()),
+                                                      0, DS.ptr(md), DS.ptr(samples), DS.ptr(scratch), nb, DS._lib.stream()),
                          "scatter")
             t_scatter = timed(scatter, args.reps)
             row = {"n": n, "cams": c, "render_ms": t_render, "map_ms": t_map, "scatter_ms": t_scatter}

@@ -73,7 +73,7 @@ def main():
 
             def normalise():
                 PQ.check(lib.gags_point_relevancy_mask(3, n, PQ.ptr(probs), 0.4, PQ.ptr(nrm), PQ.ptr(mraw), PQ.ptr(scratch), nb,
-                                                       PQ._st()), "gags_point_relevancy_mask")
+                                                       PQ._lib.stream()), "gags_point_relevancy_mask")
             run["normalise"], _ = timed(normalise, args.reps)
             run["query_total_r0.05"], _ = timed(lambda: PQ.query_points(sem, xyz, dec, head), max(1, args.reps // 2))
         votes = []
