@@ -31,6 +31,17 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_project_bwd_raw": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp]),
+    # N16: rasterize_mode "antialiased" (one more output / cotangent: the compensations) and absgrad
+    "gags_project_fwd_aa": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_project_bwd_aa": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp]),
+    "gags_project_fwd_raw_aa": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_project_bwd_raw_aa": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp]),
+    "gags_raster_bwd_abs": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "gags_scan_scratch_bytes": (_i64, [_i32]),
     "gags_cumsum_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_cumsum_gather_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -227,6 +238,7 @@ class GatherDesc(ctypes.Structure):
 
 
 GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instructions (what GAGS_BWD_F32MFMA asks of that kernel)
+GAGS_GEOM_ABSGRAD = 64  # `flags` of gags_raster_bwd_geom: columns 6, 7 of v_geo carry absgrad (rasterization(absgrad=True))
 
 _lib = None
 

@@ -146,7 +146,21 @@ extern "C" int gags_raster_bwd(int d, int width, int height, const float *means2
                                const float *v_render_colors, const float *v_render_alphas, float *v_colors,
                                float *v_opacities, float *v_means2d, float *v_conics, int flags, void *stream)
 {
+    return gags_raster_bwd_abs(d, width, height, means2d, conics, opacities, colors, backgrounds, isect_offsets, flatten_ids,
+                               n_isects, packed, render_alphas, last_ids, v_render_colors, v_render_alphas, v_colors, v_opacities,
+                               v_means2d, v_conics, nullptr, flags, stream);
+}
+
+extern "C" int gags_raster_bwd_abs(int d, int width, int height, const float *means2d, const float *conics,
+                                   const float *opacities, const float *colors, const float *backgrounds,
+                                   const int32_t *isect_offsets, const int32_t *flatten_ids, int64_t n_isects,
+                                   const void *packed, const float *render_alphas, const int32_t *last_ids,
+                                   const float *v_render_colors, const float *v_render_alphas, float *v_colors,
+                                   float *v_opacities, float *v_means2d, float *v_conics, float *v_means2d_abs, int flags,
+                                   void *stream)
+{
     if (d <= 0 || width <= 0 || height <= 0 || !isects_ok(n_isects, width, height)) return GAGS_EINVAL;
+    if (v_means2d_abs && (d > 32 || (flags & GAGS_BWD_COLORS_ONLY))) return GAGS_EINVAL;
     if (n_isects == 0) return GAGS_OK;
     if (!means2d || !conics || !opacities || !colors || !isect_offsets || !flatten_ids || !render_alphas ||
         !last_ids || !v_render_colors || !v_colors)
@@ -162,7 +176,7 @@ extern "C" int gags_raster_bwd(int d, int width, int height, const float *means2
     return gags_raster_bwd_valu(d, width, height, means2d, conics, opacities, colors, backgrounds, isect_offsets,
                                 flatten_ids, (int)n_isects, render_alphas, last_ids, v_render_colors,
                                 v_render_alphas, v_colors, v_opacities, v_means2d, v_conics, geom,
-                                (hipStream_t)stream);
+                                (hipStream_t)stream, v_means2d_abs);
 }
 
 extern "C" int64_t gags_bwd_staged_scratch_bytes(int64_t rows, int n, int d)
@@ -237,7 +251,8 @@ extern "C" int gags_raster_bwd_geom(int d, int n, int width, int height, const f
     return gags_raster_bwd_geom_launch(d, n, width, height, colors, backgrounds, isect_offsets, (int)n_isects, packed,
                                        v_render_colors, v_render_alphas, blk_rows, L.wt, L.gid, L.sidx, L.tbuf, scratch,
                                        scratch_bytes, v_geo, (flags & GAGS_RECS_BY_GAUSSIAN) ? 1 : 0, row_base, n_rows, L.hit,
-                                       flatten_ids, (flags & GAGS_GEOM_F32MFMA) ? 1 : 0, (hipStream_t)stream);
+                                       flatten_ids, (flags & GAGS_GEOM_F32MFMA) ? 1 : 0, (flags & GAGS_GEOM_ABSGRAD) ? 1 : 0,
+                                       (hipStream_t)stream);
 }
 
 extern "C" int gags_blended_mask(int64_t n_isects, int width, int height, int n, const int32_t *flatten_ids,

@@ -74,7 +74,7 @@ int gags_raster_bwd_valu(int d, int width, int height, const float *means2d, con
                          const float *opacities, const float *colors, const float *backgrounds,
                          const int32_t *offsets, const int32_t *flat, int n_isects, const float *alphas,
                          const int32_t *last_ids, const float *v_out, const float *v_alpha, float *v_colors,
-                         float *v_opac, float *v_m2d, float *v_con, bool geom, hipStream_t st);
+                         float *v_opac, float *v_m2d, float *v_con, bool geom, hipStream_t st, float *v_m2d_abs = nullptr);
 
 // ---- raster_weights.hip -----------------------------------------------------------------------------------------------
 int gags_pack_isects_launch(int n, int n_isects, const int32_t *flat, const float *means2d, const float *conics,
@@ -134,7 +134,7 @@ int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const
                                 const float *v_alphas, const int32_t *blk_rows, const float *wt, const int32_t *gid_s,
                                 const int32_t *sidx_s, const float *Tbuf, void *scratch, int64_t scratch_bytes, float *v_geo,
                                 int by_gauss, const int32_t *row_base, int64_t n_rows, const int32_t *hit,
-                                const int32_t *flatten_ids, int f32mfma, hipStream_t st);
+                                const int32_t *flatten_ids, int f32mfma, int absgrad, hipStream_t st);
 int gags_blended_mask_launch(int n_isects, const int32_t *hit, const int32_t *flatten_ids, unsigned char *mask, hipStream_t st);
 
 // ---- raster_bwd_atomic.hip: single-kernel colours backward ------------------------------------------------------------

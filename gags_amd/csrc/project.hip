@@ -37,7 +37,10 @@ __device__ __forceinline__ float gags_act_opacity(float o) { return 1.0f / (1.0f
 // RAW: quats / scales are the stored parameters (_rotation un-normalised, _scaling in log space) and the kernel applies
 // the getters itself (gags_project_fwd_raw); the activated opacity -- and, for a later backward, the activated quats and
 // scales when asked for -- are written on the way.
-template <bool RAW>
+// AA (rasterize_mode "antialiased", include/gags_raster.h): compensations[i] = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))),
+// 0 for a culled Gaussian; RAW folds it into the activated opacity and the record.  Nothing else changes: the blurred
+// covariance still decides radius, conic and tile count.
+template <bool RAW, bool AA>
 __global__ __launch_bounds__(256) void project_fwd_kernel(
     int n, const float *__restrict__ means, const float *__restrict__ quats,
     const float *__restrict__ scales, const float *__restrict__ viewmat, const float *__restrict__ Kmat,
@@ -46,7 +49,8 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     int32_t *__restrict__ radii, float *__restrict__ means2d, float *__restrict__ depths,
     float *__restrict__ conics, int32_t *__restrict__ tiles_per_gauss,
     const float *__restrict__ opacity_logits, float scaling_modifier, float *__restrict__ opacities_out,
-    float *__restrict__ quats_out, float *__restrict__ scales_out, gags_mfma::GRec *__restrict__ grec_out)
+    float *__restrict__ quats_out, float *__restrict__ scales_out, gags_mfma::GRec *__restrict__ grec_out,
+    float *__restrict__ compensations)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
         q = gags_act_rotation(q);
         s0 = gags_act_scaling(s0, scaling_modifier); s1 = gags_act_scaling(s1, scaling_modifier); s2 = gags_act_scaling(s2, scaling_modifier);
         opac = gags_act_opacity(opacity_logits[i]);
-        opacities_out[i] = opac;
+        if constexpr (!AA) opacities_out[i] = opac;
         if (quats_out) reinterpret_cast<float4 *>(quats_out)[i] = q;
         if (scales_out) { scales_out[3 * i] = s0; scales_out[3 * i + 1] = s1; scales_out[3 * i + 2] = s2; }
     }
@@ -72,6 +76,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
 
     int32_t o_rad = 0, o_tiles = 0;
     float o_mx = 0.f, o_my = 0.f, o_z = 0.f, o_a = 0.f, o_b = 0.f, o_c = 0.f;
+    float o_comp = 0.f;
 
     const float px = means[3 * i], py = means[3 * i + 1], pz = means[3 * i + 2];
     const float x = ((c.R00 * px + c.R01 * py) + c.R02 * pz) + c.t0;
@@ -129,6 +134,8 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
         const float m2x = c.fx * x * rz + c.cx;
         const float m2y = c.fy * y * rz + c.cy;
 
+        float det_o = 0.f;  // (AA: the determinant before the blur)
+        if constexpr (AA) det_o = s00 * s11 - s01 * s01;
         s00 += eps2d; s11 += eps2d;
         const float det = s00 * s11 - s01 * s01;
         if (det > 0.f) {
@@ -145,6 +152,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
                 int x0, x1, y0, y1;
                 gags_tile_aabb(m2x, m2y, o_rad, tile_w, tile_h, x0, x1, y0, y1);
                 o_tiles = (y1 - y0) * (x1 - x0);
+                if constexpr (AA) o_comp = sqrtf(fmaxf(0.f, det_o / det));
             }
         }
     }
@@ -153,11 +161,42 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     depths[i] = o_z;
     conics[3 * i] = o_a; conics[3 * i + 1] = o_b; conics[3 * i + 2] = o_c;
     tiles_per_gauss[i] = o_tiles;
+    if constexpr (AA) {
+        compensations[i] = o_comp;
+        if constexpr (RAW) { opac = opac * o_comp; opacities_out[i] = opac; }
+    }
     // K8b on the way (the activated opacity is at hand here): the per-Gaussian record of the matrix-core raster kernels
     // (gags_pack_isects with packed = NULL writes the same bytes from the arrays above)
     if constexpr (RAW) {
         if (grec_out && o_rad > 0) grec_out[i] = gags_mfma::make_grec_from(o_mx, o_my, o_a, o_b, o_c, opac);
     }
+}
+
+}  // namespace
+
+namespace {
+
+template <bool RAW, bool AA>
+int project_fwd_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
+                       float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
+                       float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d, float *depths,
+                       float *conics, int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
+                       void *grec, float *compensations, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
+    if (n == 0) return GAGS_OK;
+    if (!means || !quats || !scales || !viewmat || !K || !radii || !means2d || !depths || !conics || !tiles_per_gauss)
+        return GAGS_EINVAL;
+    if (RAW && (!opacity_logit || !opacities)) return GAGS_EINVAL;
+    if (AA && !compensations) return GAGS_EINVAL;
+    const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
+    hipLaunchKernelGGL((project_fwd_kernel<RAW, AA>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
+                       quats, scales, viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip,
+                       tile_w, tile_h, radii, means2d, depths, conics, tiles_per_gauss, opacity_logit, scaling_modifier,
+                       opacities, quats_act, scales_act, reinterpret_cast<gags_mfma::GRec *>(grec), compensations);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
 }
 
 }  // namespace
@@ -168,18 +207,20 @@ extern "C" int gags_project_fwd(int n, const float *means, const float *quats, c
                                 int32_t *radii, float *means2d, float *depths, float *conics,
                                 int32_t *tiles_per_gauss, void *stream)
 {
-    GAGS_CLEAR_ERR();
-    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
-    if (n == 0) return GAGS_OK;
-    if (!means || !quats || !scales || !viewmat || !K || !radii || !means2d || !depths || !conics ||
-        !tiles_per_gauss)
-        return GAGS_EINVAL;
-    const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    hipLaunchKernelGGL(project_fwd_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
-                       quats, scales, viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip,
-                       tile_w, tile_h, radii, means2d, depths, conics, tiles_per_gauss, nullptr, 1.0f, nullptr, nullptr, nullptr, nullptr);
-    GAGS_CHECK_LAUNCH();
-    return GAGS_OK;
+    return project_fwd_launch<false, false>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, near_plane,
+                                            far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int gags_project_fwd_aa(int n, const float *means, const float *quats, const float *scales,
+                                   const float *viewmat, const float *K, int width, int height,
+                                   float eps2d, float near_plane, float far_plane, float radius_clip,
+                                   int32_t *radii, float *means2d, float *depths, float *conics,
+                                   int32_t *tiles_per_gauss, float *compensations, void *stream)
+{
+    return project_fwd_launch<false, true>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, near_plane,
+                                           far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr,
+                                           nullptr, nullptr, nullptr, compensations, stream);
 }
 
 extern "C" int gags_project_fwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
@@ -189,19 +230,21 @@ extern "C" int gags_project_fwd_raw(int n, const float *means, const float *rota
                                     int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
                                     void *grec, void *stream)
 {
-    GAGS_CLEAR_ERR();
-    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
-    if (n == 0) return GAGS_OK;
-    if (!means || !rotation || !scaling_log || !opacity_logit || !viewmat || !K || !radii || !means2d || !depths ||
-        !conics || !tiles_per_gauss || !opacities)
-        return GAGS_EINVAL;
-    const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    hipLaunchKernelGGL(project_fwd_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
-                       rotation, scaling_log, viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip,
-                       tile_w, tile_h, radii, means2d, depths, conics, tiles_per_gauss, opacity_logit, scaling_modifier,
-                       opacities, quats_act, scales_act, reinterpret_cast<gags_mfma::GRec *>(grec));
-    GAGS_CHECK_LAUNCH();
-    return GAGS_OK;
+    return project_fwd_launch<true, false>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
+                                           height, eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths, conics,
+                                           tiles_per_gauss, opacities, quats_act, scales_act, grec, nullptr, stream);
+}
+
+extern "C" int gags_project_fwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
+                                       const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                                       int width, int height, float eps2d, float near_plane, float far_plane,
+                                       float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics,
+                                       int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
+                                       void *grec, float *compensations, void *stream)
+{
+    return project_fwd_launch<true, true>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
+                                          height, eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths, conics,
+                                          tiles_per_gauss, opacities, quats_act, scales_act, grec, compensations, stream);
 }
 
 namespace {
@@ -211,18 +254,24 @@ namespace {
 // forward's), and the gradients are taken one step further, to the stored parameters: d/d _scaling = v_s * exp(_scaling) *
 // modifier, d/d _rotation through q / max(|q|, 1e-12), d/d _opacity = v_o * o (1 - o) for EVERY Gaussian (the opacity's
 // gradient comes from the rasterizer, not from the projection, so it is not gated by radii).
-template <bool RAW>
+// AA: the exact derivative of comp = sqrt(max(0, r)), r = det(cov2d) / det(cov2d + eps2d I), joins the covariance cotangent
+// (include/gags_raster.h has the three partials).  Its cotangent is v_compensations (may be NULL), or in RAW
+// v_opacities * sigmoid(logit) -- v_opacities then being the cotangent of the COMPENSATED opacity, so that the logit's
+// gradient carries the factor comp (0 for a culled Gaussian).
+template <bool RAW, bool AA>
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     int N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmat, const float *__restrict__ Kmat, int width, int height, float eps2d,
     const int32_t *__restrict__ radii, const float *__restrict__ v_means2d, const float *__restrict__ v_depths,
     const float *__restrict__ v_conics, float *__restrict__ v_means, float *__restrict__ v_quats,
     float *__restrict__ v_scales, const float *__restrict__ opacity_logits, float scaling_modifier,
-    const float *__restrict__ v_opacities, float *__restrict__ v_opacity_logits)
+    const float *__restrict__ v_opacities, float *__restrict__ v_opacity_logits, const float *__restrict__ v_compensations)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    if constexpr (RAW) {
+    if constexpr (RAW && AA) {
+        if (v_opacity_logits) v_opacity_logits[i] = 0.f;  // (rewritten below, with comp, for the Gaussians on screen)
+    } else if constexpr (RAW) {
         if (v_opacity_logits) {
             const float o = gags_act_opacity(opacity_logits[i]);
             v_opacity_logits[i] = v_opacities ? (v_opacities[i] * (1.0f - o)) * o : 0.f;  // (torch: grad * (1 - y) * y)
@@ -278,9 +327,10 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         float B[2][3];
         _Pragma("unroll") for (int r = 0; r < 2; ++r) _Pragma("unroll") for (int c = 0; c < 3; ++c)
             B[r][c] = (J[r][0] * Sc[0][c] + J[r][1] * Sc[1][c]) + J[r][2] * Sc[2][c];
-        const float s00 = ((B[0][0] * J[0][0] + B[0][1] * J[0][1]) + B[0][2] * J[0][2]) + eps2d;
+        const float s00o = (B[0][0] * J[0][0] + B[0][1] * J[0][1]) + B[0][2] * J[0][2];
         const float s01 = (B[0][0] * J[1][0] + B[0][1] * J[1][1]) + B[0][2] * J[1][2];
-        const float s11 = ((B[1][0] * J[1][0] + B[1][1] * J[1][1]) + B[1][2] * J[1][2]) + eps2d;
+        const float s11o = (B[1][0] * J[1][0] + B[1][1] * J[1][1]) + B[1][2] * J[1][2];
+        const float s00 = s00o + eps2d, s11 = s11o + eps2d;
         const float det = s00 * s11 - s01 * s01;
         const float inv_det = 1.f / det;
         const float ca = s11 * inv_det, cb = -s01 * inv_det, cc = s00 * inv_det;
@@ -288,8 +338,27 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         const float va = v_conics[3 * i], vb = 0.5f * v_conics[3 * i + 1], vc = v_conics[3 * i + 2];
         const float t00 = ca * va + cb * vb, t01 = ca * vb + cb * vc;
         const float t10 = cb * va + cc * vb, t11 = cb * vb + cc * vc;
-        const float G00 = -(t00 * ca + t01 * cb), G01 = -(t00 * cb + t01 * cc);
-        const float G10 = -(t10 * ca + t11 * cb), G11 = -(t10 * cb + t11 * cc);
+        float G00 = -(t00 * ca + t01 * cb), G01 = -(t00 * cb + t01 * cc);
+        float G10 = -(t10 * ca + t11 * cb), G11 = -(t10 * cb + t11 * cc);
+        if constexpr (AA) {
+            const float r = (s00o * s11o - s01 * s01) / det;
+            const float comp = sqrtf(fmaxf(0.f, r));
+            float v_comp = 0.f;
+            if constexpr (RAW) {
+                const float o = opacity_logits ? gags_act_opacity(opacity_logits[i]) : 0.f;
+                const float vo = v_opacities ? v_opacities[i] : 0.f;
+                v_comp = vo * o;
+                if (v_opacity_logits) v_opacity_logits[i] = ((vo * comp) * (1.0f - o)) * o;
+            } else {
+                v_comp = v_compensations ? v_compensations[i] : 0.f;
+            }
+            const float v_r = comp > 0.f ? v_comp / (2.f * comp) : 0.f;
+            const float e = eps2d * inv_det, omr = 1.f - r;
+            G00 += v_r * (omr * ca - e);
+            G11 += v_r * (omr * cc - e);
+            G01 += v_r * omr * cb;  // (d r / d s01 = 2 (1 - r) b, half on either side of the symmetric matrix)
+            G10 += v_r * omr * cb;
+        }
         const float G[2][2] = {{G00, G01}, {G10, G11}};
         /* ---- 2. cov2d = J Sc J^T:  G_Sc = J^T G J ; G_J = G J Sc^T + G^T J Sc ---- */
         float GJ[2][3], GSc[3][3], vJ[2][3];
@@ -354,24 +423,51 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
 
 }  // namespace
 
+namespace {
+
+template <bool RAW, bool AA>
+int project_bwd_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
+                       float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
+                       const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
+                       const float *v_opacities, const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                       float *v_opacity_logit, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
+    if (n == 0) return GAGS_OK;
+    if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics || !v_means || !v_quats || !v_scales)
+        return GAGS_EINVAL;
+    if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
+    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means, quats,
+                       scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats,
+                       v_scales, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}
+
+}  // namespace
+
 extern "C" int gags_project_bwd(int n, const float *means, const float *quats, const float *scales,
                                 const float *viewmat, const float *K, int width, int height, float eps2d,
                                 const int32_t *radii, const float *conics, const float *v_means2d,
                                 const float *v_depths, const float *v_conics, float *v_means, float *v_quats,
                                 float *v_scales, void *stream)
 {
-    GAGS_CLEAR_ERR();
     (void)conics;  // recomputed in-kernel with the forward's operation order
-    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
-    if (n == 0) return GAGS_OK;
-    if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics || !v_means ||
-        !v_quats || !v_scales)
-        return GAGS_EINVAL;
-    hipLaunchKernelGGL(project_bwd_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means, quats,
-                       scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means,
-                       v_quats, v_scales, nullptr, 1.0f, nullptr, nullptr);
-    GAGS_CHECK_LAUNCH();
-    return GAGS_OK;
+    return project_bwd_launch<false, false>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, radii,
+                                            v_means2d, v_depths, v_conics, nullptr, nullptr, v_means, v_quats, v_scales, nullptr,
+                                            stream);
+}
+
+extern "C" int gags_project_bwd_aa(int n, const float *means, const float *quats, const float *scales,
+                                   const float *viewmat, const float *K, int width, int height, float eps2d,
+                                   const int32_t *radii, const float *v_means2d, const float *v_depths,
+                                   const float *v_conics, const float *v_compensations, float *v_means, float *v_quats,
+                                   float *v_scales, void *stream)
+{
+    return project_bwd_launch<false, true>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, radii,
+                                           v_means2d, v_depths, v_conics, nullptr, v_compensations, v_means, v_quats, v_scales,
+                                           nullptr, stream);
 }
 
 extern "C" int gags_project_bwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
@@ -380,15 +476,18 @@ extern "C" int gags_project_bwd_raw(int n, const float *means, const float *rota
                                     const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
                                     float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream)
 {
-    GAGS_CLEAR_ERR();
-    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
-    if (n == 0) return GAGS_OK;
-    if (!means || !rotation || !scaling_log || !viewmat || !K || !radii || !v_means2d || !v_conics || !v_means ||
-        !v_rotation || !v_scaling_log || (v_opacity_logit && !opacity_logit))
-        return GAGS_EINVAL;
-    hipLaunchKernelGGL(project_bwd_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means, rotation,
-                       scaling_log, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means,
-                       v_rotation, v_scaling_log, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit);
-    GAGS_CHECK_LAUNCH();
-    return GAGS_OK;
+    return project_bwd_launch<true, false>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
+                                           height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities, nullptr, v_means,
+                                           v_rotation, v_scaling_log, v_opacity_logit, stream);
+}
+
+extern "C" int gags_project_bwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
+                                       const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                                       int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                                       const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
+                                       float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream)
+{
+    return project_bwd_launch<true, true>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
+                                          height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities, nullptr, v_means,
+                                          v_rotation, v_scaling_log, v_opacity_logit, stream);
 }

@@ -463,11 +463,9 @@ int gags_blended_mask_launch(int n_isects, const int32_t *hit, const int32_t *fl
     return GAGS_OK;
 }
 
-// (prototype: -Wmissing-prototypes)
-__global__ __launch_bounds__(64) void raster_bwd_geom(int, int, int, int, int, const GRec *, const int32_t *, int, const int32_t *,
-                                                      const float *, const int32_t *, const int32_t *, const float *, const float *,
-                                                      const float *, const float *, float *, uint32_t *, int32_t *, int,
-                                                      const int32_t *, int, size_t, size_t);
+// ABS (GAGS_GEOM_ABSGRAD): lanes 6 and 7 of the row carry the wave sums of |g3| and |g4|, the per-pixel terms of v_means2d before
+// any reduction across pixels (absgrad, include/gags_raster.h); without it they are the zeros they always were.
+template <bool ABS>
 __global__ __launch_bounds__(64) void raster_bwd_geom(int width, int height, int tile_w, int n_tiles, int n_gauss,
                                                       const GRec *__restrict__ packed, const int32_t *__restrict__ offsets,
                                                       int n_isects, const int32_t *__restrict__ blk_rows,
@@ -563,9 +561,12 @@ __global__ __launch_bounds__(64) void raster_bwd_geom(int width, int height, int
             }
         }
         g0 = gags_wave_sum(g0); g1 = gags_wave_sum(g1); g2 = gags_wave_sum(g2);
+        float g6 = 0.f, g7 = 0.f;
+        if constexpr (ABS) { g6 = gags_wave_sum(fabsf(g3)); g7 = gags_wave_sum(fabsf(g4)); }
         g3 = gags_wave_sum(g3); g4 = gags_wave_sum(g4); g5 = gags_wave_sum(g5);
         if (lane < 8) {
-            const float v = lane == 0 ? g0 : lane == 1 ? g1 : lane == 2 ? g2 : lane == 3 ? g3 : lane == 4 ? g4 : lane == 5 ? g5 : 0.f;
+            const float v = lane == 0 ? g0 : lane == 1 ? g1 : lane == 2 ? g2 : lane == 3 ? g3 : lane == 4 ? g4 : lane == 5 ? g5
+                            : !ABS ? 0.f : lane == 6 ? g6 : g7;
             grow[(size_t)row * 8 + lane] = v;
         }
         if (lane == 0) { key[row] = (uint32_t)g; idx[row] = row; }
@@ -623,7 +624,7 @@ int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const
                                 const float *v_alphas, const int32_t *blk_rows, const float *wt, const int32_t *gid_s,
                                 const int32_t *sidx_s, const float *Tbuf, void *scratch, int64_t scratch_bytes, float *v_geo,
                                 int by_gauss, const int32_t *row_base, int64_t n_rows, const int32_t *hit,
-                                const int32_t *flatten_ids, int f32mfma, hipStream_t st)
+                                const int32_t *flatten_ids, int f32mfma, int absgrad, hipStream_t st)
 {
     GAGS_CLEAR_ERR();
     if (d < 16 || d % 8 != 0) return 1;
@@ -682,9 +683,9 @@ int gags_raster_bwd_geom_launch(int d, int n_gauss, int width, int height, const
             hipLaunchKernelGGL(raster_bwd_sdot<0>, grid, dim3(256), lds, st, d, ch0, dch, width, height, tile_w, n_tiles, n_gauss,
                                v_out, colors, backgrounds, offsets, n_isects, blk_rows, gid_s, S, bgdot, ch0 > 0 ? 1 : 0, row_base);
     }
-    hipLaunchKernelGGL(raster_bwd_geom, dim3(n_tiles * GAGS_BLOCKS_PER_TILE), dim3(64), 0, st, width, height, tile_w, n_tiles,
-                       n_gauss, reinterpret_cast<const GRec *>(packed), offsets, n_isects, blk_rows, wt, gid_s, sidx_s, S, Tbuf,
-                       v_alphas, bgdot, grow, key, idx, by_gauss, row_base, n_pass, s_stride, bg_stride);
+    hipLaunchKernelGGL(absgrad ? raster_bwd_geom<true> : raster_bwd_geom<false>, dim3(n_tiles * GAGS_BLOCKS_PER_TILE), dim3(64), 0, st,
+                       width, height, tile_w, n_tiles, n_gauss, reinterpret_cast<const GRec *>(packed), offsets, n_isects, blk_rows, wt,
+                       gid_s, sidx_s, S, Tbuf, v_alphas, bgdot, grow, key, idx, by_gauss, row_base, n_pass, s_stride, bg_stride);
     GAGS_CHECK_LAUNCH();
     int rc = gags_rows_group_launch(slots, n_gauss, nullptr, key, idx, key_s, idx_s, seg, L.sort, L.sort_bytes, st);
     if (rc != GAGS_OK) return rc;

@@ -112,7 +112,9 @@ __device__ __forceinline__ void atomic_add_f32(float *p, float v)
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int CDIM, bool GEOM>
+// ABS (gags_raster_bwd_abs; GEOM and one channel chunk only, D <= CDIM): v_means2d_abs[g] += the wave sums of (|g3|, |g4|), the
+// per-pixel terms of v_means2d over all channels of the pixel (absgrad, include/gags_raster.h).
+template <int CDIM, bool GEOM, bool ABS>
 __global__ __launch_bounds__(256) void raster_bwd_valu(
     int d, int width, int height, int tile_w, int n_tiles, const float *__restrict__ means2d,
     const float *__restrict__ conics, const float *__restrict__ opacities, const float *__restrict__ colors,
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(256) void raster_bwd_valu(
     const int32_t *__restrict__ flatten_ids, int n_isects, const float *__restrict__ render_alphas,
     const int32_t *__restrict__ last_ids, const float *__restrict__ v_render_colors,
     const float *__restrict__ v_render_alphas, float *__restrict__ v_colors, float *__restrict__ v_opacities,
-    float *__restrict__ v_means2d, float *__restrict__ v_conics)
+    float *__restrict__ v_means2d, float *__restrict__ v_conics, float *__restrict__ v_means2d_abs)
 {
     __shared__ GaussLds gs[BATCH];
     __shared__ int32_t ids[BATCH];
@@ -220,8 +222,13 @@ __global__ __launch_bounds__(256) void raster_bwd_valu(
                         g5 = vis * v_alpha;
                     }
                 }
+                float g6 = 0.f, g7 = 0.f;
+                if constexpr (ABS) { g6 = gags_wave_sum(fabsf(g3)); g7 = gags_wave_sum(fabsf(g4)); }
                 g0 = gags_wave_sum(g0); g1 = gags_wave_sum(g1); g2 = gags_wave_sum(g2);
                 g3 = gags_wave_sum(g3); g4 = gags_wave_sum(g4); g5 = gags_wave_sum(g5);
+                if constexpr (ABS) {
+                    if (lane == 6 || lane == 7) atomic_add_f32(v_means2d_abs + 2 * (size_t)g + (lane - 6), lane == 6 ? g6 : g7);
+                }
                 if (lane < 3) atomic_add_f32(v_conics + 3 * (size_t)g + lane, lane == 0 ? g0 : (lane == 1 ? g1 : g2));
                 else if (lane < 5) atomic_add_f32(v_means2d + 2 * (size_t)g + (lane - 3), lane == 3 ? g3 : g4);
                 else if (lane == 5) atomic_add_f32(v_opacities + g, g5);
@@ -303,18 +310,18 @@ int launch_fwd(int d, int width, int height, const float *means2d, const float *
     return GAGS_OK;
 }
 
-template <int CDIM, bool GEOM>
+template <int CDIM, bool GEOM, bool ABS = false>
 int launch_bwd(int d, int width, int height, const float *means2d, const float *conics, const float *opacities,
                const float *colors, const float *backgrounds, const int32_t *offsets, const int32_t *flat,
                int n_isects, const float *alphas, const int32_t *last_ids, const float *v_out, const float *v_alpha,
-               float *v_colors, float *v_opac, float *v_m2d, float *v_con, hipStream_t st)
+               float *v_colors, float *v_opac, float *v_m2d, float *v_con, hipStream_t st, float *v_m2d_abs = nullptr)
 {
     const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
     const int n_tiles = tile_w * tile_h;
     dim3 grid(n_tiles, (d + CDIM - 1) / CDIM);
-    hipLaunchKernelGGL((raster_bwd_valu<CDIM, GEOM>), grid, dim3(256), 0, st, d, width, height, tile_w, n_tiles,
+    hipLaunchKernelGGL((raster_bwd_valu<CDIM, GEOM, ABS>), grid, dim3(256), 0, st, d, width, height, tile_w, n_tiles,
                        means2d, conics, opacities, colors, backgrounds, offsets, flat, n_isects, alphas, last_ids,
-                       v_out, v_alpha, v_colors, v_opac, v_m2d, v_con);
+                       v_out, v_alpha, v_colors, v_opac, v_m2d, v_con, v_m2d_abs);
     GAGS_CHECK_LAUNCH();
     return GAGS_OK;
 }
@@ -339,10 +346,16 @@ int gags_raster_bwd_valu(int d, int width, int height, const float *means2d, con
                          const float *opacities, const float *colors, const float *backgrounds,
                          const int32_t *offsets, const int32_t *flat, int n_isects, const float *alphas,
                          const int32_t *last_ids, const float *v_out, const float *v_alpha, float *v_colors,
-                         float *v_opac, float *v_m2d, float *v_con, bool geom, hipStream_t st)
+                         float *v_opac, float *v_m2d, float *v_con, bool geom, hipStream_t st, float *v_m2d_abs)
 {
     GAGS_CLEAR_ERR();
 #define ARGS d, width, height, means2d, conics, opacities, colors, backgrounds, offsets, flat, n_isects, alphas, last_ids, v_out, v_alpha, v_colors, v_opac, v_m2d, v_con, st
+    if (v_m2d_abs) {  // absgrad: all gradients, one channel chunk (an absolute value of a chunk's partial sum is not the rule)
+        if (!geom || d > 32) return GAGS_EINVAL;
+        if (d <= 4) return launch_bwd<4, true, true>(ARGS, v_m2d_abs);
+        if (d <= 16) return launch_bwd<16, true, true>(ARGS, v_m2d_abs);
+        return launch_bwd<32, true, true>(ARGS, v_m2d_abs);
+    }
     if (geom) {
         if (d <= 4) return launch_bwd<4, true>(ARGS);
         if (d <= 16) return launch_bwd<16, true>(ARGS);

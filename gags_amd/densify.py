@@ -80,15 +80,28 @@ def stats(model, grad, radii, update_filter, visibility_filter, width, height):
             _lib.ptr(model.max_radii2D if radii is not None else None), _lib.stream(dev)), "gags_densify_stats")
 
 
-def accumulate(model, render_pkg):
-    """The per-step statistics of train.py:209-211 in one launch: accum / denom from the viewspace gradient and max_radii2D
-    from the radii, both over `radii > 0` (the reference passes visibility_filter for both filters).  The reference also
-    scales viewspace_point_tensor.grad in place; nothing reads it afterwards and it is not written back."""
-    vp = render_pkg["viewspace_points"]
+def viewspace_gradient(vp, absgrad=False):
+    """The tensor the statistics are taken from: `vp.grad`, or with absgrad `vp.absgrad` -- what a backward of
+    render(..., absgrad=True) attaches (the sum over pixels of the absolute per-pixel gradients, AbsGS)."""
+    if absgrad:
+        g = getattr(vp, "absgrad", None)
+        if g is None:
+            raise RuntimeError("densify: viewspace_points has no .absgrad (render with absgrad=True, geometry gradients wanted, "
+                               "and call backward first)")
+        return g
     if vp.grad is None:
         raise RuntimeError("accumulate: viewspace_points has no gradient (call backward first)")
+    return vp.grad
+
+
+def accumulate(model, render_pkg, absgrad=False):
+    """The per-step statistics of train.py:209-211 in one launch: accum / denom from the viewspace gradient and max_radii2D
+    from the radii, both over `radii > 0` (the reference passes visibility_filter for both filters).  The reference also
+    scales viewspace_point_tensor.grad in place; nothing reads it afterwards and it is not written back.
+    absgrad: the statistic is taken from viewspace_points.absgrad instead of .grad (render(..., absgrad=True))."""
+    vp = render_pkg["viewspace_points"]
     img = render_pkg["render"]
-    stats(model, vp.grad, render_pkg["radii"], None, None, img.shape[2], img.shape[1])
+    stats(model, viewspace_gradient(vp, absgrad), render_pkg["radii"], None, None, img.shape[2], img.shape[1])
 
 
 class Plan:

@@ -81,10 +81,12 @@ def _stored_parameters(pc):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True, scaling_modifier=1.0,
-           override_color=None, render_mode="RGB", raster_flags=0, context=None):
+           override_color=None, render_mode="RGB", raster_flags=0, context=None, rasterize_mode="classic", absgrad=False):
     """Render the scene.  Background tensor (bg_color) must be on GPU!
     raster_flags / context are this package's additions to the reference's signature (kernel selection; the RasterContext
-    holding this caller's hooks, capacities and caches -- None = the calling thread's default)."""
+    holding this caller's hooks, capacities and caches -- None = the calling thread's default).
+    rasterize_mode / absgrad: gsplat's options of the same names, handed to rasterization() (antialiased opacity
+    compensation; `viewspace_points.absgrad` after backward(), which densify.accumulate(..., absgrad=True) reads)."""
     rctx = context if context is not None else default_context()
     means3D = pc.get_xyz
     K = _intrinsics(viewpoint_camera, means3D.device, rctx.k_cache)
@@ -112,7 +114,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
         viewmats=viewmat[None], Ks=K[None], backgrounds=bg_color[None],
         width=int(viewpoint_camera.image_width), height=int(viewpoint_camera.image_height),
         packed=False, sh_degree=sh_degree, render_mode=render_mode, raster_flags=raster_flags,
-        raw_params=stored is not None, scaling_modifier=float(scaling_modifier), context=rctx)
+        raw_params=stored is not None, scaling_modifier=float(scaling_modifier), context=rctx,
+        rasterize_mode=rasterize_mode, absgrad=absgrad)
 
     # squeeze (not [0]): its backward is a view, [0]'s is a zero-fill + copy of the whole map
     rendered_image = render_colors.squeeze(0).permute(2, 0, 1)  # [1,H,W,D'] -> [D',H,W]

@@ -322,10 +322,11 @@ def _c(t):
 
 
 class _Project(torch.autograd.Function):
-    """K1 + K4 forward, K2 backward."""
+    """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
+    cotangent in the backward (gags_project_fwd_aa / gags_project_bwd_aa); the caller multiplies them into the opacities."""
 
     @staticmethod
-    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip):
+    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False):
         lib = _lib.load()
         means, quats, scales, viewmat, K = _c(means), _c(quats), _c(scales), _c(viewmat), _c(K)
         n = means.shape[0]
@@ -335,20 +336,28 @@ class _Project(torch.autograd.Function):
         depths = torch.empty(n, dtype=torch.float32, device=dev)
         conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
         tiles = torch.empty(n, dtype=torch.int32, device=dev)
+        comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
         with profiler.stage("project_fwd"):
-            check(lib.gags_project_fwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
-                                       eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths),
-                                       ptr(conics), ptr(tiles), _stream()), "gags_project_fwd")
+            if aa:
+                check(lib.gags_project_fwd_aa(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
+                                              eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths),
+                                              ptr(conics), ptr(tiles), ptr(comp), _stream()), "gags_project_fwd_aa")
+            else:
+                check(lib.gags_project_fwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
+                                           eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths),
+                                           ptr(conics), ptr(tiles), _stream()), "gags_project_fwd")
         ctx.save_for_backward(means, quats, scales, viewmat, K, radii, conics)
-        ctx.cfg = (width, height, eps2d)
+        ctx.cfg = (width, height, eps2d, aa)
         ctx.mark_non_differentiable(radii, tiles)
+        if aa:
+            return radii, means2d, depths, conics, tiles, comp
         return radii, means2d, depths, conics, tiles
 
     @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles):
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_comp=None):
         lib = _lib.load()
         means, quats, scales, viewmat, K, radii, conics = ctx.saved_tensors
-        width, height, eps2d = ctx.cfg
+        width, height, eps2d, aa = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
@@ -357,20 +366,29 @@ class _Project(torch.autograd.Function):
         v_means = torch.empty(n, 3, device=dev)
         v_quats = torch.empty(n, 4, device=dev)
         v_scales = torch.empty(n, 3, device=dev)
-        check(lib.gags_project_bwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
-                                   eps2d, ptr(radii), ptr(conics), ptr(v_means2d), ptr(v_depths), ptr(v_conics),
-                                   ptr(v_means), ptr(v_quats), ptr(v_scales), _stream()), "gags_project_bwd")
-        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None
+        if aa:
+            v_comp = None if v_comp is None else _c(v_comp)
+            check(lib.gags_project_bwd_aa(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
+                                          eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_comp),
+                                          ptr(v_means), ptr(v_quats), ptr(v_scales), _stream()), "gags_project_bwd_aa")
+        else:
+            check(lib.gags_project_bwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
+                                       eps2d, ptr(radii), ptr(conics), ptr(v_means2d), ptr(v_depths), ptr(v_conics),
+                                       ptr(v_means), ptr(v_quats), ptr(v_scales), _stream()), "gags_project_bwd")
+        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None, None
 
 
 class _ProjectRaw(torch.autograd.Function):
     """K1 + K4 on the STORED parameters (gags_project_fwd_raw / gags_project_bwd_raw): the getters of
     scene/gaussian_model.py:116-139 -- exp, F.normalize, sigmoid -- and render()'s `* scaling_modifier` run inside the
-    projection kernel, bit for bit as torch evaluates them; the backward returns gradients of the stored parameters."""
+    projection kernel, bit for bit as torch evaluates them; the backward returns gradients of the stored parameters.
+    aa (rasterize_mode "antialiased"): the kernel folds the compensation into the activated opacity and the record
+    (gags_project_fwd_raw_aa), the compensations [N] are one more -- non-differentiable -- output, and the backward takes the
+    compensation's cotangent from the opacity's (gags_project_bwd_raw_aa)."""
 
     @staticmethod
     def forward(ctx, means, rotation, scaling_log, opacity_logit, viewmat, K, width, height, eps2d, near, far, radius_clip,
-                scaling_modifier, want_records):
+                scaling_modifier, want_records, aa=False):
         lib = _lib.load()
         means, rotation, scaling_log, viewmat, K = _c(means), _c(rotation), _c(scaling_log), _c(viewmat), _c(K)
         logit = _c(opacity_logit.reshape(-1))
@@ -384,21 +402,32 @@ class _ProjectRaw(torch.autograd.Function):
         opac = torch.empty(n, dtype=torch.float32, device=dev)
         # the per-Gaussian records of the matrix-core raster kernels (K8b), written on the way: no record kernel in the binning
         grec = torch.empty(max(n, 1), 8, dtype=torch.float32, device=dev) if want_records else torch.empty(0, device=dev)
+        comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
         with profiler.stage("project_fwd"):
-            check(lib.gags_project_fwd_raw(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier,
-                                           ptr(viewmat), ptr(K), width, height, eps2d, near, far, radius_clip, ptr(radii),
-                                           ptr(means2d), ptr(depths), ptr(conics), ptr(tiles), ptr(opac), None, None,
-                                           ptr(grec) if want_records else None, _stream()), "gags_project_fwd_raw")
+            if aa:
+                check(lib.gags_project_fwd_raw_aa(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier,
+                                                  ptr(viewmat), ptr(K), width, height, eps2d, near, far, radius_clip, ptr(radii),
+                                                  ptr(means2d), ptr(depths), ptr(conics), ptr(tiles), ptr(opac), None, None,
+                                                  ptr(grec) if want_records else None, ptr(comp), _stream()),
+                      "gags_project_fwd_raw_aa")
+            else:
+                check(lib.gags_project_fwd_raw(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier,
+                                               ptr(viewmat), ptr(K), width, height, eps2d, near, far, radius_clip, ptr(radii),
+                                               ptr(means2d), ptr(depths), ptr(conics), ptr(tiles), ptr(opac), None, None,
+                                               ptr(grec) if want_records else None, _stream()), "gags_project_fwd_raw")
         ctx.save_for_backward(means, rotation, scaling_log, logit, viewmat, K, radii)
-        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape))
+        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa)
+        if aa:
+            ctx.mark_non_differentiable(radii, tiles, grec, comp)
+            return radii, means2d, depths, conics, tiles, opac, grec, comp
         ctx.mark_non_differentiable(radii, tiles, grec)
         return radii, means2d, depths, conics, tiles, opac, grec
 
     @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_opac, _v_grec):
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_opac, _v_grec, _v_comp=None):
         lib = _lib.load()
         means, rotation, scaling_log, logit, viewmat, K, radii = ctx.saved_tensors
-        width, height, eps2d, modifier, oshape = ctx.cfg
+        width, height, eps2d, modifier, oshape, aa = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
@@ -409,12 +438,14 @@ class _ProjectRaw(torch.autograd.Function):
         v_rot = torch.empty(n, 4, device=dev)
         v_scal = torch.empty(n, 3, device=dev)
         v_logit = torch.empty(n, device=dev) if ctx.needs_input_grad[3] else None
-        check(lib.gags_project_bwd_raw(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), modifier, ptr(viewmat),
-                                       ptr(K), width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths),
-                                       ptr(v_conics), ptr(v_opac), ptr(v_means), ptr(v_rot), ptr(v_scal), ptr(v_logit),
-                                       _stream()), "gags_project_bwd_raw")
+        entry, name = ((lib.gags_project_bwd_raw_aa, "gags_project_bwd_raw_aa") if aa
+                       else (lib.gags_project_bwd_raw, "gags_project_bwd_raw"))
+        check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), modifier, ptr(viewmat),
+                    ptr(K), width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths),
+                    ptr(v_conics), ptr(v_opac), ptr(v_means), ptr(v_rot), ptr(v_scal), ptr(v_logit),
+                    _stream()), name)
         return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), None, None, None, None, None,
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
 class _SH(torch.autograd.Function):
@@ -596,6 +627,7 @@ class _Route(NamedTuple):
     zero_fill: bool      # the gradient's zero-fill starts on a second stream before the binning (RasterContext.overlap_zero_fill)
     flags: int           # the caller's raster_flags, for the kernel-variant bits the translations below read (never the route);
     #                      GAGS_FWD_F16MFMA only where it applies (an fp16 table read as it is, D >= 128)
+    absgrad: bool = False  # the backward also produces absgrad (only with geom; _BWD_STAGED_GEOM, or _BWD_VALU at D <= 32)
 
     @property
     def keeps_scratch(self):
@@ -614,14 +646,18 @@ class _Route(NamedTuple):
                              bwd=_BWD_NONE if self.bwd == _BWD_NONE else _BWD_VALU)
 
 
+ABSGRAD_VALU_MAX_D = 32  # gags_raster_bwd_abs: one channel chunk must cover D
+
+
 def _route(n, d, f16, needs, raster_flags, profiling, capacity_mode=False, early_rowmap=True, overlap_zero_fill=False,
-           hooked=False, trim_lists=None):
+           hooked=False, trim_lists=None, absgrad=False):
     """The _Route of a call, from plain values: n Gaussians, d = the FINAL channel count, f16 = the table is fp16, needs = which
     of (means2d, conics, colors, opacities, backgrounds) require grad while a graph is recorded, the caller's raster_flags,
     profiler.ENABLED, and the RasterContext settings that matter (hooked: grad_range_hook is set).
     The widths: the matrix-core forward serves every D >= 16 (gags_mfma_width in csrc/common.h; 16 is what the reference
     rasterizes, 513 = 512 + 1 is BASELINE.json configs[4]), the staged backward D <= 1024, gags_raster_bwd_geom D % 8 == 0
-    of those (below 16 the VALU kernel is faster)."""
+    of those (below 16 the VALU kernel is faster).  absgrad: asked for by the caller; the route carries it only where a geometry
+    gradient is produced (rasterization() refuses the one route that cannot serve it: _BWD_VALU at D > ABSGRAD_VALU_MAX_D)."""
     wide = d >= 16
     mfma = wide and n > 0 and not (raster_flags & (_lib.GAGS_FWD_NO_MFMA | _lib.GAGS_FWD_FUSED))
     half = mfma and f16
@@ -640,7 +676,8 @@ def _route(n, d, f16, needs, raster_flags, profiling, capacity_mode=False, early
                   geom=bool(geom), colors=bool(needs[2]), flags=int(raster_flags),
                   early_rowmap=bwd == _BWD_STAGED and bool(early_rowmap) and not capacity_mode,
                   trim=trim_lists if fwd in (_FWD_SPLIT, _FWD_LEAN16) else False,
-                  zero_fill=bool(overlap_zero_fill) and not hooked and bwd == _BWD_STAGED and n * d >= ZERO_FILL_MIN_ELEMS)
+                  zero_fill=bool(overlap_zero_fill) and not hooked and bwd == _BWD_STAGED and n * d >= ZERO_FILL_MIN_ELEMS,
+                  absgrad=bool(absgrad) and bool(geom) and bwd in (_BWD_STAGED_GEOM, _BWD_VALU))
 
 
 class _Rasterize(torch.autograd.Function):
@@ -652,9 +689,10 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, packed, width, height, route, rctx,
-                prezero=None):
+                prezero=None, abs_holder=None):
         """offsets: the buffer of n_tiles + 1 int32 entries tile_binning returns as `offsets_full` (last entry = the
-        intersection count).  route: _route() of the call; rctx: its RasterContext."""
+        intersection count).  route: _route() of the call; rctx: its RasterContext.  abs_holder (route.absgrad): a list whose
+        first entry is the [1,N,2] tensor the backward attaches `.absgrad` to (the node callers hold, as gsplat does)."""
         lib = _lib.load()
         n_isects = flatten_ids.shape[0]  # (capacity mode: the buffers' size; the kernels take the count from `offsets`)
         if n_isects == 0:
@@ -692,6 +730,7 @@ class _Rasterize(torch.autograd.Function):
                               "intersections could not be allocated; this view runs on the scratch-free kernels "
                               "(INTEGRATION.md, memory model)", RuntimeWarning, stacklevel=3)
                 route, nbytes, colors = route.without_scratch(), 0, _c(colors)
+                _check_absgrad_route(route, d)
         if route.fwd == _FWD_SPLIT:
             blk_rows = torch.empty(n_tiles * 4, dtype=torch.int32, device=dev)  # per 8x8 pixel block
         cflags = _fwd_flags(route)
@@ -720,6 +759,7 @@ class _Rasterize(torch.autograd.Function):
         ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, packed, alphas,
                               last_ids, scratch if keep else None, blk_rows if keep else None)
         ctx.route = route
+        ctx.abs_holder = abs_holder if route.absgrad else None
         ctx.cfg = (width, height, rctx, prezero if route.bwd == _BWD_STAGED else None, early)
         ctx.mark_non_differentiable(last_ids)
         return out, alphas, last_ids
@@ -748,17 +788,32 @@ class _Rasterize(torch.autograd.Function):
         else:
             grads = _backward_valu(lib, route, fwd, means2d, conics, opacities, colors, backgrounds, packed, alphas, last_ids,
                                    v_out, v_alphas)
-        return _raster_grads(*grads, v_bg)
+        if route.absgrad:
+            # overwritten by each backward, never accumulated; [1,N,2] like the tensor it goes on
+            grads, v_abs = grads[:4], grads[4]
+            if ctx.abs_holder:
+                ctx.abs_holder[0].absgrad = v_abs[None]
+        return _raster_grads(*grads[:4], v_bg)
 
 
 def _raster_grads(v_m2d, v_con, v_colors, v_opac, v_bg):
     """_Rasterize.backward's return: the five gradients in the slots of forward's tensor arguments, None for the rest."""
-    return (v_m2d, v_con, v_colors, v_opac, v_bg) + (None,) * 8
+    return (v_m2d, v_con, v_colors, v_opac, v_bg) + (None,) * 9
+
+
+def _check_absgrad_route(route, d):
+    """absgrad on the one route that cannot serve it: the VALU kernel splits a pixel's channels over blocks above
+    ABSGRAD_VALU_MAX_D, and an absolute value of a partial sum is not the rule."""
+    if route.absgrad and route.bwd == _BWD_VALU and d > ABSGRAD_VALU_MAX_D:
+        raise NotImplementedError(
+            f"absgrad=True with geometry gradients at D = {d} on the VALU backward: served for D <= {ABSGRAD_VALU_MAX_D} there, "
+            "and for every D % 8 == 0 in 16..1024 on the matrix-core geometry pass (DESIGN.md section 7, N16)")
 
 
 def _backward_geom_mfma(lib, rctx, route, fwd, colors, backgrounds, packed, v_out, v_alphas):
     """Wide D, geometry wanted: colours (if wanted) through the staged backward, geometry through the matrix-core dot pass +
-    scalar pass of gags_raster_bwd_geom, both on the forward's scratch.  Returns (v_means2d, v_conics, v_colors, v_opacities)."""
+    scalar pass of gags_raster_bwd_geom, both on the forward's scratch.  Returns (v_means2d, v_conics, v_colors, v_opacities)
+    and -- route.absgrad -- absgrad [N,2] as a fifth."""
     dev = colors.device
     v_colors = _backward_staged(lib, rctx, fwd, v_out, _stage_bits(route.flags, route.half)) if route.colors else None
     if route.half:  # the geometry kernels read an fp32 table: widen the halves (exact) for this backward
@@ -780,17 +835,29 @@ def _backward_geom_mfma(lib, rctx, route, fwd, colors, backgrounds, packed, v_ou
                                        ptr(fwd.fwd_scratch), fwd.fwd_scratch.numel(), ptr(gscratch), nb, ptr(v_geo),
                                        ptr(fwd.flatten_ids), ptr(row_base), n_rows, _geom_flags(route), _stream()),
               "gags_raster_bwd_geom")
-    return v_geo[:, 3:5].contiguous(), v_geo[:, 0:3].contiguous(), v_colors, v_geo[:, 5].contiguous()
+    grads = (v_geo[:, 3:5].contiguous(), v_geo[:, 0:3].contiguous(), v_colors, v_geo[:, 5].contiguous())
+    return grads + (v_geo[:, 6:8].contiguous(),) if route.absgrad else grads
 
 
 def _backward_valu(lib, route, fwd, means2d, conics, opacities, colors, backgrounds, packed, alphas, last_ids, v_out, v_alphas):
     """gags_raster_bwd, the VALU / atomic kernels: colours, and -- route.geom -- geometry.  They read an fp32 table: the halves
-    are widened (exact) and the gradient goes back in the table's dtype.  Returns (v_means2d, v_conics, v_colors, v_opacities)."""
+    are widened (exact) and the gradient goes back in the table's dtype.  Returns (v_means2d, v_conics, v_colors, v_opacities)
+    and -- route.absgrad, through gags_raster_bwd_abs -- absgrad [N,2] as a fifth."""
     dev = colors.device
     if route.half:
         colors = colors.float()
     v_colors = torch.zeros(fwd.n, fwd.d, device=dev)
     v_opac, v_m2d, v_con = ([torch.zeros(fwd.n, *k, device=dev) for k in ((), (2,), (3,))] if route.geom else (None, None, None))
+    if route.absgrad:
+        _check_absgrad_route(route, fwd.d)
+        v_abs = torch.zeros(fwd.n, 2, device=dev)
+        with profiler.stage("raster_bwd"):
+            check(lib.gags_raster_bwd_abs(fwd.d, fwd.width, fwd.height, ptr(means2d), ptr(conics), ptr(opacities), ptr(colors),
+                                          ptr(backgrounds), ptr(fwd.offsets), ptr(fwd.flatten_ids), fwd.n_isects, ptr(packed),
+                                          ptr(alphas), ptr(last_ids), ptr(v_out), ptr(v_alphas), ptr(v_colors),
+                                          ptr(v_opac), ptr(v_m2d), ptr(v_con), ptr(v_abs), _bwd_flags(route), _stream()),
+                  "gags_raster_bwd_abs")
+        return v_m2d, v_con, v_colors.half() if route.half else v_colors, v_opac, v_abs
     with profiler.stage("raster_bwd"):
         check(lib.gags_raster_bwd(fwd.d, fwd.width, fwd.height, ptr(means2d), ptr(conics), ptr(opacities), ptr(colors),
                                   ptr(backgrounds), ptr(fwd.offsets), ptr(fwd.flatten_ids), fwd.n_isects, ptr(packed),
@@ -891,7 +958,8 @@ def _bwd_flags(route):
 
 def _geom_flags(route):
     """`flags` of gags_raster_bwd_geom."""
-    return _lib.GAGS_RECS_BY_GAUSSIAN | (_lib.GAGS_GEOM_F32MFMA if (route.flags & _lib.GAGS_BWD_F32MFMA) else 0)
+    return (_lib.GAGS_RECS_BY_GAUSSIAN | (_lib.GAGS_GEOM_F32MFMA if (route.flags & _lib.GAGS_BWD_F32MFMA) else 0)
+            | (_lib.GAGS_GEOM_ABSGRAD if route.absgrad else 0))
 
 
 def _rowmap(lib, fwd):
@@ -1079,22 +1147,23 @@ def _backward_staged(lib, rctx, fwd, v_out, stage_bits=0, prezero=None, exact_ro
     return v_colors
 
 
-def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh, render_mode, raw_params):
+def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh, render_mode, raw_params, aa=False):
     """What _Rasterize will be handed, known before anything runs: (d, f16, needs) = the final channel count (after SH
     evaluation and the depth channel of RGB+D / RGB+ED), whether the final table is fp16 (only a table passed through as it
     is), and which of (means2d, conics, colors, opacities, backgrounds) will require grad -- autograd's own rule: an output
     requires grad when a graph is recorded and any tensor it was computed from does.  rasterization() checks all three
-    against the tensors themselves before it rasterizes."""
+    against the tensors themselves before it rasterizes.  aa: the opacities are multiplied by the projection's compensations."""
     def rg(*ts):
         return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
     proj = rg(means, quats, scales, viewmats, Ks) or (raw_params and rg(opacities))  # (means2d, conics, depths)
+    v_opac = proj if raw_params else (rg(opacities) or (aa and proj))
     if render_mode in ("D", "ED"):
-        return 1, False, (proj, proj, proj, proj if raw_params else rg(opacities), False)
+        return 1, False, (proj, proj, proj, v_opac, False)
     depth = render_mode != "RGB"
     d = (3 if sh else colors.shape[-1]) + (1 if depth else 0)
     v_cols = rg(colors) or (sh and rg(means, viewmats)) or (depth and proj)
     return (d, colors.dtype == torch.float16 and not sh and not depth,
-            (proj, proj, v_cols, proj if raw_params else rg(opacities), rg(backgrounds)))
+            (proj, proj, v_cols, v_opac, rg(backgrounds)))
 
 
 def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height,
@@ -1110,13 +1179,23 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     (gags_project_fwd_raw; bit-identical to torch's exp / F.normalize / sigmoid): no elementwise launches, no extra passes
     over N, and the backward returns the gradients of the stored parameters.
     context (not part of gsplat's signature): the RasterContext that carries this caller's hooks and capacities; None = the
-    calling thread's default_context()."""
+    calling thread's default_context().
+    rasterize_mode="antialiased": Mip-Splatting's opacity compensation, comp = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I)))
+    from the projection kernel (no constant in the divisor); the opacity every later stage sees --
+    and info["opacities"] -- is opacity * comp, and info["compensations"] is [1,N] (None in classic mode).
+    absgrad=True: after backward(), info["means2d"].absgrad is the [1,N,2] sum over pixels of the absolute per-pixel
+    screen-space gradients (AbsGS), overwritten by each backward; set only where a geometry gradient is produced."""
     rctx = context if context is not None else default_context()
     if tile_size != TILE:
         raise NotImplementedError("tile_size must be 16 (the gsplat default the reference relies on)")
-    if rasterize_mode != "classic" or camera_model != "pinhole" or covars is not None or distributed or absgrad:
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"unknown rasterize_mode {rasterize_mode!r} (\"classic\" or \"antialiased\")")
+    if not isinstance(absgrad, bool):
+        raise ValueError("absgrad must be True or False")
+    aa = rasterize_mode == "antialiased"
+    if camera_model != "pinhole" or covars is not None or distributed:
         raise NotImplementedError("only the options the reference uses are implemented "
-                                  "(classic mode, pinhole camera, quats+scales)")
+                                  "(pinhole camera, quats+scales, one process per view)")
     if render_mode not in ("RGB", "D", "ED", "RGB+D", "RGB+ED"):
         raise ValueError(f"unknown render_mode {render_mode}")
     if viewmats.dim() != 3 or viewmats.shape[0] != 1 or Ks.shape[0] != 1:
@@ -1126,27 +1205,33 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         raise ValueError("means [N,3], quats [N,4], scales [N,3] expected")
     if opacities.shape != (n,) and not (raw_params and opacities.shape == (n, 1)):  # (the stored logits are [N,1])
         raise ValueError("opacities [N] expected" + (" (or the stored [N,1] logits with raw_params)" if raw_params else ""))
-    _need_cuda(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds)
     width, height = int(width), int(height)
     viewmat, K = viewmats[0], Ks[0]
 
     # the final channel count -- after SH evaluation and the depth channel of RGB+D / RGB+ED -- and with it the route, once
     d, f16, needs = _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh_degree is not None,
-                                 render_mode, raw_params)
+                                 render_mode, raw_params, aa)
     route = _route(n, d, f16, needs, int(raster_flags), profiler.ENABLED, rctx.capacity_mode, rctx.early_rowmap,
-                   rctx.overlap_zero_fill, rctx.grad_range_hook is not None, rctx.trim_lists)
+                   rctx.overlap_zero_fill, rctx.grad_range_hook is not None, rctx.trim_lists, absgrad=absgrad)
+    _check_absgrad_route(route, d)  # (before any launch, and before the tensors are looked at: plain values decide it)
+    _need_cuda(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds)
 
-    records = None
+    records, compensations = None, None
     if raw_params:
-        radii, means2d, depths, conics, tiles, opacities, records = _ProjectRaw.apply(
+        radii, means2d, depths, conics, tiles, opacities, records, *comp = _ProjectRaw.apply(
             means, quats, scales, opacities, viewmat, K, width, height, float(eps2d), float(near_plane), float(far_plane),
-            float(radius_clip), float(scaling_modifier), route.records and n > 0)
+            float(radius_clip), float(scaling_modifier), route.records and n > 0, aa)
         if records.numel() == 0:
             records = None
+        if aa:  # (already folded into `opacities` and the records by the kernel)
+            compensations = comp[0]
     else:
-        radii, means2d, depths, conics, tiles = _Project.apply(means, quats, scales, viewmat, K, width, height,
-                                                               float(eps2d), float(near_plane), float(far_plane),
-                                                               float(radius_clip))
+        radii, means2d, depths, conics, tiles, *comp = _Project.apply(means, quats, scales, viewmat, K, width, height,
+                                                                      float(eps2d), float(near_plane), float(far_plane),
+                                                                      float(radius_clip), aa)
+        if aa:  # a torch multiply: autograd carries both factors
+            compensations = comp[0]
+            opacities = opacities * compensations
     # [1,N,2] node callers may retain_grad() on (gaussian_renderer/__init__.py:75-78); the
     # rasterizer consumes a view of it so its .grad receives d loss / d means2d.
     means2d_c = means2d[None]
@@ -1207,7 +1292,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
                 offs, flat = trimmed[0], trimmed[1]
         # any width in ONE rasterization: 513 = 512 CLIP channels + 1 (BASELINE.json configs[4] "512-d feat + granularity")
         # is four 128-channel slices and one lane of a narrow slice on the same matrix-core kernels, into one output tensor
-        r = _Rasterize.apply(means2d, conics, cols, opacities, bg, offs, flat, b.packed, width, height, route, rctx, prezero)
+        r = _Rasterize.apply(means2d, conics, cols, opacities, bg, offs, flat, b.packed, width, height, route, rctx, prezero,
+                             [means2d_c] if route.absgrad else None)
         if trimmed is not None:
             # last_ids are sorted indices: a COPY goes back to the full lists' numbering for the caller (the autograd node keeps
             # its own, which matches the lists it saved)
@@ -1246,7 +1332,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     info = {
         "camera_ids": None, "gaussian_ids": None,
         "radii": radii[None], "means2d": means2d_c, "depths": depths[None], "conics": conics[None],
-        "opacities": opacities[None], "tile_width": tile_w, "tile_height": tile_h,
+        "opacities": opacities[None], "compensations": None if compensations is None else compensations[None],
+        "tile_width": tile_w, "tile_height": tile_h,
         "tiles_per_gauss": tiles[None], "isect_ids": isect_ids, "flatten_ids": flatten_ids,
         "isect_offsets": isect_offsets[None], "last_ids": last_ids, "width": width, "height": height,
         "tile_size": TILE, "n_cameras": 1, "n_isects": n_isects,

@@ -357,11 +357,13 @@ class GaussianModel:
         if self.active_sh_degree < self.max_sh_degree:
             self.active_sh_degree += 1
 
-    def add_densification_stats(self, viewspace_point_tensor, update_filter, width, height):
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, width, height, absgrad=False):
         """accum += |grad scaled to the [-1, 1] screen|, denom += 1 over update_filter.  The reference also scales
-        viewspace_point_tensor.grad in place; nothing reads it afterwards, so it is left as it is."""
+        viewspace_point_tensor.grad in place; nothing reads it afterwards, so it is left as it is.
+        absgrad: read viewspace_point_tensor.absgrad (render(..., absgrad=True)) instead of .grad."""
         from . import densify
-        densify.stats(self, viewspace_point_tensor.grad, None, update_filter, None, width, height)
+        grad = densify.viewspace_gradient(viewspace_point_tensor, True) if absgrad else viewspace_point_tensor.grad
+        densify.stats(self, grad, None, update_filter, None, width, height)
 
     def update_max_radii(self, radii, visibility_filter):
         """train.py:209: max_radii2D[v] = max(max_radii2D[v], radii[v])."""

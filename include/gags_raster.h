@@ -84,6 +84,30 @@ int gags_project_fwd(int n, const float *means, const float *quats, const float 
                      int32_t *radii, float *means2d, float *depths, float *conics,
                      int32_t *tiles_per_gauss, void *stream);
 
+/* K1 + K4 in rasterize_mode "antialiased" (Mip-Splatting's opacity compensation; N16).  The rule, in fp32:
+ *   s00, s01, s11 = the 2-D covariance BEFORE eps2d is added;  det_o = s00 s11 - s01^2;  det_b = the blurred determinant
+ *   (s00 + eps2d)(s11 + eps2d) - s01^2;  compensations[i] = sqrt(max(0, det_o / det_b)), and 0 for a culled Gaussian (radius 0).
+ * No constant is added to the divisor.  The opacity that reaches the binning records, the raster forward and backward is
+ * fl(opacity * compensation): the caller multiplies (gags_project_fwd_aa), or the kernel does on the activated opacity,
+ * fl(fl(sigmoid(logit)) * compensation), in `opacities` and in the record it writes (gags_project_fwd_raw_aa).  Radius, conic,
+ * means2d, depth and tile count are those of gags_project_fwd / gags_project_fwd_raw bit for bit: the blurred covariance
+ * still decides them.  Same arguments as those entries plus compensations[N] (written in full).
+ * Backward: the exact derivative.  With r = det_o / det_b and (a, b, c) the conic, v_r = v_comp / (2 comp) where comp > 0, else
+ * 0, and
+ *   d r / d s00 = (1 - r) a - eps2d / det_b,   d r / d s11 = (1 - r) c - eps2d / det_b,   d r / d s01 = 2 (1 - r) b
+ * are added to the covariance cotangent built from v_conics.  gags_project_bwd_aa takes v_compensations[N] (NULL = zeros);
+ * gags_project_bwd_raw_aa takes v_opacities as the cotangent of the COMPENSATED opacity: v_comp = v_opacities * sigmoid(logit),
+ * and v_opacity_logit gets the extra factor comp (0 for a culled Gaussian). */
+int gags_project_fwd_aa(int n, const float *means, const float *quats, const float *scales,
+                        const float *viewmat, const float *K, int width, int height,
+                        float eps2d, float near_plane, float far_plane, float radius_clip,
+                        int32_t *radii, float *means2d, float *depths, float *conics,
+                        int32_t *tiles_per_gauss, float *compensations, void *stream);
+int gags_project_bwd_aa(int n, const float *means, const float *quats, const float *scales,
+                        const float *viewmat, const float *K, int width, int height, float eps2d,
+                        const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
+                        const float *v_compensations, float *v_means, float *v_quats, float *v_scales, void *stream);
+
 /* K5: inclusive prefix sum of tiles_per_gauss -> cum[N]; the grand total (n_isects) is
  * also written to total[0], or -1 when it does not fit an int32 (the caller must refuse the view; the entries of cum
  * behind the wrap are then unspecified).  Every entry must lie in [0, 2^20): the 2048 entries one workgroup sums then fit an
@@ -213,6 +237,20 @@ int gags_raster_bwd(int d, int width, int height, const float *means2d, const fl
                     float *v_colors, float *v_opacities, float *v_means2d, float *v_conics,
                     int flags, void *stream);
 
+/* K10 with absgrad (AbsGS; N16): gags_raster_bwd's arguments plus v_means2d_abs[N,2], zero-filled by the caller like the
+ * others.  The rule: absgrad[g] = SUM over pixels of (|g3|, |g4|), g3 / g4 being the pixel's v_means2d terms over ALL of its
+ * channels, before any reduction across pixels; zero for a Gaussian that blended nowhere.  Defined only where one channel chunk
+ * covers D (D <= 32): above that the kernel splits the per-pixel total over chunks, and an absolute value of a partial is not
+ * the rule -- GAGS_EINVAL for D > 32 (or GAGS_BWD_COLORS_ONLY) with a non-NULL pointer.  NULL: gags_raster_bwd itself. */
+int gags_raster_bwd_abs(int d, int width, int height, const float *means2d, const float *conics,
+                        const float *opacities, const float *colors, const float *backgrounds,
+                        const int32_t *isect_offsets, const int32_t *flatten_ids, int64_t n_isects,
+                        const void *packed /* from gags_pack_isects, or NULL */,
+                        const float *render_alphas, const int32_t *last_ids,
+                        const float *v_render_colors, const float *v_render_alphas,
+                        float *v_colors, float *v_opacities, float *v_means2d, float *v_conics, float *v_means2d_abs,
+                        int flags, void *stream);
+
 /* K10, staged flavour: colours-only backward WITHOUT atomics (deterministic), 16 <= D <= 1024 (any such D).
  * Consumes the scratch + blk_rows of a split gags_raster_fwd.
  *
@@ -229,7 +267,9 @@ int gags_bwd_rowmap(int64_t n_isects, int width, int height, const int32_t *isec
                     const void *fwd_scratch, int64_t fwd_scratch_bytes, int32_t *rowmap, int64_t rowmap_elems,
                     int32_t *total, void *scratch, int64_t scratch_bytes, void *stream);
 /* K10, geometry part at wide D (D >= 32, D % 8 == 0) after a split gags_raster_fwd: v_geo[N][8] =
- * (v_conics[3], v_means2d[2], v_opacities[1], 0, 0) per Gaussian, written in full, no atomics, deterministic.
+ * (v_conics[3], v_means2d[2], v_opacities[1], A, A) per Gaussian, written in full, no atomics, deterministic.  A = (0, 0), or
+ * with flags bit GAGS_GEOM_ABSGRAD the absgrad of gags_raster_bwd_abs: SUM over pixels of (|g3|, |g4|), the per-pixel v_means2d
+ * terms over all channels (both dot passes and every D the entry serves; the dot products are complete before the scalar pass).
  * The D-proportional work -- <colors[g], v_render_colors[px]> for every (slot, pixel) of the forward -- runs on the
  * matrix cores: by default the 16-bit ones with split operands (feature rows and cotangent as two fp16 terms each after
  * exact power-of-two scalings -- one per Gaussian row, one per 8x8 block -- and three product terms: as close to float64 as
@@ -246,6 +286,7 @@ int gags_bwd_rowmap(int64_t n_isects, int width, int height, const int32_t *isec
  * the forward's sparse slot space (~1.1 KB per tile intersection and pass); + 1.5 KB per Gaussian for the split table.
  * Returns 1 when D is not eligible. */
 #define GAGS_GEOM_F32MFMA 32 /* gags_raster_bwd_geom's `flags`, next to GAGS_RECS_BY_GAUSSIAN */
+#define GAGS_GEOM_ABSGRAD 0x40 /* gags_raster_bwd_geom's `flags`: columns 6, 7 of v_geo carry absgrad (N16) */
 int64_t gags_raster_bwd_geom_scratch_bytes(int64_t n_isects, int width, int height, int n, int d, int64_t n_rows);
 int gags_raster_bwd_geom(int d, int n, int width, int height, const float *colors, const float *backgrounds,
                          const int32_t *isect_offsets, int64_t n_isects, const void *packed,
@@ -364,6 +405,19 @@ int gags_project_bwd_raw(int n, const float *means, const float *rotation, const
                          int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
                          const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
                          float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream);
+/* ... in rasterize_mode "antialiased" (the rule stands at gags_project_fwd_aa): compensations[N] is one more output, and
+ * `opacities` and the records carry fl(fl(sigmoid(logit)) * compensation). */
+int gags_project_fwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
+                            const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                            int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
+                            int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
+                            float *opacities, float *quats_act, float *scales_act, void *grec, float *compensations,
+                            void *stream);
+int gags_project_bwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
+                            const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                            int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                            const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
+                            float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream);
 
 /* K2: projection backward: chain rule of gags_project_fwd for Gaussians with radii>0.
  * Inputs v_means2d[N,2], v_depths[N] (may be NULL), v_conics[N,3];
