@@ -100,7 +100,7 @@ def reduce_feature_grad(grad, mode="rs_ag", average=False, bucket_bytes=BUCKET_B
     # c10d collectives write their tensors without moving torch's version counter (all_reduce, reduce_scatter_tensor into
     # a slice under GAGS_DIST_INPLACE=1; all_gather_into_tensor and copy_ happen to move it).  `grad` now holds other ranks'
     # rows: whoever trusts "unchanged since I handed it out" on the counter -- the persistent gradient buffer of the staged
-    # backward (rasterization._KeptGrad), OverlappedGradReducer's adoption check -- is told here, whatever the branch above
+    # backward (raster_context._KeptGrad), OverlappedGradReducer's adoption check -- is told here, whatever the branch above
     from .rasterization import grad_written
     grad_written(grad)
     return grad
@@ -187,8 +187,7 @@ def _pack_rows(grad, idx, c0, c1, wire_dtype):
     from . import _lib
     wire = torch.empty(rows, c1 - c0, dtype=wire_dtype, device=grad.device)
     _lib.check(_lib.load().gags_pack_rows(rows, _lib.ptr(idx), _lib.ptr(grad), _TYPE[grad.dtype], grad.shape[1], c0,
-                                          c1 - c0, _lib.ptr(wire), _TYPE[wire_dtype],
-                                          torch.cuda.current_stream().cuda_stream), "gags_pack_rows")
+                                          c1 - c0, _lib.ptr(wire), _TYPE[wire_dtype], _lib.stream()), "gags_pack_rows")
     return wire
 
 
@@ -207,8 +206,8 @@ def _unpack_rows(grad, idx, c0, c1, wire, local=None):
     from . import _lib
     rows = grad.shape[0] if idx is None else idx.numel()
     _lib.check(_lib.load().gags_unpack_rows(rows, _lib.ptr(idx), _lib.ptr(wire), _TYPE[wire.dtype], _lib.ptr(local),
-                                            _lib.ptr(grad), _TYPE[grad.dtype], grad.shape[1], c0, c1 - c0,
-                                            torch.cuda.current_stream().cuda_stream), "gags_unpack_rows")
+                                            _lib.ptr(grad), _TYPE[grad.dtype], grad.shape[1], c0, c1 - c0, _lib.stream()),
+               "gags_unpack_rows")
 
 
 class OverlappedGradReducer:
@@ -369,10 +368,9 @@ class OverlappedGradReducer:
         pos = torch.empty(max(n, 1), dtype=torch.int32, device=dev)  # the inverse: position of row g in idx, or -1
         count = torch.empty(1, dtype=torch.int32, device=dev)
         sb = lib.gags_compact_mask_scratch_bytes(n)
-        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+        scratch = _lib.scratch(sb, dev)
         _lib.check(lib.gags_compact_mask_pos(n, _lib.ptr(mask), cap, _lib.ptr(idx), _lib.ptr(pos), _lib.ptr(count),
-                                             _lib.ptr(scratch), sb, torch.cuda.current_stream().cuda_stream),
-                   "gags_compact_mask_pos")
+                                             _lib.ptr(scratch), sb, _lib.stream()), "gags_compact_mask_pos")
         self._pos = pos
         self._union_ev = torch.cuda.Event()
         self._union_ev.record()  # (on the exchange stream: the backward's reduce stage waits for it before it reads `pos`)

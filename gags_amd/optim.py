@@ -46,7 +46,7 @@ class FeatureAdam(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["step"] += 1
                 with torch.cuda.device(p.device):
-                    stream = torch.cuda.current_stream(p.device).cuda_stream
+                    stream = _lib.stream(p.device)
                     _lib.check(lib.gags_adam_step(p.numel(), _lib.ptr(p), _lib.ptr(g), _lib.ptr(st["exp_avg"]),
                                                   _lib.ptr(st["exp_avg_sq"]), float(group["lr"]), float(b1), float(b2),
                                                   float(group["eps"]), int(st["step"].item()), stream),

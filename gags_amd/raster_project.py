@@ -1,0 +1,163 @@
+"""The autograd functions in front of the rasterizer: projection of the activated (_Project) or the stored (_ProjectRaw)
+parameters, and SH colour (_SH)."""
+import torch
+
+from . import _lib, profiler
+from ._lib import check, ptr
+
+
+def _c(t):
+    return t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
+
+
+class _Project(torch.autograd.Function):
+    """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
+    cotangent in the backward (gags_project_fwd_aa / gags_project_bwd_aa); the caller multiplies them into the opacities."""
+
+    @staticmethod
+    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False):
+        lib = _lib.load()
+        means, quats, scales, viewmat, K = _c(means), _c(quats), _c(scales), _c(viewmat), _c(K)
+        n = means.shape[0]
+        dev = means.device
+        radii = torch.empty(n, dtype=torch.int32, device=dev)
+        means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        depths = torch.empty(n, dtype=torch.float32, device=dev)
+        conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        tiles = torch.empty(n, dtype=torch.int32, device=dev)
+        comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
+        entry, name = (lib.gags_project_fwd_aa, "gags_project_fwd_aa") if aa else (lib.gags_project_fwd, "gags_project_fwd")
+        with profiler.stage("project_fwd"):
+            check(entry(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height, eps2d, near, far,
+                        radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(tiles),
+                        *((ptr(comp),) if aa else ()), _lib.stream()), name)
+        ctx.save_for_backward(means, quats, scales, viewmat, K, radii, conics)
+        ctx.cfg = (width, height, eps2d, aa)
+        ctx.mark_non_differentiable(radii, tiles)
+        if aa:
+            return radii, means2d, depths, conics, tiles, comp
+        return radii, means2d, depths, conics, tiles
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_comp=None):
+        lib = _lib.load()
+        means, quats, scales, viewmat, K, radii, conics = ctx.saved_tensors
+        width, height, eps2d, aa = ctx.cfg
+        n = means.shape[0]
+        dev = means.device
+        v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
+        v_conics = torch.zeros(n, 3, device=dev) if v_conics is None else _c(v_conics)
+        v_depths = None if v_depths is None else _c(v_depths)
+        v_means = torch.empty(n, 3, device=dev)
+        v_quats = torch.empty(n, 4, device=dev)
+        v_scales = torch.empty(n, 3, device=dev)
+        if aa:
+            v_comp = None if v_comp is None else _c(v_comp)
+            check(lib.gags_project_bwd_aa(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
+                                          eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_comp),
+                                          ptr(v_means), ptr(v_quats), ptr(v_scales), _lib.stream()), "gags_project_bwd_aa")
+        else:
+            check(lib.gags_project_bwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
+                                       eps2d, ptr(radii), ptr(conics), ptr(v_means2d), ptr(v_depths), ptr(v_conics),
+                                       ptr(v_means), ptr(v_quats), ptr(v_scales), _lib.stream()), "gags_project_bwd")
+        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None, None
+
+
+class _ProjectRaw(torch.autograd.Function):
+    """K1 + K4 on the STORED parameters (gags_project_fwd_raw / gags_project_bwd_raw): the getters of
+    scene/gaussian_model.py:116-139 -- exp, F.normalize, sigmoid -- and render()'s `* scaling_modifier` run inside the
+    projection kernel, bit for bit as torch evaluates them; the backward returns gradients of the stored parameters.
+    aa (rasterize_mode "antialiased"): the kernel folds the compensation into the activated opacity and the record
+    (gags_project_fwd_raw_aa), the compensations [N] are one more -- non-differentiable -- output, and the backward takes the
+    compensation's cotangent from the opacity's (gags_project_bwd_raw_aa)."""
+
+    @staticmethod
+    def forward(ctx, means, rotation, scaling_log, opacity_logit, viewmat, K, width, height, eps2d, near, far, radius_clip,
+                scaling_modifier, want_records, aa=False):
+        lib = _lib.load()
+        means, rotation, scaling_log, viewmat, K = _c(means), _c(rotation), _c(scaling_log), _c(viewmat), _c(K)
+        logit = _c(opacity_logit.reshape(-1))
+        n = means.shape[0]
+        dev = means.device
+        radii = torch.empty(n, dtype=torch.int32, device=dev)
+        means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        depths = torch.empty(n, dtype=torch.float32, device=dev)
+        conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        tiles = torch.empty(n, dtype=torch.int32, device=dev)
+        opac = torch.empty(n, dtype=torch.float32, device=dev)
+        # the per-Gaussian records of the matrix-core raster kernels (K8b), written on the way: no record kernel in the binning
+        grec = torch.empty(max(n, 1), 8, dtype=torch.float32, device=dev) if want_records else torch.empty(0, device=dev)
+        comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
+        entry, name = ((lib.gags_project_fwd_raw_aa, "gags_project_fwd_raw_aa") if aa
+                       else (lib.gags_project_fwd_raw, "gags_project_fwd_raw"))
+        with profiler.stage("project_fwd"):
+            check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier, ptr(viewmat), ptr(K),
+                        width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
+                        ptr(tiles), ptr(opac), None, None, ptr(grec) if want_records else None,
+                        *((ptr(comp),) if aa else ()), _lib.stream()), name)
+        ctx.save_for_backward(means, rotation, scaling_log, logit, viewmat, K, radii)
+        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa)
+        if aa:
+            ctx.mark_non_differentiable(radii, tiles, grec, comp)
+            return radii, means2d, depths, conics, tiles, opac, grec, comp
+        ctx.mark_non_differentiable(radii, tiles, grec)
+        return radii, means2d, depths, conics, tiles, opac, grec
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_opac, _v_grec, _v_comp=None):
+        lib = _lib.load()
+        means, rotation, scaling_log, logit, viewmat, K, radii = ctx.saved_tensors
+        width, height, eps2d, modifier, oshape, aa = ctx.cfg
+        n = means.shape[0]
+        dev = means.device
+        v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
+        v_conics = torch.zeros(n, 3, device=dev) if v_conics is None else _c(v_conics)
+        v_depths = None if v_depths is None else _c(v_depths)
+        v_opac = None if v_opac is None else _c(v_opac)
+        v_means = torch.empty(n, 3, device=dev)
+        v_rot = torch.empty(n, 4, device=dev)
+        v_scal = torch.empty(n, 3, device=dev)
+        v_logit = torch.empty(n, device=dev) if ctx.needs_input_grad[3] else None
+        entry, name = ((lib.gags_project_bwd_raw_aa, "gags_project_bwd_raw_aa") if aa
+                       else (lib.gags_project_bwd_raw, "gags_project_bwd_raw"))
+        check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), modifier, ptr(viewmat),
+                    ptr(K), width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths),
+                    ptr(v_conics), ptr(v_opac), ptr(v_means), ptr(v_rot), ptr(v_scal), ptr(v_logit),
+                    _lib.stream()), name)
+        return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), None, None, None, None, None,
+                None, None, None, None, None, None)
+
+
+class _SH(torch.autograd.Function):
+    """K3: SH colour and its backward: coefficients, and -- when positions are trainable -- the view direction
+    (d colour / d means through normalize(mean - campos), as gsplat propagates it)."""
+
+    @staticmethod
+    def forward(ctx, coeffs, means, campos, radii, degree):
+        lib = _lib.load()
+        coeffs, means, campos = _c(coeffs), _c(means), _c(campos)
+        n, kc = coeffs.shape[0], coeffs.shape[1]
+        out = torch.empty(n, 3, device=coeffs.device)
+        check(lib.gags_sh_fwd(n, kc, degree, ptr(means), ptr(campos), ptr(coeffs), ptr(radii), ptr(out), _lib.stream()),
+              "gags_sh_fwd")
+        ctx.save_for_backward(means, campos, radii, out, coeffs if ctx.needs_input_grad[1] else None)
+        ctx.cfg = (kc, degree)
+        return out
+
+    @staticmethod
+    def backward(ctx, v_out):
+        lib = _lib.load()
+        means, campos, radii, out, coeffs = ctx.saved_tensors
+        kc, degree = ctx.cfg
+        n = means.shape[0]
+        v_out = _c(v_out)
+        v_coeffs = v_means = None
+        if ctx.needs_input_grad[0]:
+            v_coeffs = torch.empty(n, kc, 3, device=means.device)
+            check(lib.gags_sh_bwd(n, kc, degree, ptr(means), ptr(campos), ptr(radii), ptr(out), ptr(v_out),
+                                  ptr(v_coeffs), _lib.stream()), "gags_sh_bwd")
+        if ctx.needs_input_grad[1]:
+            v_means = torch.empty(n, 3, device=means.device)
+            check(lib.gags_sh_bwd_dirs(n, kc, degree, ptr(means), ptr(campos), ptr(coeffs), ptr(radii), ptr(out),
+                                       ptr(v_out), ptr(v_means), _lib.stream()), "gags_sh_bwd_dirs")
+        return v_coeffs, v_means, None, None, None

@@ -1,5 +1,7 @@
 """Shared input builders for the parity tests (seeded, CPU-generated so that the oracle and
 the GPU see bit-identical inputs)."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -101,6 +103,28 @@ def rel_l2(a, b):
 
 def to_dev(a, dev="cuda"):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+@contextlib.contextmanager
+def spy_entries(*names):
+    """Counting spies on entries of the loaded library (the pattern of tests/test_route_gpu.py): yields the list that
+    receives (name, args) of every call, in order.  For A/B tests that must show that B ran."""
+    from gags_amd import _lib
+    lib, calls = _lib.load(), []
+    real = {name: getattr(lib, name) for name in names}
+
+    def spy(name):
+        def f(*args):
+            calls.append((name, args))
+            return real[name](*args)
+        return f
+    for name in names:
+        setattr(lib, name, spy(name))
+    try:
+        yield calls
+    finally:
+        for name in names:
+            setattr(lib, name, real[name])
 
 
 # The default forward of an fp32 table contracts its 128-channel slices on the 16-bit matrix cores with both operands split

@@ -290,7 +290,7 @@ def test_stage_bits_of_the_staged_backward_agree_with_the_header():
 def test_forward_and_backward_flags_agree_with_the_header():
     """Every forward / backward flag #define of the header against its mirror in gags_amd/_lib.py.  One mirror has a name of its
     own: the header's GAGS_FWD_F16MFMA (64) is _lib.GAGS_FWD_F16MFMA_C, because _lib.GAGS_FWD_F16MFMA is the PUBLIC request bit
-    (128; 64 was taken by the python-side GAGS_BWD_F32MFMA) that rasterization._fwd_flags translates."""
+    (128; 64 was taken by the python-side GAGS_BWD_F32MFMA) that raster_route._fwd_flags translates."""
     from gags_amd import _lib
     src = open(os.path.join(ROOT, "include", "gags_raster.h")).read()
     defs = {k: int(v) for k, v in re.findall(r"^#define\s+(GAGS_(?:BWD|FWD|FEAT|RECS)_\w+)\s+(\d+)\b", src, flags=re.M)}

@@ -139,7 +139,7 @@ def test_channel_sharded_step_two_ranks():
 
 
 def _overlap_worker(rank, world, port, wire, q):
-    """OverlappedGradReducer fed range by range the way the staged backward feeds it (gags_amd/rasterization.py):
+    """OverlappedGradReducer fed range by range the way the staged backward feeds it (gags_amd/raster_staged.py):
     exact fp32 sum on the default wire; bfloat16 wire within its stated bound; and every way autograd may hand the
     gradient on -- adopted, copied, accumulated onto an existing gradient, behind a dtype cast -- must end with the
     sum over the ranks ONCE (a copied gradient used to be reduced a second time)."""
@@ -354,7 +354,7 @@ def test_geometry_gradients_reduce_as_one_packed_block_two_ranks():
 
 
 def _kept_backward(ctx, n, d, rows, values):
-    """What the staged colours-only backward does with the persistent gradient buffer (rasterization._KeptGrad), on the host:
+    """What the staged colours-only backward does with the persistent gradient buffer (raster_context._KeptGrad), on the host:
     the rows this view has are written, the rows flagged by the previous step and absent now are zeroed, no other row is
     touched, the flags are recorded for the next step -- all through `.data`, as the kernels write through raw pointers."""
     alias, prev, cur = ctx.kept_grad(n, d, torch.float32, torch.device("cpu"))

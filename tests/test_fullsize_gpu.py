@@ -272,7 +272,7 @@ def test_c5_heavy_splats_on_a_tile_sample(oracle):
     if free < 100 * 2 ** 30:
         pytest.skip(f"needs ~60 GiB of device memory (free: {free / 2 ** 30:.0f} GiB)")
     # (until round 6 this view needed ~200 GiB: 1 KB of forward scratch per list entry.  Its lists are now cut to what their
-    # tiles read before saturation -- gags_amd.rasterization._trim_lists, automatic above 48 GiB of scratch: 169 M -> 1.5 M)
+    # tiles read before saturation -- gags_amd.raster_binning._trim_lists, automatic above 48 GiB of scratch: 169 M -> 1.5 M)
     st = _heavy_tile_sample(oracle, c["n"], c["width"], c["height"], 512, step=32, fp16_table=True, min_isects_per_visible=30)
     print("C5H:", st)
     assert st["n_isects"] > (1 << 27)

@@ -152,7 +152,7 @@ def test_bench_dump_keeps_small_arrays_whole_and_samples_the_same_rows_of_large_
 
 
 def test_an_unused_row_map_recycles_its_pinned_word_only_when_the_copy_has_landed():
-    """rasterization._EarlyRowmap (a forward enqueues the backward's row map and sends its count to a pinned word): a forward
+    """raster_staged._EarlyRowmap (a forward enqueues the backward's row map and sends its count to a pinned word): a forward
     that is never differentiated returns the word to the context's pool from __del__ -- but only when the event behind the
     copy has completed.  A word whose copy may still be in flight is dropped: handed to the next forward it could be
     overwritten by the older count after the newer one arrived.  rows() waits for the event first and recycles.  Plain Python

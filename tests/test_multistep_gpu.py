@@ -1,7 +1,7 @@
 """State carried from one training step to the next, against a recomputation that carries none.
 
 The product is a loop of tens of thousands of steps; between two of them the Python layer keeps a persistent gradient buffer
-and its flag arrays (rasterization._KeptGrad), the row map a forward enqueues for its backward (_EarlyRowmap) and its pool of
+and its flag arrays (raster_context._KeptGrad), the row map a forward enqueues for its backward (_EarlyRowmap) and its pool of
 pinned words, packed 16-bit decoder weights (decoders._PACK_CACHE), a bound on the segment ids (losses._NSEG_CACHE) and the
 optimizer's moments (optim.FeatureAdam) -- each trusted on identity, address, version counter or a reference count.  Every
 test here runs K steps with all of that at its default, snapshots the inputs of each step, and compares what the step
@@ -20,6 +20,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from helpers import spy_entries
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -128,7 +130,7 @@ def test_twelve_steps_equal_the_stateless_step_bit_for_bit(oracle, monkeypatch, 
     extra channel rides with the float4 columns), an fp16 table behind its fp32 master, and 256 with PROW_MAX_BYTES at 0 so that
     the kept buffer is written one 128-channel range at a time (the "narrow" path of the staged backward).  The mechanism
     under test is asserted to have been on: one buffer over all steps, no step counted as a failure."""
-    from gags_amd import rasterization as R, synthetic as syn
+    from gags_amd import _lib, raster_tunables as T, rasterization as R, synthetic as syn
     from gags_amd.gaussian_renderer import render
     from gags_amd.optim import FeatureAdam
     n, w, h = 6000, 200, 138
@@ -148,11 +150,17 @@ def test_twelve_steps_equal_the_stateless_step_bit_for_bit(oracle, monkeypatch, 
         st = opt.state[p]
         m0 = st["exp_avg"].detach().cpu().numpy().copy() if len(st) else np.zeros((n, d), np.float32)
         v0 = st["exp_avg_sq"].detach().cpu().numpy().copy() if len(st) else np.zeros((n, d), np.float32)
-        with monkeypatch.context() as mp:
+        with monkeypatch.context() as mp, spy_entries("gags_raster_bwd_colors_staged") as staged:
             if narrow:
-                mp.setattr(R, "PROW_MAX_BYTES", 0)
+                mp.setattr(T, "PROW_MAX_BYTES", 0)
             (render(cams[view], pc, None, bg, feature_mode=True, context=ctx)["render"] * G).sum().backward()
-        want = _stateless_feature_grad(pc, feat0, view, G, w, h)
+        # (argument 15: the stage word, 17: the channel width) the range-sized scratch in every call of the narrow case, in none else
+        ranged = [bool(a[15] & _lib.GAGS_STAGED_RANGE_SCRATCH) for _, a in staged]
+        assert ranged and all(r == narrow for r in ranged), (case, t, ranged)
+        assert not narrow or all(a[17] == 128 for _, a in staged), (case, t)
+        with spy_entries("gags_raster_bwd_colors_staged") as staged:
+            want = _stateless_feature_grad(pc, feat0, view, G, w, h)
+        assert staged and not any(a[15] & _lib.GAGS_STAGED_RANGE_SCRATCH for _, a in staged), (case, t)
         got = p.grad
         assert got.dtype == torch.float32 and torch.equal(got, want), (case, t, view, float((got - want).abs().max()))
         rows_seen.append((want != 0).any(1))
@@ -184,11 +192,11 @@ def test_changing_shapes_evaluation_and_geometry_steps_within_one_context(oracle
     that is rendered with a graph and dropped (evaluation inside the loop: its _EarlyRowmap is released unused) between two
     trained steps, then a step with geometry gradients on (full backward) between two colours-only steps.  Same assertions as
     above per step, for the model that stepped."""
-    from gags_amd import rasterization as R, synthetic as syn
+    from gags_amd import raster_tunables as T, rasterization as R, synthetic as syn
     from gags_amd.gaussian_renderer import render
     w, h = 160, 112
     shapes = {"A": (3000, 64), "B": (2500, 128), "C": (2000, 32), "A2": (3600, 64)}
-    assert len(shapes) > R.KEEP_GRAD_SHAPES
+    assert len(shapes) > T.KEEP_GRAD_SHAPES
     models, opts, Gs, steps = {}, {}, {}, {}
     for i, (k, (n, d)) in enumerate(shapes.items()):
         models[k] = _make_model(n, d, w, h, seed=20 + i, mult=5)
@@ -225,7 +233,7 @@ def test_changing_shapes_evaluation_and_geometry_steps_within_one_context(oracle
         np.testing.assert_array_equal(st["exp_avg"].cpu().numpy(), m0)
         np.testing.assert_array_equal(st["exp_avg_sq"].cpu().numpy(), v0)
         np.testing.assert_array_equal(p.detach().cpu().numpy(), po)
-        assert len(ctx._kept) <= R.KEEP_GRAD_SHAPES
+        assert len(ctx._kept) <= T.KEEP_GRAD_SHAPES
 
     for i, k in enumerate("ABCABCA"):           # rotation over three shapes
         trained_step(k, view=(3 * i + 1) % 8)

@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import FWD_SPLIT_TOL, check_forward, rel_l2, scene_arrays, to_dev
+from helpers import FWD_SPLIT_TOL, check_forward, rel_l2, scene_arrays, spy_entries, to_dev
+
+STAGED = "gags_raster_bwd_colors_staged"  # argument 15: the stage word, 17: the channel width of the call
 
 pytestmark = pytest.mark.gpu
 
@@ -357,26 +359,30 @@ def test_backward_kernels_on_both_matrix_pipes_are_within_tolerance(oracle):
 def test_sparse_reduce_with_overlapped_zero_fill_is_bit_identical(oracle):
     """Stage bit 128 of gags_raster_bwd_colors_staged (the gradient arrives zero-filled -- here by the opt-in overlap of
     RasterContext.overlap_zero_fill -- and the reduce stage skips the Gaussians that blended nothing): same bits as the dense reduce,
-    every culled / unblended row exactly zero, for fp32 and fp16 gradients and an odd width."""
-    from gags_amd import rasterization as R
+    every culled / unblended row exactly zero, for fp32 and fp16 gradients and an odd width.  That the two runs differ in
+    that bit is read off the stage word of every staged call."""
+    from gags_amd import _lib, raster_tunables as T, rasterization as R
     for d, half in ((256, False), (513, False), (128, True)):
         n, w, h = 5000, 176, 130
         s = scene_arrays(n, d, w, h, seed=33, view=3, scale_mult=5.0)
         v_out = np.random.default_rng(11).standard_normal((h, w, d)).astype(np.float32)
         res = []
         for overlap in (True, False):
-            rctx, old_min = R.RasterContext(overlap_zero_fill=overlap), R.ZERO_FILL_MIN_ELEMS
-            R.ZERO_FILL_MIN_ELEMS = 0
+            rctx, old_min = R.RasterContext(overlap_zero_fill=overlap), T.ZERO_FILL_MIN_ELEMS
+            T.ZERO_FILL_MIN_ELEMS = 0
             try:
                 cols = torch.from_numpy(s["colors"]).cuda()
                 cols = (cols.half() if half else cols).requires_grad_(True)
-                out, _, info = R.rasterization(to_dev(s["means"]), to_dev(s["quats"]), to_dev(s["scales"]), to_dev(s["opacities"]),
-                                               cols, to_dev(s["viewmat"])[None], to_dev(s["K"])[None], w, h, context=rctx)
-                (out[0] * to_dev(v_out)).sum().backward()
-                torch.cuda.synchronize()
+                with spy_entries(STAGED) as calls:
+                    out, _, info = R.rasterization(to_dev(s["means"]), to_dev(s["quats"]), to_dev(s["scales"]),
+                                                   to_dev(s["opacities"]), cols, to_dev(s["viewmat"])[None], to_dev(s["K"])[None],
+                                                   w, h, context=rctx)
+                    (out[0] * to_dev(v_out)).sum().backward()
+                    torch.cuda.synchronize()
                 res.append(cols.grad.clone())
             finally:
-                R.ZERO_FILL_MIN_ELEMS = old_min
+                T.ZERO_FILL_MIN_ELEMS = old_min
+            assert calls and all(bool(a[15] & _lib.GAGS_STAGED_PREZEROED) == overlap for _, a in calls), (d, half, overlap)
         assert torch.equal(res[0], res[1]), (d, half)
         assert bool((res[0][info["radii"][0] == 0] == 0).all())
 
@@ -425,7 +431,7 @@ def test_capacity_mode_keeps_the_counts_on_the_device_and_changes_nothing(oracle
             if isinstance(a, np.ndarray):
                 np.testing.assert_array_equal(a, b)
     # the two overflows fell back to the exact path: the row count's through gags_read_i32, the intersection count's through
-    # the early pinned copy of tile_binning (round 6: summed and sent before the depth sort, rasterization.EARLY_COUNT)
+    # the early pinned copy of tile_binning (round 6: summed and sent before the depth sort, raster_tunables.EARLY_COUNT)
     assert len(calls) >= 1
 
 
@@ -469,27 +475,34 @@ def test_backward_by_channel_ranges_is_bit_identical(oracle):
 
 def test_backward_through_a_range_sized_scratch_is_bit_identical(oracle):
     """Stage bit 256 of the staged backward (heavy views: the partial rows of ONE 128-channel range at a time through a
-    [rows, 128] scratch instead of [rows, D]; rasterization.PROW_MAX_BYTES decides): same kernels, same order of summation,
-    so the same bits as the one-shot backward -- fp32 and fp16 gradients."""
-    from gags_amd import rasterization as R
+    [rows, 128] scratch instead of [rows, D]; raster_tunables.PROW_MAX_BYTES decides): same kernels, same order of summation,
+    so the same bits as the one-shot backward -- fp32 and fp16 gradients.  With the limit at 0 every staged call carries the bit
+    and 128 channels; with the default limit none does."""
+    from gags_amd import _lib, raster_tunables as T, rasterization as R
     n, w, h = 5000, 192, 144
     for d, half in ((384, False), (256, True)):
         s = scene_arrays(n, d, w, h, seed=43, view=3, scale_mult=5.0)
         v_out = np.random.default_rng(9).standard_normal((h, w, d)).astype(np.float32)
         res = []
-        saved = R.PROW_MAX_BYTES
+        saved = T.PROW_MAX_BYTES
         for limit in (saved, 0):
-            R.PROW_MAX_BYTES = limit
+            T.PROW_MAX_BYTES = limit
             try:
                 cols = torch.from_numpy(s["colors"]).cuda()
                 cols = (cols.half() if half else cols).requires_grad_(True)
-                out, _, _ = R.rasterization(to_dev(s["means"]), to_dev(s["quats"]), to_dev(s["scales"]), to_dev(s["opacities"]), cols,
-                                            to_dev(s["viewmat"])[None], to_dev(s["K"])[None], w, h)
-                (out[0] * to_dev(v_out)).sum().backward()
-                torch.cuda.synchronize()
+                with spy_entries(STAGED) as calls:
+                    out, _, _ = R.rasterization(to_dev(s["means"]), to_dev(s["quats"]), to_dev(s["scales"]), to_dev(s["opacities"]),
+                                                cols, to_dev(s["viewmat"])[None], to_dev(s["K"])[None], w, h)
+                    (out[0] * to_dev(v_out)).sum().backward()
+                    torch.cuda.synchronize()
                 res.append(cols.grad.clone())
             finally:
-                R.PROW_MAX_BYTES = saved
+                T.PROW_MAX_BYTES = saved
+            assert calls, (d, half, limit)
+            if limit == 0:
+                assert all(a[15] & _lib.GAGS_STAGED_RANGE_SCRATCH and a[17] == 128 for _, a in calls), (d, half)
+            else:
+                assert not any(a[15] & _lib.GAGS_STAGED_RANGE_SCRATCH for _, a in calls), (d, half)
         assert torch.equal(res[0], res[1]), (d, half)
 
 
@@ -618,20 +631,30 @@ def test_full_backward_with_more_than_1024_slots_in_one_block(oracle):
 def test_wide_geometry_backward_in_the_sparse_slot_numbering():
     """gags_raster_bwd_geom with row_base = NULL (rows and dot products live in the forward's sparse slot space: no prefix
     sum, no readback, ~6x the keys to sort) gives the same gradients, bit for bit, as the compact numbering the wrapper
-    uses -- the sums run over the same rows in the same order."""
-    from gags_amd import rasterization as R
+    uses -- the sums run over the same rows in the same order.  Which numbering a run used is read off the entry's arguments
+    (18: row_base, 19: n_rows)."""
+    from gags_amd import raster_tunables as T
     n, w, h, d = 2000, 112, 80, 328
     s = scene_arrays(n, d, w, h, seed=34, view=2, scale_mult=5.0)
     rng = np.random.default_rng(10)
     v_out = rng.standard_normal((h, w, d)).astype(np.float32)
     v_alpha = rng.standard_normal((h, w)).astype(np.float32)
     bg = np.full(d, 0.2, np.float32)
-    _, _, _, g_c = _run_gpu(s, w, h, s["colors"], bg, need_geom=True, v_out=v_out, v_alpha=v_alpha)
-    R.GEOM_COMPACT_ROWS = False
+
+    def sparse(args):
+        return (args[18] is None or not args[18].value, args[19] == -1)
+
+    with spy_entries("gags_raster_bwd_geom") as compact:
+        _, _, _, g_c = _run_gpu(s, w, h, s["colors"], bg, need_geom=True, v_out=v_out, v_alpha=v_alpha)
+    assert T.GEOM_COMPACT_ROWS is True
+    T.GEOM_COMPACT_ROWS = False
     try:
-        _, _, _, g_s = _run_gpu(s, w, h, s["colors"], bg, need_geom=True, v_out=v_out, v_alpha=v_alpha)
+        with spy_entries("gags_raster_bwd_geom") as slots:
+            _, _, _, g_s = _run_gpu(s, w, h, s["colors"], bg, need_geom=True, v_out=v_out, v_alpha=v_alpha)
     finally:
-        R.GEOM_COMPACT_ROWS = True
+        T.GEOM_COMPACT_ROWS = True
+    assert compact and all(sparse(a) == (False, False) for _, a in compact)
+    assert slots and all(sparse(a) == (True, True) for _, a in slots)
     for k in ("means", "quats", "scales", "opacities", "means2d", "colors"):
         np.testing.assert_array_equal(g_c[k], g_s[k])
 
@@ -1398,22 +1421,27 @@ def test_sixteen_channel_render_without_a_backward_needs_no_scratch(oracle, with
 
 
 def test_intersection_count_sent_before_the_sorts_is_the_prefix_sums_total():
-    """rasterization.EARLY_COUNT: the count the host sizes the id lists with is the plain sum of the per-Gaussian tile counts,
+    """raster_tunables.EARLY_COUNT: the count the host sizes the id lists with is the plain sum of the per-Gaussian tile counts,
     read back before the depth sort and the prefix sum are enqueued; it must be the total the prefix sum arrives at (the last
-    entry of the offsets buffer) and leave every index tensor as the late readback leaves it."""
-    from gags_amd import rasterization as R
+    entry of the offsets buffer) and leave every index tensor as the late readback leaves it.  The late readback is the
+    forward's one gags_read_i32, ahead of gags_raster_fwd; the early count needs none."""
+    from gags_amd import raster_tunables as T, rasterization as R
     n, w, h, d = 5000, 200, 152, 16
     s = scene_arrays(n, d, w, h, seed=5, view=2, scale_mult=3.0)
-    got = {}
-    old = R.EARLY_COUNT
+    got, order = {}, {}
+    old = T.EARLY_COUNT
     try:
         for flag in (True, False):
-            R.EARLY_COUNT = flag
-            _, _, info, _ = _run_gpu(s, w, h, s["colors"], None, context=R.RasterContext())
+            T.EARLY_COUNT = flag
+            with spy_entries("gags_read_i32", "gags_raster_fwd") as calls:
+                _, _, info, _ = _run_gpu(s, w, h, s["colors"], None, context=R.RasterContext())
+            order[flag] = [name for name, _ in calls]
             got[flag] = (info["n_isects"], info["isect_ids"].cpu().numpy(), info["flatten_ids"].cpu().numpy(),
                          info["isect_offsets"][0].cpu().numpy())
     finally:
-        R.EARLY_COUNT = old
+        T.EARLY_COUNT = old
+    assert order[True] == ["gags_raster_fwd"]
+    assert order[False] == ["gags_read_i32", "gags_raster_fwd"]
     assert got[True][0] == got[False][0] > 0
     for a, b in zip(got[True][1:], got[False][1:]):
         np.testing.assert_array_equal(a, b)

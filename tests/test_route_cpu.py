@@ -1,4 +1,4 @@
-"""rasterization._route: which kernels serve a call, decided once from plain values -- a hand-written table of named cases
+"""raster_route._route: which kernels serve a call, decided once from plain values -- a hand-written table of named cases
 (the expected _Route and the flag words that reach the C entries), and invariants over the whole input grid.  No GPU, no
 library: the function takes no tensor.  tests/test_route_gpu.py runs the same cases on the kernels."""
 import itertools

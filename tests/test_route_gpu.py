@@ -102,7 +102,7 @@ def _reference(oracle, d, f16):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_route_on_the_kernels(oracle, monkeypatch, name):
-    from gags_amd import _lib, profiler
+    from gags_amd import _lib, profiler, raster_tunables
     from gags_amd import rasterization as R
     d, wants, opt, expected = CASES[name]
     f16 = opt.get("f16", False)
@@ -123,7 +123,7 @@ def test_route_on_the_kernels(oracle, monkeypatch, name):
     if opt.get("hook"):
         ctx.grad_range_hook = lambda g, c0, c1: hooked.append((c0, c1))
     if opt.get("zero_fill"):
-        monkeypatch.setattr(R, "ZERO_FILL_MIN_ELEMS", 0)  # (the fill is worth it from 2^24 elements; here: that it is routed)
+        monkeypatch.setattr(raster_tunables, "ZERO_FILL_MIN_ELEMS", 0)  # (the fill is worth it from 2^24 elements; here: that it is routed)
     lib = _lib.load()
     if opt.get("no_scratch"):
         monkeypatch.setattr(lib, "gags_raster_fwd_scratch_bytes", lambda *a: 1 << 52)  # "does not fit"

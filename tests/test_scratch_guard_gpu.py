@@ -4,11 +4,16 @@ Every binding allocates its scratch through gags_amd._lib.scratch(nbytes, device
 that helper is replaced by one that allocates TAIL more bytes, fills them with 0xA5 and hands out the first nbytes: after
 a call the tail must be untouched, and the results must be those of a plain call (bit-equal where the function's own
 tests assert repeatability bit for bit, else within the tolerance those tests use).  One call per function, at the smallest
-shape that reaches every region of its layout.  The drivers reached only through gags_amd/rasterization.py allocate their
-scratch themselves and are covered by the raster tests, not here.
+shape that reaches every region of its layout.  The raster drivers run on the scene of tests/test_route_gpu.py (N = 300 on
+48 x 32: six tiles, every tile and block edge), each call with a RasterContext of its own so that no kept gradient buffer
+links the plain and the guarded call; their paths are asserted deterministic by
+test_parity_gpu.py::test_backward_flavours_agree_and_staged_is_deterministic and
+::test_wide_geometry_backward_matches_the_valu_kernel_and_is_deterministic, so everything is compared bit for bit.
 """
 import pytest
 import torch
+
+from helpers import scene_arrays, to_dev
 
 pytestmark = pytest.mark.gpu
 TAIL, FILL = 4096, 0xA5
@@ -150,7 +155,50 @@ def _wgrad_exact():
     return call, {}
 
 
-CASES = [_knn, _smooth, _query_points, _activate, _moments, _select, _query_images, _nms, _depthsample, _prompts, _wgrad_exact]
+def _raster(d, all_grads, trim):
+    """rasterization() + backward on the scene of tests/test_route_gpu.py, a fresh RasterContext per call."""
+    from gags_amd.rasterization import RasterContext, rasterization
+    n, w, h = 300, 48, 32
+    s = scene_arrays(n, d, w, h, seed=40 + d % 37, view=2, scale_mult=5.0)
+    names = ("means", "quats", "scales", "opacities", "colors")
+    viewmat, K, bg = to_dev(s["viewmat"])[None], to_dev(s["K"])[None], torch.full((1, d), 0.25, device="cuda")
+    v_out = torch.randn(h, w, d, device="cuda", generator=rng(21 + d))
+    v_alpha = torch.randn(h, w, device="cuda", generator=rng(22 + d))
+
+    def call():
+        t = {k: to_dev(s[k]) for k in names}
+        for k in (names if all_grads else ("colors",)):
+            t[k].requires_grad_(True)
+        ctx = RasterContext()
+        ctx.early_rowmap, ctx.trim_lists = True, (True if trim else None)
+        out, alphas, info = rasterization(*(t[k] for k in names), viewmat, K, w, h, backgrounds=bg, context=ctx)
+        if all_grads:
+            info["means2d"].retain_grad()
+        ((out[0] * v_out).sum() + (alphas[0, ..., 0] * v_alpha).sum()).backward()
+        res = {"out": out.detach(), "alphas": alphas.detach(), "last_ids": info["last_ids"], "n_isects": torch.tensor(info["n_isects"])}
+        res.update({"v_" + k: t[k].grad for k in names if t[k].grad is not None})
+        if all_grads:
+            res["v_means2d"] = info["means2d"].grad
+        if trim:
+            assert info["n_isects_trimmed"] is not None
+        return res
+    return call, {}
+
+
+def _raster_colours():  # depth order, scan, sort, forward scratch, early row map, staged scratch
+    return _raster(16, False, False)
+
+
+def _raster_all_grads():  # ... and the geometry scratch
+    return _raster(24, True, False)
+
+
+def _raster_trimmed():  # ... and the trimming scan
+    return _raster(16, False, True)
+
+
+CASES = [_knn, _smooth, _query_points, _activate, _moments, _select, _query_images, _nms, _depthsample, _prompts, _wgrad_exact,
+         _raster_colours, _raster_all_grads, _raster_trimmed]
 
 
 def test_every_driver_stays_inside_the_scratch_it_asked_for(monkeypatch):

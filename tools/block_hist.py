@@ -4,7 +4,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gags_amd import _lib, synthetic as syn
-from gags_amd import rasterization as R
+from gags_amd import raster_function as F
 from gags_amd.gaussian_renderer import render
 
 cfg = syn.CONFIGS[sys.argv[1] if len(sys.argv) > 1 else "C3"]
@@ -13,11 +13,11 @@ dev = torch.device("cuda", 0)
 pc = syn.make_model(n, d, w, h, seed=0, device=dev, gen_device=dev)
 cam = syn.make_camera(w, h, device=dev)
 captured = {}
-orig = R._backward_staged
+orig = F._backward_staged
 def spy(lib, rctx, fwd, *a, **k):
     captured["blk_rows"] = fwd.blk_rows.clone(); captured["offsets"] = fwd.offsets[:-1].clone(); captured["n_isects"] = fwd.n_isects
     return orig(lib, rctx, fwd, *a, **k)
-R._backward_staged = spy
+F._backward_staged = spy
 pc.training_setup()
 pkg = render(cam, pc, None, torch.zeros(3, device=dev), feature_mode=True)
 pkg["render"].sum().backward()

@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
-from gags_amd import rasterization as R, synthetic as syn
+from gags_amd import raster_function as F, raster_staged as S, synthetic as syn
 from gags_amd.gaussian_renderer import render
 
 cfg = syn.CONFIGS[sys.argv[1] if len(sys.argv) > 1 else "C3"]
@@ -19,18 +19,18 @@ pc.training_setup()
 cam = syn.make_camera(w, h, device=dev)
 G = syn.make_cotangent(d, h, w, seed=1, device=dev)
 cap = {}
-orig = R._backward_staged
+orig = F._backward_staged
 
 
 def spy(lib, rctx, fwd, *a, **kw):
-    rm, _tot, _tmp = R._rowmap(lib, fwd)
+    rm, _tot, _tmp = S._rowmap(lib, fwd)
     torch.cuda.synchronize()
     cap.update(offsets=fwd.offsets.cpu().numpy().reshape(-1)[:-1], blk=fwd.blk_rows.cpu().numpy(), rm=rm.cpu().numpy(),
                I=fwd.n_isects)
     return orig(lib, rctx, fwd, *a, **kw)
 
 
-R._backward_staged = spy
+F._backward_staged = spy
 pkg = render(cam, pc, None, torch.zeros(3, device=dev), feature_mode=True)
 (pkg["render"] * G).sum().backward()
 torch.cuda.synchronize()

@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gags_amd import synthetic as syn
-from gags_amd import rasterization as R
+from gags_amd import raster_function as F, rasterization as R
 from gags_amd.gaussian_renderer import render
 
 cfg = syn.CONFIGS["C3"]
@@ -23,11 +23,11 @@ def spy(*a, **k):
     cap["ids"], cap["packed"] = out.isect_ids, out.packed[out.flatten_ids.long()]  # per-Gaussian records -> per sorted intersection
     return out
 R.tile_binning = spy
-orig_b = R._backward_staged
+orig_b = F._backward_staged
 def spy_b(lib, rctx, fwd, *a, **k):
     cap["blk_rows"] = fwd.blk_rows.clone()
     return orig_b(lib, rctx, fwd, *a, **k)
-R._backward_staged = spy_b
+F._backward_staged = spy_b
 pkg = render(cam, pc, None, torch.zeros(3, device=dev), feature_mode=True)
 pkg["render"].sum().backward()
 ids, pk = cap["ids"], cap["packed"]

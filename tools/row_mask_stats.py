@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from gags_amd import synthetic as syn
-from gags_amd import rasterization as R
+from gags_amd import raster_function as F, raster_staged as S
 from gags_amd.gaussian_renderer import render
 
 cfg = syn.CONFIGS[sys.argv[1] if len(sys.argv) > 1 else "C3"]
@@ -22,18 +22,18 @@ pc = syn.make_model(n, d, w, h, seed=0, device=dev, gen_device=dev, scale0=cfg.g
 pc.training_setup()
 cam = syn.make_camera(w, h, device=dev)
 cap = {}
-orig = R._backward_staged
+orig = F._backward_staged
 
 
 def spy(lib, rctx, fwd, *a, **kw):
-    rm, tot, _tmp = R._rowmap(lib, fwd)
+    rm, tot, _tmp = S._rowmap(lib, fwd)
     torch.cuda.synchronize()
     cap.update(offsets=fwd.offsets.reshape(-1)[:-1].long().clone(), blk=fwd.blk_rows.long().clone(), rm=rm.long().clone(),
                I=fwd.n_isects, rows=int(tot.item()))
     return orig(lib, rctx, fwd, *a, **kw)
 
 
-R._backward_staged = spy
+F._backward_staged = spy
 pkg = render(cam, pc, None, torch.zeros(3, device=dev), feature_mode=True)
 pkg["render"].sum().backward()
 off, blk, rm, I, rows = cap["offsets"], cap["blk"], cap["rm"], cap["I"], cap["rows"]

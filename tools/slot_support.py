@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gags_amd import synthetic as syn
-from gags_amd import rasterization as R
+from gags_amd import raster_function as F
 from gags_amd.gaussian_renderer import render
 
 cfg = syn.CONFIGS[sys.argv[1] if len(sys.argv) > 1 else "C3"]
@@ -17,12 +17,12 @@ pc = syn.make_model(n, d, w, h, seed=0, device=dev, gen_device=dev)
 pc.training_setup()
 cam = syn.make_camera(w, h, device=dev)
 cap = {}
-orig = R._backward_staged
+orig = F._backward_staged
 def spy(lib, rctx, fwd, *a, **k):
     cap.update(offsets=fwd.offsets[:-1].clone().reshape(-1).long(), n_isects=fwd.n_isects, blk_rows=fwd.blk_rows.clone().long(),
                scratch=fwd.fwd_scratch)
     return orig(lib, rctx, fwd, *a, **k)
-R._backward_staged = spy
+F._backward_staged = spy
 pkg = render(cam, pc, None, torch.zeros(3, device=dev), feature_mode=True)
 pkg["render"].sum().backward()
 off, I, br = cap["offsets"], cap["n_isects"], cap["blk_rows"]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where list trimming (gags_amd.rasterization._trim_lists) starts to pay: the C3 geometry at splat scales between the headline
+"""Where list trimming (gags_amd.raster_binning._trim_lists) starts to pay: the C3 geometry at splat scales between the headline
 workload's (0.0009 z_mean, 7.4 M intersections) and SURVEY 8d's literal one (0.004: 63 M), step time with the lists trimmed
 and untrimmed.  Prints one JSON object."""
 import json
