@@ -42,6 +42,11 @@ SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _vp]),
     "gags_raster_bwd_abs": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    # N17: camera pose gradients (flags, n, ..., v_viewmat, partials, partials_bytes) and the column-sum kernel behind them
+    "gags_project_pose_partials": (_i64, [_i32]),
+    "gags_project_bwd_pose": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gags_colsum_f32": (_i32, [_i64, _i32, _vp, _f32, _vp, _i32, _vp]),
     "gags_scan_scratch_bytes": (_i64, [_i32]),
     "gags_cumsum_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_cumsum_gather_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -238,6 +243,7 @@ class GatherDesc(ctypes.Structure):
 
 
 GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instructions (what GAGS_BWD_F32MFMA asks of that kernel)
+GAGS_POSE_RAW, GAGS_POSE_AA = 1, 2  # `flags` of gags_project_bwd_pose
 GAGS_GEOM_ABSGRAD = 64  # `flags` of gags_raster_bwd_geom: columns 6, 7 of v_geo carry absgrad (rasterization(absgrad=True))
 
 _lib = None

@@ -5,6 +5,7 @@
 // translation unit must be built with -ffp-contract=off.
 #include "common.h"
 #include "raster_mfma_common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -258,17 +259,39 @@ namespace {
 // (include/gags_raster.h has the three partials).  Its cotangent is v_compensations (may be NULL), or in RAW
 // v_opacities * sigmoid(logit) -- v_opacities then being the cotangent of the COMPENSATED opacity, so that the logit's
 // gradient carries the factor comp (0 for a culled Gaussian).
-template <bool RAW, bool AA>
+// POSE (gags_project_bwd_pose, N17): the cotangent of the upper 3 x 4 of viewmat on the way.  With p = Rcw mu + t and
+// Sc = Rcw S3 Rcw^T (S3 symmetric, A = Rcw S3) a Gaussian on screen contributes
+//   v_t[r] = vp[r],   v_Rcw[r][c] = vp[r] mu[c] + sum_k (GSc[r][k] + GSc[k][r]) A[k][c]
+// (the clamp of tx / ty, the antialiased term and v_depths are inside vp and GSc already); pose[4 r + c] takes them in the
+// row-major order of viewmat, pose[4 r + 3] = v_t[r], and keeps its zeros for a lane past N or a culled Gaussian.  v_means,
+// v_quats, v_scales may then each be NULL (a frozen scene): the stores are skipped, the values that are stored are the
+// POSE = false kernel's bit for bit (same operations, same order).
+// A lane past N or on a culled Gaussian LEAVEs the per-Gaussian work: it ends there without POSE; with POSE it only leaves
+// the do { } while (0) around that work, so that all 64 lanes of every wave reach the wave sums behind it.  That is the first
+// stage of the deterministic sum over N: a gags_wave_sum per term, the four wave totals of the workgroup added in double in
+// wave order, one row of twelve floats per workgroup into pose_partials[blockIdx.x][12].  gags_colsum_f32 adds the rows
+// (second stage).  No atomics.
+#define GAGS_PBWD_LEAVE()              \
+    {                                  \
+        if constexpr (POSE) break;     \
+        else return;                   \
+    }
+template <bool RAW, bool AA, bool POSE>
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     int N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmat, const float *__restrict__ Kmat, int width, int height, float eps2d,
     const int32_t *__restrict__ radii, const float *__restrict__ v_means2d, const float *__restrict__ v_depths,
     const float *__restrict__ v_conics, float *__restrict__ v_means, float *__restrict__ v_quats,
     float *__restrict__ v_scales, const float *__restrict__ opacity_logits, float scaling_modifier,
-    const float *__restrict__ v_opacities, float *__restrict__ v_opacity_logits, const float *__restrict__ v_compensations)
+    const float *__restrict__ v_opacities, float *__restrict__ v_opacity_logits, const float *__restrict__ v_compensations,
+    float *__restrict__ pose_partials)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
+    float pose[12];
+    if constexpr (POSE) { _Pragma("unroll") for (int k = 0; k < 12; ++k) pose[k] = 0.f; }
+    do {
+    if (i >= N) GAGS_PBWD_LEAVE()
+    const bool w_means = !POSE || v_means, w_quats = !POSE || v_quats, w_scales = !POSE || v_scales;
     if constexpr (RAW && AA) {
         if (v_opacity_logits) v_opacity_logits[i] = 0.f;  // (rewritten below, with comp, for the Gaussians on screen)
     } else if constexpr (RAW) {
@@ -277,9 +300,12 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
             v_opacity_logits[i] = v_opacities ? (v_opacities[i] * (1.0f - o)) * o : 0.f;  // (torch: grad * (1 - y) * y)
         }
     }
-    _Pragma("unroll") for (int k = 0; k < 3; ++k) { v_means[3 * i + k] = 0.f; v_scales[3 * i + k] = 0.f; }
-    _Pragma("unroll") for (int k = 0; k < 4; ++k) v_quats[4 * i + k] = 0.f;
-    if (radii[i] <= 0) return;
+    _Pragma("unroll") for (int k = 0; k < 3; ++k) {
+        if (w_means) v_means[3 * i + k] = 0.f;
+        if (w_scales) v_scales[3 * i + k] = 0.f;
+    }
+    if (w_quats) { _Pragma("unroll") for (int k = 0; k < 4; ++k) v_quats[4 * i + k] = 0.f; }
+    if (radii[i] <= 0) GAGS_PBWD_LEAVE()
     const float Rc[3][3] = {{viewmat[0], viewmat[1], viewmat[2]},
                             {viewmat[4], viewmat[5], viewmat[6]},
                             {viewmat[8], viewmat[9], viewmat[10]}};
@@ -382,8 +408,18 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         if (x_in) vp[0] += -fx * rz2 * vJ[0][2]; else vp[2] += -fx * rz3 * vJ[0][2] * tx;
         if (y_in) vp[1] += -fy * rz2 * vJ[1][2]; else vp[2] += -fy * rz3 * vJ[1][2] * ty;
         vp[2] += -fx * rz2 * vJ[0][0] - fy * rz2 * vJ[1][1] + 2.f * fx * tx * rz3 * vJ[0][2] + 2.f * fy * ty * rz3 * vJ[1][2];
+        if constexpr (POSE) {
+            _Pragma("unroll") for (int r = 0; r < 3; ++r) {
+                _Pragma("unroll") for (int c = 0; c < 3; ++c)
+                    pose[4 * r + c] = vp[r] * mu[c] + (((GSc[r][0] + GSc[0][r]) * A[0][c] + (GSc[r][1] + GSc[1][r]) * A[1][c]) +
+                                                       (GSc[r][2] + GSc[2][r]) * A[2][c]);
+                pose[4 * r + 3] = vp[r];
+            }
+        }
         /* ---- 4. camera -> world ---- */
-        _Pragma("unroll") for (int c = 0; c < 3; ++c) v_means[3 * i + c] = (Rc[0][c] * vp[0] + Rc[1][c] * vp[1]) + Rc[2][c] * vp[2];
+        if (w_means) {
+            _Pragma("unroll") for (int c = 0; c < 3; ++c) v_means[3 * i + c] = (Rc[0][c] * vp[0] + Rc[1][c] * vp[1]) + Rc[2][c] * vp[2];
+        }
         float T1[3][3], GS[3][3];
         _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 3; ++c)
             T1[r][c] = (Rc[0][r] * GSc[0][c] + Rc[1][r] * GSc[1][c]) + Rc[2][r] * GSc[2][c];
@@ -397,7 +433,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         float GR[3][3];
         _Pragma("unroll") for (int c = 0; c < 3; ++c) {
             const float vs = (R[0][c] * GM[0][c] + R[1][c] * GM[1][c]) + R[2][c] * GM[2][c];
-            v_scales[3 * i + c] = RAW ? vs * s[c] : vs;  // RAW: d/d log-scale (torch: grad * modifier, then * exp(_scaling))
+            if (w_scales) v_scales[3 * i + c] = RAW ? vs * s[c] : vs;  // RAW: d/d log-scale (torch: grad * modifier, then * exp(_scaling))
             _Pragma("unroll") for (int r = 0; r < 3; ++r) GR[r][c] = GM[r][c] * s[c];
         }
         /* ---- 7. R(q^) -> q^ ---- */
@@ -418,7 +454,45 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
             g0 = (g0 - q0 * d2) / raw_nrm; g1 = (g1 - q1 * d2) / raw_nrm;
             g2 = (g2 - q2 * d2) / raw_nrm; g3 = (g3 - q3 * d2) / raw_nrm;
         }
-        v_quats[4 * i] = g0; v_quats[4 * i + 1] = g1; v_quats[4 * i + 2] = g2; v_quats[4 * i + 3] = g3;
+        if (w_quats) { v_quats[4 * i] = g0; v_quats[4 * i + 1] = g1; v_quats[4 * i + 2] = g2; v_quats[4 * i + 3] = g3; }
+    } while (0);
+#undef GAGS_PBWD_LEAVE
+    if constexpr (POSE) {
+        __shared__ double red[4][12];
+        _Pragma("unroll") for (int k = 0; k < 12; ++k) {
+            const float w = gags_wave_sum(pose[k]);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = (double)w;
+        }
+        __syncthreads();
+        if (threadIdx.x < 12) {
+            const int k = threadIdx.x;
+            pose_partials[(int64_t)blockIdx.x * 12 + k] = (float)(((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]);
+        }
+    }
+}
+
+// Column sums of an fp32 table [n_rows, k], k <= GAGS_COLSUM_MAX_K, by ONE workgroup, in double and in a fixed order: thread t adds
+// rows t, t + 256, ... in that order, the 256 per-thread sums are folded pairwise through LDS (t += t + 128, 64, ... 1).
+// out[c] = (float)(sign * sum_c) for c < k, and out[k .. n_out) = 0.
+constexpr int GAGS_COLSUM_MAX_K = 12;
+__global__ __launch_bounds__(256) void colsum_kernel(int64_t n_rows, int k, const float *__restrict__ table, float sign,
+                                                     float *__restrict__ out, int n_out)
+{
+    __shared__ double red[256][GAGS_COLSUM_MAX_K];
+    const int t = threadIdx.x;
+    double acc[GAGS_COLSUM_MAX_K];
+    _Pragma("unroll") for (int c = 0; c < GAGS_COLSUM_MAX_K; ++c) acc[c] = 0.0;
+    for (int64_t r = t; r < n_rows; r += 256) {
+        _Pragma("unroll") for (int c = 0; c < GAGS_COLSUM_MAX_K; ++c)
+            if (c < k) acc[c] += (double)table[r * k + c];
+    }
+    _Pragma("unroll") for (int c = 0; c < GAGS_COLSUM_MAX_K; ++c) red[t][c] = acc[c];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { _Pragma("unroll") for (int c = 0; c < GAGS_COLSUM_MAX_K; ++c) red[t][c] += red[t + s][c]; }
+        __syncthreads();
+    }
+    if (t < n_out) out[t] = t < k ? (float)((double)sign * red[0][t]) : 0.f;
 }
 
 }  // namespace
@@ -438,11 +512,40 @@ int project_bwd_launch(int n, const float *means, const float *quats, const floa
     if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics || !v_means || !v_quats || !v_scales)
         return GAGS_EINVAL;
     if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
-    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means, quats,
-                       scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats,
-                       v_scales, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations);
+    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, false>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
+                       quats, scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats,
+                       v_scales, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, nullptr);
     GAGS_CHECK_LAUNCH();
     return GAGS_OK;
+}
+
+int colsum_launch(int64_t n_rows, int k, const float *table, float sign, float *out, int n_out, hipStream_t st)
+{
+    if (n_rows < 0 || k < 1 || k > GAGS_COLSUM_MAX_K || n_out < k || n_out > 256 || !out || (n_rows > 0 && !table))
+        return GAGS_EINVAL;
+    hipLaunchKernelGGL(colsum_kernel, dim3(1), dim3(256), 0, st, n_rows, k, table, sign, out, n_out);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}
+
+template <bool RAW, bool AA>
+int project_bwd_pose_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
+                            float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
+                            const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
+                            const float *v_opacities, const float *v_compensations, float *v_means, float *v_quats,
+                            float *v_scales, float *v_opacity_logit, float *v_viewmat, float *partials, hipStream_t st)
+{
+    const int64_t rows = n > 0 ? gags_project_pose_partials(n) : 0;
+    if (n > 0) {
+        if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics) return GAGS_EINVAL;
+        if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
+        hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, true>), dim3((unsigned)rows), dim3(256), 0, st, n, means, quats, scales,
+                           viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats, v_scales,
+                           opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, partials);
+        GAGS_CHECK_LAUNCH();
+    }
+    // second stage: the rows of `partials` in row order; entries 12 .. 15 (row 3 of the 4 x 4) are written as zeros
+    return colsum_launch(rows, 12, partials, 1.0f, v_viewmat, 16, st);
 }
 
 }  // namespace
@@ -490,4 +593,37 @@ extern "C" int gags_project_bwd_raw_aa(int n, const float *means, const float *r
     return project_bwd_launch<true, true>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
                                           height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities, nullptr, v_means,
                                           v_rotation, v_scaling_log, v_opacity_logit, stream);
+}
+
+// ---- N17: camera pose gradients ---------------------------------------------------------------------------------------------
+
+extern "C" int64_t gags_project_pose_partials(int n) { return n > 0 ? ((int64_t)n + 255) / 256 : 1; }
+
+extern "C" int gags_project_bwd_pose(int flags, int n, const float *means, const float *quats, const float *scales,
+                                     const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                                     int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                                     const float *v_depths, const float *v_conics, const float *v_opacities,
+                                     const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                                     float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes,
+                                     void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (n < 0 || width <= 0 || height <= 0 || (flags & ~(GAGS_POSE_RAW | GAGS_POSE_AA))) return GAGS_EINVAL;
+    // (a short partials buffer would be written out of bounds: refused before anything is launched)
+    if (!v_viewmat || !partials || partials_bytes < gags_project_pose_partials(n) * 12 * (int64_t)sizeof(float)) return GAGS_EINVAL;
+    const bool raw = flags & GAGS_POSE_RAW, aa = flags & GAGS_POSE_AA;
+    if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; v_opacities = nullptr; v_opacity_logit = nullptr; }
+    if (raw || !aa) v_compensations = nullptr;
+#define GAGS_POSE_ARGS n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d, \
+                       v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit, v_viewmat,    \
+                       partials, (hipStream_t)stream
+    if (raw) return aa ? project_bwd_pose_launch<true, true>(GAGS_POSE_ARGS) : project_bwd_pose_launch<true, false>(GAGS_POSE_ARGS);
+    return aa ? project_bwd_pose_launch<false, true>(GAGS_POSE_ARGS) : project_bwd_pose_launch<false, false>(GAGS_POSE_ARGS);
+#undef GAGS_POSE_ARGS
+}
+
+extern "C" int gags_colsum_f32(int64_t n_rows, int k, const float *table, float sign, float *out, int n_out, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    return colsum_launch(n_rows, k, table, sign, out, n_out, (hipStream_t)stream);
 }

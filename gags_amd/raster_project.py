@@ -10,6 +10,24 @@ def _c(t):
     return t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
 
 
+def _project_bwd_pose(lib, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                      v_depths, v_conics, v_opac, v_comp, want):
+    """gags_project_bwd_pose (N17): the projection backward when the pose needs a gradient.  want = which of (means, quats,
+    scales, opacity logit) need theirs: the others are neither allocated nor stored.  Returns (v_means, v_quats, v_scales,
+    v_logit, v_viewmat [4,4]), None where not wanted."""
+    n = means.shape[0]
+    dev = means.device
+    v_means, v_quats, v_scales, v_logit = (torch.empty(n, *shape, device=dev) if w else None
+                                           for w, shape in zip(want, ((3,), (4,), (3,), ())))
+    v_viewmat = torch.empty(4, 4, device=dev)
+    partials = torch.empty(lib.gags_project_pose_partials(n), 12, device=dev)
+    check(lib.gags_project_bwd_pose(flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
+                                    width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac),
+                                    ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_logit), ptr(v_viewmat),
+                                    ptr(partials), partials.numel() * 4, _lib.stream()), "gags_project_bwd_pose")
+    return v_means, v_quats, v_scales, v_logit, v_viewmat
+
+
 class _Project(torch.autograd.Function):
     """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
     cotangent in the backward (gags_project_fwd_aa / gags_project_bwd_aa); the caller multiplies them into the opacities."""
@@ -48,6 +66,12 @@ class _Project(torch.autograd.Function):
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
         v_conics = torch.zeros(n, 3, device=dev) if v_conics is None else _c(v_conics)
         v_depths = None if v_depths is None else _c(v_depths)
+        if ctx.needs_input_grad[3]:  # the pose: one more output of the same kernel, and only the scene gradients that are wanted
+            v_comp = None if (not aa or v_comp is None) else _c(v_comp)
+            v_means, v_quats, v_scales, _, v_viewmat = _project_bwd_pose(
+                lib, _lib.GAGS_POSE_AA if aa else 0, means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii,
+                v_means2d, v_depths, v_conics, None, v_comp, tuple(ctx.needs_input_grad[:3]) + (False,))
+            return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None
         v_means = torch.empty(n, 3, device=dev)
         v_quats = torch.empty(n, 4, device=dev)
         v_scales = torch.empty(n, 3, device=dev)
@@ -114,6 +138,13 @@ class _ProjectRaw(torch.autograd.Function):
         v_conics = torch.zeros(n, 3, device=dev) if v_conics is None else _c(v_conics)
         v_depths = None if v_depths is None else _c(v_depths)
         v_opac = None if v_opac is None else _c(v_opac)
+        if ctx.needs_input_grad[4]:  # the pose (see _Project.backward)
+            flags = _lib.GAGS_POSE_RAW | (_lib.GAGS_POSE_AA if aa else 0)
+            v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd_pose(
+                lib, flags, means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                v_depths, v_conics, v_opac, None, tuple(ctx.needs_input_grad[:4]))
+            return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, None, None, None,
+                    None, None, None, None, None, None, None)
         v_means = torch.empty(n, 3, device=dev)
         v_rot = torch.empty(n, 4, device=dev)
         v_scal = torch.empty(n, 3, device=dev)
@@ -130,7 +161,8 @@ class _ProjectRaw(torch.autograd.Function):
 
 class _SH(torch.autograd.Function):
     """K3: SH colour and its backward: coefficients, and -- when positions are trainable -- the view direction
-    (d colour / d means through normalize(mean - campos), as gsplat propagates it)."""
+    (d colour / d means through normalize(mean - campos), as gsplat propagates it); when the camera position needs a gradient
+    (a trainable pose, N17), v_campos = - the column sums of that table (gags_colsum_f32)."""
 
     @staticmethod
     def forward(ctx, coeffs, means, campos, radii, degree):
@@ -140,7 +172,7 @@ class _SH(torch.autograd.Function):
         out = torch.empty(n, 3, device=coeffs.device)
         check(lib.gags_sh_fwd(n, kc, degree, ptr(means), ptr(campos), ptr(coeffs), ptr(radii), ptr(out), _lib.stream()),
               "gags_sh_fwd")
-        ctx.save_for_backward(means, campos, radii, out, coeffs if ctx.needs_input_grad[1] else None)
+        ctx.save_for_backward(means, campos, radii, out, coeffs if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else None)
         ctx.cfg = (kc, degree)
         return out
 
@@ -156,8 +188,16 @@ class _SH(torch.autograd.Function):
             v_coeffs = torch.empty(n, kc, 3, device=means.device)
             check(lib.gags_sh_bwd(n, kc, degree, ptr(means), ptr(campos), ptr(radii), ptr(out), ptr(v_out),
                                   ptr(v_coeffs), _lib.stream()), "gags_sh_bwd")
-        if ctx.needs_input_grad[1]:
-            v_means = torch.empty(n, 3, device=means.device)
+        v_campos = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            # (the pose alone: the same table into a temporary, for its column sums)
+            v_dirs = torch.empty(n, 3, device=means.device)
             check(lib.gags_sh_bwd_dirs(n, kc, degree, ptr(means), ptr(campos), ptr(coeffs), ptr(radii), ptr(out),
-                                       ptr(v_out), ptr(v_means), _lib.stream()), "gags_sh_bwd_dirs")
-        return v_coeffs, v_means, None, None, None
+                                       ptr(v_out), ptr(v_dirs), _lib.stream()), "gags_sh_bwd_dirs")
+            if ctx.needs_input_grad[1]:
+                v_means = v_dirs
+            if ctx.needs_input_grad[2]:
+                # dir = normalize(mean - campos): v_campos = - sum_i v_means_i, summed in double in a fixed order (N17)
+                v_campos = torch.empty(3, device=means.device)
+                check(lib.gags_colsum_f32(n, 3, ptr(v_dirs), -1.0, ptr(v_campos), 3, _lib.stream()), "gags_colsum_f32")
+        return v_coeffs, v_means, v_campos, None, None

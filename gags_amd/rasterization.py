@@ -97,6 +97,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     rasterize_mode="antialiased": Mip-Splatting's opacity compensation, comp = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I)))
     from the projection kernel (no constant in the divisor); the opacity every later stage sees --
     and info["opacities"] -- is opacity * comp, and info["compensations"] is [1,N] (None in classic mode).
+    viewmats.requires_grad (N17): after backward(), viewmats.grad [1,4,4] is d loss / d viewmats -- the
+    projection backward produces it on the way (gags_project_bwd_pose, a deterministic sum over N, row 3 exactly zero), and the
+    SH view direction reaches it through campos = inverse(viewmat)[:3, 3], as in gsplat (torch's backward of the 4 x 4 inverse:
+    with sh_degree row 3 gets what that puts there).  Scene tensors that need no gradient
+    get none computed (pose refinement against a frozen scene).  Ks gets NO gradient, as in gsplat.  With viewmats not
+    requiring grad nothing changes: same launches, same bits.
     absgrad=True: after backward(), info["means2d"].absgrad is the [1,N,2] sum over pixels of the absolute per-pixel
     screen-space gradients (AbsGS), overwritten by each backward; set only where a geometry gradient is produced."""
     rctx = context if context is not None else default_context()

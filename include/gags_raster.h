@@ -428,6 +428,34 @@ int gags_project_bwd(int n, const float *means, const float *quats, const float 
                      const float *v_means2d, const float *v_depths, const float *v_conics,
                      float *v_means, float *v_quats, float *v_scales, void *stream);
 
+/* N17: the projection backward with the camera pose's cotangent (pose refinement, relocalisation against a frozen scene).
+ * flags: GAGS_POSE_RAW = the stored parameters, as gags_project_bwd_raw[_aa]; GAGS_POSE_AA = rasterize_mode "antialiased", as
+ * gags_project_bwd_aa / _raw_aa.  The arguments are the union of those entries' (what a variant does not read is ignored:
+ * opacity_logit, scaling_modifier, v_opacities, v_opacity_logit without RAW; v_compensations unless AA without RAW).
+ * v_viewmat[16] (overwritten): d loss / d viewmat, row-major 4 x 4, row 3 exactly zero.  With Rcw, t the upper 3 x 4, vp the
+ * cotangent of the camera-space point, GSc that of the camera-space covariance and A = Rcw Sigma, a Gaussian with radii > 0
+ * contributes
+ *   v_t[r] += vp[r],   v_Rcw[r][c] += vp[r] mean[c] + sum_k (GSc[r][k] + GSc[k][r]) A[k][c]
+ * and a culled one exactly zero.  K is not differentiated.  The sum over N is deterministic (no atomics): a wave sum, the four
+ * waves of a workgroup in double, one row of 12 floats per workgroup into `partials`, then gags_colsum_f32 over the rows.
+ * v_means, v_quats / v_rotation, v_scales / v_scaling_log, v_opacity_logit may each be NULL (not wanted: not stored); where
+ * given they are bit for bit what gags_project_bwd* writes.  partials: gags_project_pose_partials(n) rows of 12 floats
+ * (partials_bytes >= rows * 48, else GAGS_EINVAL before any launch; NULL v_viewmat or partials likewise).  n = 0: v_viewmat
+ * is written (zeros). */
+#define GAGS_POSE_RAW 1
+#define GAGS_POSE_AA 2
+int64_t gags_project_pose_partials(int n);
+int gags_project_bwd_pose(int flags, int n, const float *means, const float *quats, const float *scales,
+                          const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                          int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                          const float *v_depths, const float *v_conics, const float *v_opacities,
+                          const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                          float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
+/* Column sums of an fp32 table [n_rows, k], 1 <= k <= 12: out[c] = sign * sum over rows of table[r, c] for c < k, and
+ * out[k .. n_out) = 0 (k <= n_out <= 256).  One workgroup, sums in double, fixed order: two calls give the same bits.
+ * n_rows = 0 writes zeros.  (Second stage of gags_project_bwd_pose; v_campos = -sum of gags_sh_bwd_dirs' rows.) */
+int gags_colsum_f32(int64_t n_rows, int k, const float *table, float sign, float *out, int n_out, void *stream);
+
 /* K3: spherical-harmonics colour, used when feature_mode=False and no override colour
  * (gaussian_renderer/__init__.py:51-53).  coeffs[N,kc,3], campos[3] (device),
  * out[N,3] = max(SH(dir) + 0.5, 0) where radii>0, zeros elsewhere.  Basis and signs as
