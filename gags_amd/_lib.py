@@ -204,6 +204,14 @@ SIGNATURES = {
     "gags_tilecut_boxes": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
     # N15: the query head, CNN_decoder + relevancy in one kernel (csrc/decoder_query.hip)
     "gags_decoder_query_fused": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    # N18: MCMC density control (csrc/mcmc.hip)
+    "gags_mcmc_sample": (_i32, [_i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gags_mcmc_relocation": (_i32, [_i32, _vp, _i32, _f64, _vp, _vp, _vp]),
+    "gags_mcmc_copy_rows": (_i32, [_i64, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "gags_mcmc_noise": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "gags_mcmc_reg_partials": (_i64, [_i32]),
+    "gags_mcmc_reg_fwd": (_i32, [_i32, _vp, _vp, _f32, _f32, _vp, _i64, _vp, _vp]),
+    "gags_mcmc_reg_bwd": (_i32, [_i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)
@@ -234,7 +242,8 @@ GAGS_STAGE_ALL, GAGS_STAGE_ROWS, GAGS_STAGE_SORT, GAGS_STAGE_REDUCE, GAGS_STAGE_
 GAGS_STAGED_F32MFMA, GAGS_STAGED_OUT_F16, GAGS_STAGED_PREZEROED = 32, 64, 128
 GAGS_STAGED_RANGE_SCRATCH, GAGS_STAGED_BLOCKWAVES, GAGS_STAGED_EXACT_WEIGHTS = 256, 512, 1024
 GAGS_KIND_KEEP, GAGS_KIND_CLONE, GAGS_KIND_CHILD_A, GAGS_KIND_CHILD_B = 0, 1, 2, 3  # `kind` of gags_densify_plan
-GAGS_GATHER_MAX_DESC, GAGS_GATHER_COPY, GAGS_GATHER_MOMENT = 24, 0, 1  # gags_densify_gather
+GAGS_GATHER_MAX_DESC, GAGS_GATHER_COPY, GAGS_GATHER_MOMENT = 24, 0, 1  # gags_densify_gather, gags_mcmc_copy_rows
+GAGS_MCMC_MAX_RATIO = 51  # gags_mcmc_relocation clamps a ratio to [1, this]
 
 
 class GatherDesc(ctypes.Structure):

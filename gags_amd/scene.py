@@ -383,3 +383,14 @@ class GaussianModel:
     def reset_opacity(self):
         from . import densify
         densify.reset_opacity(self)
+
+    # -- MCMC density control (gags_amd/mcmc.py): the method names gsplat's strategy uses -------------------
+    def relocate_gs(self, dead_mask=None, *, min_opacity=0.005, uniforms=None, generator=None):
+        """Move the dead Gaussians (default: opacity <= min_opacity) onto live ones drawn by opacity; returns their number."""
+        from . import mcmc
+        return mcmc.relocate(self, dead_mask, min_opacity, uniforms=uniforms, generator=generator)
+
+    def add_new_gs(self, cap_max, *, min_opacity=0.005, uniforms=None, generator=None):
+        """Grow by 5 % up to cap_max with copies of Gaussians drawn by opacity; returns the number added."""
+        from . import mcmc
+        return mcmc.sample_add(self, cap_max, min_opacity, uniforms=uniforms, generator=generator)

@@ -627,6 +627,63 @@ int gags_tilecut_boxes(int n_masks, int height, int width, const void *bits, int
 int gags_decoder_query_fused(int64_t n_pix, int c_in, int n_last, const float *x, const void *const *w_bf16,
                              const float *const *bias, const float *phrases, int n_pos, int n_neg, float *probs, void *stream);
 
+/* ---- N18: MCMC density control ("3D Gaussian Splatting as Markov Chain Monte Carlo": relocation, capped growth, position
+ * noise; csrc/mcmc.hip, gags_amd/mcmc.py; the rules R1-R6 are declared in DESIGN.md section 7 "N18") -------------------------
+ * Stored parameters as everywhere: opacity [n] logits, scaling [n, 3] logs, rotation [n, 4] (w, x, y, z) un-normalised,
+ * xyz [n, 3]; fp32, contiguous.  n = 0 (and zero draws / pairs) is accepted everywhere and launches nothing.  No float atomics,
+ * no inline assembly: two runs give the same bits.
+ *
+ * Sampling (R2).  cdf [n] float64 = the inclusive prefix sums of non-negative weights (non-decreasing), u [n_draws] float64 in
+ * [0, 1).  One thread per draw: t = u * cdf[n - 1]; draws[k] = the first j with cdf[j] > t (binary search), and when no entry
+ * exceeds t the first j with cdf[j] == cdf[n - 1]: a row of weight zero (cdf[j] == cdf[j - 1]) is never drawn.
+ * counts[j] += 1 per draw of j (int32 atomics: exact, order-free); the CALLER zero-fills counts [n] first.
+ * GAGS_EINVAL: n < 0, n_draws < 0 or >= 2^31, n == 0 with n_draws > 0, a null pointer while n_draws > 0. */
+int gags_mcmc_sample(int n, const double *cdf, int64_t n_draws, const double *u, int32_t *draws, int32_t *counts, void *stream);
+/* Relocation values (R1), in place, over the rows with k[i] > 0; every other row is not touched.  r = k[i] + ratio_bias clamped
+ * to [1, GAGS_MCMC_MAX_RATIO] (ratio_bias 1: k = gags_mcmc_sample's counts; ratio_bias 0: k = the ratios themselves).  Per row,
+ * in FLOAT64 from the stored float32 values, rounded once at the end:
+ *   q     = max(1 / (1 + exp(x)), 2^-23),  o = 1 - q                      (x the logit: o = min(sigmoid(x), 1 - 2^-23))
+ *   o_new = 1 - q^(1/r)                                                   (as -expm1(log(q) / r))
+ *   denom = sum_{i = 1..r} sum_{k = 0..i-1} C(i-1, k) (-1)^k o_new^(k+1) / sqrt(k+1)      (in this order; C from a constant
+ *                                                                          51 x 51 table of exact doubles)
+ *   scaling[i, a] = fl32(scaling[i, a] + log(o / denom))   a = 0, 1, 2;   r == 1: not written (o_new = o, the coefficient is 1)
+ *   opacity[i]    = fl32(logit(min(max(o_new, min_opacity), 1 - 2^-23)))
+ * GAGS_EINVAL: n < 0, ratio_bias outside {0, 1}, min_opacity outside (0, 1) (a NaN included), a null pointer while n > 0. */
+#define GAGS_MCMC_MAX_RATIO 51
+int gags_mcmc_relocation(int n, const int32_t *k, int ratio_bias, double min_opacity, float *opacity, float *scaling,
+                         void *stream);
+/* Row copies of a relocation (R3) for up to GAGS_GATHER_MAX_DESC tensors of n_rows rows in one launch, IN PLACE (gags_gather_desc
+ * with in == out, rows of row_floats > 0 floats, 16-byte lanes as for gags_densify_gather), over the n_pairs pairs
+ * (dst_rows[p] int64, src_rows[p] int32):
+ *   GAGS_GATHER_COPY:    out[dst_rows[p], :] = out[src_rows[p], :]       (bit copies; the caller keeps the two sets disjoint)
+ *   GAGS_GATHER_MOMENT:  out[src_rows[p], :] = 0                          (Adam's moments at the drawn sources; dst rows keep theirs)
+ * A pair with a row outside [0, n_rows) is skipped.  GAGS_EINVAL: n_pairs < 0 or >= 2^31, n_rows < 0, n_desc outside
+ * [0, GAGS_GATHER_MAX_DESC], a descriptor with in != out, a null pointer, row_floats <= 0 or an unknown mode, null row lists
+ * while there is work. */
+int gags_mcmc_copy_rows(int64_t n_pairs, const int64_t *dst_rows, const int32_t *src_rows, int n_rows, int n_desc,
+                        const gags_gather_desc *descs_host, void *stream);
+/* Position noise (R5), one thread per Gaussian, fp32, no FMA, xyz in place (68 bytes of traffic per Gaussian):
+ *   o = 1 / (1 + exp(-x)),  gate = 1 / (1 + exp(-100 ((1 - o) - 0.995f)))
+ *   norm = sqrt(((w w + x x) + y y) + z z), q = stored / norm, R as gags_densify_children builds it, M[r][a] = R[r][a] exp(s_a)
+ *   S[r][c] = (M[r][0] M[c][0] + M[r][1] M[c][1]) + M[r][2] M[c][2]
+ *   v_a = (z[i, a] * gate) * scaler,   xyz[i, r] += (S[r][0] v_0 + S[r][1] v_1) + S[r][2] v_2
+ * GAGS_EINVAL: n < 0, a null pointer while n > 0, scaler not finite. */
+int gags_mcmc_noise(int n, const float *opacity, const float *scaling, const float *rotation, const float *z, float scaler,
+                    float *xyz, void *stream);
+/* Regularisers (R6): out[0] = opacity_reg mean(sigmoid(opacity)) + scale_reg mean(exp(scaling)) (means over n and 3 n entries).
+ * Per element in float64; a fixed-order float64 tree over the 64 lanes of a wave, the four wave sums of a workgroup added in
+ * wave order, fl32(opacity_reg / n * sum_o + scale_reg / (3 n) * sum_s) as the workgroup's row of `partials`, then
+ * gags_colsum_f32 over the rows: deterministic.  partials: gags_mcmc_reg_partials(n) floats (partials_bytes >= 4 * that, else
+ * GAGS_EINVAL before any launch).  n = 0: out[0] = 0.
+ * Backward, one launch, closed form, float64 per element rounded once; g = v_out[0], a DEVICE float (no host sync):
+ *   v_opacity[i] = g opacity_reg / n * o (1 - o),   v_scaling[i, a] = g scale_reg / (3 n) * exp(s_a)
+ * GAGS_EINVAL: n < 0, a null pointer (partials and the inputs may be null when n == 0), coefficients not finite. */
+int64_t gags_mcmc_reg_partials(int n);
+int gags_mcmc_reg_fwd(int n, const float *opacity, const float *scaling, float opacity_reg, float scale_reg, float *partials,
+                      int64_t partials_bytes, float *out, void *stream);
+int gags_mcmc_reg_bwd(int n, const float *opacity, const float *scaling, float opacity_reg, float scale_reg, const float *v_out,
+                      float *v_opacity, float *v_scaling, void *stream);
+
 /* ---- the "f16" decoder tier -------------------------------------------------------------------------------------------
  * The SAME kernels compiled with IEEE half as their 16-bit operand type (csrc/half16.h; v_mfma_f32_32x32x16_f16, fp32
  * accumulation): an 11-bit significand -- exactly the TF32 significand the reference's nn.Conv2d layers
