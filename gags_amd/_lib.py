@@ -212,6 +212,9 @@ SIGNATURES = {
     "gags_mcmc_reg_partials": (_i64, [_i32]),
     "gags_mcmc_reg_fwd": (_i32, [_i32, _vp, _vp, _f32, _f32, _vp, _i64, _vp, _vp]),
     "gags_mcmc_reg_bwd": (_i32, [_i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
+    # N19: row-selective Adam, all tensors of a step in one launch (csrc/optim.hip)
+    "gags_adam_tensor_bytes": (_i64, []),
+    "gags_adam_step_rows": (_i32, [_i64, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp]),
 }
 
 for _name in [k for k, v in SIGNATURES.items() if v is None]:  # (a twin's signature is its bf16 counterpart's)
@@ -250,6 +253,14 @@ class GatherDesc(ctypes.Structure):
     """gags_gather_desc of include/gags_next.h."""
     _fields_ = [("in_", _vp), ("out", _vp), ("row_floats", ctypes.c_int32), ("mode", ctypes.c_int32)]
 
+
+class AdamTensor(ctypes.Structure):
+    """gags_adam_tensor of include/gags_raster.h (gags_adam_tensor_bytes() is its size on the C side)."""
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("width", _i64),
+                ("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64)]
+
+
+GAGS_ADAM_MAX_TENSORS, GAGS_ADAM_SKIP_ZERO_ROWS, GAGS_ADAM_NO_BIAS_CORRECTION = 8, 1, 2  # gags_adam_step_rows
 
 GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instructions (what GAGS_BWD_F32MFMA asks of that kernel)
 GAGS_POSE_RAW, GAGS_POSE_AA = 1, 2  # `flags` of gags_project_bwd_pose

@@ -68,6 +68,181 @@ extern "C" int gags_adam_step(int64_t numel, float *param, const float *grad, fl
     return GAGS_OK;
 }
 
+// ---- N19: row-selective Adam, all tensors of a step in one launch (include/gags_raster.h) -----------------------------------
+// blockIdx.y = tensor.  A tensor is walked in UNITS: float4 when its four bases are 16-byte aligned and width % 4 == 0,
+// float otherwise.  Rows of <= 64 units: a group of `lanes` (the next power of two) lanes per row, 64 / lanes rows per wave,
+// one unit per lane -- the gradient unit stays in its register between the row's test and its update.  Wider rows: a wave
+// per row, 64 units per sweep; the first ROW_KEEP sweeps of the gradient stay in registers, later ones are read again for
+// the update.  The row's "any non-zero" is one ballot, taken before any access to param / exp_avg / exp_avg_sq.
+// Without mask and zero test every row is live and rows carry no meaning: the host hands such a tensor over as
+// n_rows * units rows of one unit (the dense kernel's mapping).
+namespace {
+
+constexpr int ROW_KEEP = 4;            // sweeps of a wide row's gradient kept in registers (float4: rows up to 1024 floats)
+constexpr int ROWS_MAX_BLOCKS = 256 * 32;
+
+struct AdamItem {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    int64_t rows;    // rows of this tensor as the kernel walks it
+    int64_t units;   // units per row
+    int32_t vec;     // unit = float4
+    int32_t shift;   // units <= 64: 1 << shift lanes per row (the power of two >= units), 64 >> shift rows per wave; else 6
+    AdamScalars s;
+};
+struct AdamTable {
+    AdamItem t[GAGS_ADAM_MAX_TENSORS];
+};
+
+__device__ __forceinline__ bool nonzero(float x) { return (__float_as_uint(x) & 0x7fffffffu) != 0u; }
+__device__ __forceinline__ bool nonzero(const float4 &x)
+{
+    return ((int)nonzero(x.x) | (int)nonzero(x.y) | (int)nonzero(x.z) | (int)nonzero(x.w)) != 0;
+}
+__device__ __forceinline__ void zero_unit(float &x) { x = 0.f; }
+__device__ __forceinline__ void zero_unit(float4 &x) { x = make_float4(0.f, 0.f, 0.f, 0.f); }
+
+__device__ __forceinline__ void adam_unit(float *p, float *m, float *v, int64_t i, float g, const AdamScalars &s)
+{
+    float pp = p[i], mm = m[i], vv = v[i];
+    adam1(pp, g, mm, vv, s);
+    p[i] = pp; m[i] = mm; v[i] = vv;
+}
+__device__ __forceinline__ void adam_unit(float4 *p, float4 *m, float4 *v, int64_t i, const float4 &g, const AdamScalars &s)
+{
+    float4 pp = p[i], mm = m[i], vv = v[i];
+    adam1(pp.x, g.x, mm.x, vv.x, s);
+    adam1(pp.y, g.y, mm.y, vv.y, s);
+    adam1(pp.z, g.z, mm.z, vv.z, s);
+    adam1(pp.w, g.w, mm.w, vv.w, s);
+    p[i] = pp; m[i] = mm; v[i] = vv;
+}
+
+template <typename T, bool TEST>
+__device__ __forceinline__ void adam_rows_body(const AdamItem &it, const uint8_t *__restrict__ mask)
+{
+    T *p = reinterpret_cast<T *>(it.p), *m = reinterpret_cast<T *>(it.m), *v = reinterpret_cast<T *>(it.v);
+    const T *g = reinterpret_cast<const T *>(it.g);
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
+    const int64_t rows = it.rows, units = it.units;
+    if (units <= 64) {
+        const int shift = it.shift, lanes = 1 << shift, rows_shift = 6 - shift;  // 1 << rows_shift rows per wave
+        const int col = lane & (lanes - 1), first = lane - col;  // first lane of this lane's row
+        const unsigned long long group = lanes == 64 ? ~0ull : ((1ull << lanes) - 1ull);
+        const int64_t tasks = (rows + (1 << rows_shift) - 1) >> rows_shift;
+        for (int64_t task = wave; task < tasks; task += n_waves) {  // (trip count is wave-uniform: the ballot sees 64 lanes)
+            const int64_t row = (task << rows_shift) + (first >> shift);
+            bool live = row < rows && col < units;
+            if (live && mask) live = mask[row] != 0;
+            const int64_t i = row * units + col;
+            T gg;
+            zero_unit(gg);
+            if (live) gg = g[i];
+            if (TEST) {
+                const unsigned long long any = __ballot(live && nonzero(gg));
+                live = live && ((any >> first) & group) != 0ull;
+            }
+            if (live) adam_unit(p, m, v, i, gg, it.s);
+        }
+    } else {
+        for (int64_t row = wave; row < rows; row += n_waves) {  // everything that skips a row here is wave-uniform
+            if (mask && mask[row] == 0) continue;
+            const int64_t base = row * units;
+            T keep[ROW_KEEP];
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < ROW_KEEP; ++k) {
+                const int64_t c = (int64_t)k * 64 + lane;
+                zero_unit(keep[k]);
+                if (c < units) keep[k] = g[base + c];
+                any |= nonzero(keep[k]);
+            }
+            if (TEST) {
+                for (int64_t c = (int64_t)ROW_KEEP * 64 + lane; c < units; c += 64) any |= nonzero(g[base + c]);
+                if (__ballot(any) == 0ull) continue;
+            }
+#pragma unroll
+            for (int k = 0; k < ROW_KEEP; ++k) {
+                const int64_t c = (int64_t)k * 64 + lane;
+                if (c < units) adam_unit(p, m, v, base + c, keep[k], it.s);
+            }
+            for (int64_t c = (int64_t)ROW_KEEP * 64 + lane; c < units; c += 64) adam_unit(p, m, v, base + c, g[base + c], it.s);
+        }
+    }
+}
+
+template <bool TEST>
+__global__ __launch_bounds__(256) void adam_rows_kernel(const uint8_t *__restrict__ mask, AdamTable tab)
+{
+    const AdamItem &it = tab.t[blockIdx.y];
+    if (it.vec)
+        adam_rows_body<float4, TEST>(it, mask);
+    else
+        adam_rows_body<float, TEST>(it, mask);
+}
+
+}  // namespace
+
+extern "C" int64_t gags_adam_tensor_bytes(void) { return (int64_t)sizeof(gags_adam_tensor); }
+
+extern "C" int gags_adam_step_rows(int64_t n_rows, int32_t n_tensors, const gags_adam_tensor *tensors, const uint8_t *row_mask,
+                                   int32_t flags, int32_t step, void *stream)
+{
+    if (n_rows < 0 || n_tensors < 1 || n_tensors > GAGS_ADAM_MAX_TENSORS || step < 1 || !tensors) return GAGS_EINVAL;
+    if (flags & ~(GAGS_ADAM_SKIP_ZERO_ROWS | GAGS_ADAM_NO_BIAS_CORRECTION)) return GAGS_EINVAL;
+    const bool test = flags & GAGS_ADAM_SKIP_ZERO_ROWS;
+    const bool dense = !test && !row_mask;
+    AdamTable tab = {};
+    int64_t most = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        const gags_adam_tensor &d = tensors[t];
+        if (d.width < 1 || !(d.beta1 >= 0.0 && d.beta1 < 1.0) || !(d.beta2 >= 0.0 && d.beta2 < 1.0) || !(d.eps >= 0.0))
+            return GAGS_EINVAL;
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(d.param) | reinterpret_cast<uintptr_t>(d.grad) |
+                               reinterpret_cast<uintptr_t>(d.exp_avg) | reinterpret_cast<uintptr_t>(d.exp_avg_sq);
+        if (bits & 3) return GAGS_EINVAL;
+        if (n_rows > 0 && (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq)) return GAGS_EINVAL;
+        AdamItem &it = tab.t[t];
+        it.p = d.param; it.g = d.grad; it.m = d.exp_avg; it.v = d.exp_avg_sq;
+        it.vec = (bits & 15) == 0 && d.width % 4 == 0;
+        it.rows = n_rows;
+        it.units = it.vec ? d.width / 4 : d.width;
+        if (dense) {  // no row is ever skipped: one unit per lane over the whole tensor
+            it.rows = n_rows * it.units;
+            it.units = 1;
+        }
+        it.shift = 6;
+        if (it.units <= 64) {
+            it.shift = 0;
+            while ((1 << it.shift) < it.units) ++it.shift;
+        }
+        const int64_t per_wave = 64 >> it.shift;  // rows a wave takes per trip (1 for a wide row)
+        const int64_t waves = (it.rows + per_wave - 1) / per_wave;
+        if (waves > most) most = waves;
+        // the scalars exactly as gags_adam_step forms them
+        const double bc1 = 1.0 - pow(d.beta1, (double)step), bc2 = 1.0 - pow(d.beta2, (double)step);
+        it.s.w1 = (float)(1.0 - d.beta1); it.s.b2 = (float)d.beta2; it.s.w2 = (float)(1.0 - d.beta2);
+        it.s.step_size = (float)(d.lr / bc1); it.s.bc2_sqrt = (float)sqrt(bc2); it.s.eps = (float)d.eps;
+        if (flags & GAGS_ADAM_NO_BIAS_CORRECTION) {
+            it.s.step_size = (float)d.lr;
+            it.s.bc2_sqrt = 1.0f;
+        }
+    }
+    if (n_rows == 0) return GAGS_OK;
+    GAGS_CLEAR_ERR();
+    const int64_t want = (most + 3) / 4;
+    const dim3 grid((unsigned)(want < ROWS_MAX_BLOCKS ? want : ROWS_MAX_BLOCKS), (unsigned)n_tensors);
+    if (test)
+        hipLaunchKernelGGL(adam_rows_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, row_mask, tab);
+    else
+        hipLaunchKernelGGL(adam_rows_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, row_mask, tab);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
+}
+
 // ---- harness helper: loss = <render, G>, the terminal loss of the synthetic step -------------
 // Two 4.25 GB streams at C3: one read each, fp32 partial sums per thread, double across threads / blocks; fixed
 // grid and order => reproducible.  (rocBLAS sdot runs the same reduction at ~4.8 TB/s; this one is bandwidth-bound.)

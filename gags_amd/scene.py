@@ -283,8 +283,11 @@ class GaussianModel:
         self.xyz_gradient_accum, self.denom = xyz_gradient_accum, denom
         return self
 
-    def training_setup(self, semantic_feature_lr=0.001, semantic_dim=16):
-        """Feature-only optimisation, as scene/gaussian_model.py:183-208."""
+    def training_setup(self, semantic_feature_lr=0.001, semantic_dim=16, optimizer_type="default"):
+        """Feature-only optimisation, as scene/gaussian_model.py:183-208.  optimizer_type="sparse_adam": the same group in
+        optim.SelectiveAdam(skip_zero_rows=True) -- the rows the backward left at zero keep parameter and moments."""
+        if optimizer_type not in ("default", "sparse_adam"):
+            raise ValueError(f"optimizer_type must be 'default' or 'sparse_adam', not {optimizer_type!r}")
         n = self._xyz.shape[0]
         if self._semantic_feature is None or self._semantic_feature.shape[0] != n:
             self._semantic_feature = nn.Parameter(
@@ -293,7 +296,10 @@ class GaussianModel:
             p.requires_grad_(False)
         # same constructor call as the reference; on the GPU the step is the single-pass HIP kernel
         groups = [{"params": [self._semantic_feature], "lr": semantic_feature_lr, "name": "semantic_feature"}]
-        if self._semantic_feature.is_cuda:
+        if optimizer_type == "sparse_adam":
+            from .optim import SelectiveAdam
+            self.optimizer = SelectiveAdam(groups, lr=0.0, eps=1e-15, skip_zero_rows=True)
+        elif self._semantic_feature.is_cuda:
             from .optim import FeatureAdam
             self.optimizer = FeatureAdam(groups, lr=0.0, eps=1e-15)
         else:  # host-side bookkeeping only (CPU unit tests): the stock optimizer the reference uses
@@ -302,12 +308,16 @@ class GaussianModel:
 
     # -- the RGB stage's optimizer and adaptive density control: scene/gaussian_model.py:147-149, 183-220, 261-264, 321-482
     #    (gags_amd/densify.py; train.py:206-218 runs on these unchanged) ------------------------------------------------
-    def training_setup_rgb(self, training_args, semantic_dim=16, spatial_lr_scale=None):
+    def training_setup_rgb(self, training_args, semantic_dim=16, spatial_lr_scale=None, optimizer_type="default"):
         """Every tensor optimised: the seven named groups the reference's training_setup keeps as comments
         (scene/gaussian_model.py:193-199) with the rates of arguments/__init__.py:76-85, FeatureAdam(lr=0.0, eps=1e-15), the
-        densification statistics, percent_dense and the position schedule.  training_setup (feature-only) is untouched."""
+        densification statistics, percent_dense and the position schedule.  training_setup (feature-only) is untouched.
+        optimizer_type="sparse_adam": the same groups in optim.SelectiveAdam, one launch for the seven tensors; the training
+        loop passes the view's mask, optimizer.step(render_pkg["visibility_filter"])."""
         from . import densify
-        from .optim import FeatureAdam
+        from .optim import FeatureAdam, SelectiveAdam
+        if optimizer_type not in ("default", "sparse_adam"):
+            raise ValueError(f"optimizer_type must be 'default' or 'sparse_adam', not {optimizer_type!r}")
         if not self._xyz.is_cuda:
             raise RuntimeError("gags_amd.scene.training_setup_rgb: no CPU path (the model must live on the GPU)")
         n, dev = self._xyz.shape[0], self._xyz.device
@@ -337,7 +347,7 @@ class GaussianModel:
             {"params": [self._rotation], "lr": a.rotation_lr, "name": "rotation"},
             {"params": [self._semantic_feature], "lr": a.semantic_feature_lr, "name": "semantic_feature"},
         ]
-        self.optimizer = FeatureAdam(groups, lr=0.0, eps=1e-15)
+        self.optimizer = (SelectiveAdam if optimizer_type == "sparse_adam" else FeatureAdam)(groups, lr=0.0, eps=1e-15)
         self.xyz_scheduler_args = dict(lr_init=a.position_lr_init * self.spatial_lr_scale,
                                        lr_final=a.position_lr_final * self.spatial_lr_scale,
                                        lr_delay_mult=a.position_lr_delay_mult, max_steps=a.position_lr_max_steps)

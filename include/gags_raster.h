@@ -484,6 +484,34 @@ int gags_ed_normalize(int64_t n_pix, int d, float *render_colors, const float *r
 int gags_adam_step(int64_t numel, float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
                    double lr, double beta1, double beta2, double eps, int step, void *stream);
 
+/* N19: row-selective Adam, every tensor of a step in ONE launch.  Tensor t is [n_rows, width_t] fp32, row-major and
+ * contiguous; its four arrays share that shape.  Row r of tensor t is updated iff
+ *     (row_mask == NULL || row_mask[r] != 0)  &&  (!(flags & GAGS_ADAM_SKIP_ZERO_ROWS) || grad_t[r, :] has a non-zero),
+ * "non-zero" by bit pattern (bits & 0x7fffffff: -0.0 is zero, NaN is not), decided per tensor.  A row that is not updated
+ * keeps param, exp_avg and exp_avg_sq bit for bit (its moments do NOT decay); an updated element holds exactly the bits
+ * gags_adam_step writes (same arithmetic, same host scalars).  `step` is the global 1-based count, there is no per-row
+ * counter.  GAGS_ADAM_NO_BIAS_CORRECTION: step_size = lr and sqrt(v) is not divided.
+ * tensors: a HOST array of n_tensors descriptors (1 .. GAGS_ADAM_MAX_TENSORS), copied into the kernel argument: no device
+ * allocation, no global state, no readback.  Pointers need 4-byte alignment only (a row slice, a view at an odd offset);
+ * a tensor whose four bases are 16-byte aligned with width % 4 == 0 is accessed 16 bytes per lane.  row_mask: device,
+ * n_rows bytes.  Traffic of a skipped row: the mask byte (mask), or the gradient row once (zero test); nothing else.
+ * GAGS_EINVAL, nothing launched: n_rows < 0, n_tensors outside [1, 8], step < 1, unknown flag bits, width < 1, betas
+ * outside [0, 1), eps < 0, a pointer not 4-byte aligned, a NULL array with n_rows > 0.  n_rows == 0: GAGS_OK. */
+typedef struct {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t width;
+    double lr, beta1, beta2, eps;
+} gags_adam_tensor;
+#define GAGS_ADAM_MAX_TENSORS 8
+#define GAGS_ADAM_SKIP_ZERO_ROWS 1
+#define GAGS_ADAM_NO_BIAS_CORRECTION 2
+int64_t gags_adam_tensor_bytes(void); /* sizeof(gags_adam_tensor): lets a binding check its mirror of the struct */
+int gags_adam_step_rows(int64_t n_rows, int32_t n_tensors, const gags_adam_tensor *tensors, const uint8_t *row_mask,
+                        int32_t flags, int32_t step, void *stream);
+
 /* Multi-GPU by-view step (north_star "RCCL all-reduce of feature/geometry gradients"): the exchange itself is
  * torch.distributed over RCCL; these two kernels move the rows that can be non-zero between the gradient [N, d] and
  * the dense wire block [n_rows, cw] of one channel range [c0, c0 + cw).  idx: int64 row numbers (device; NULL = all rows,
