@@ -47,6 +47,11 @@ SIGNATURES = {
     "gags_project_bwd_pose": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_colsum_f32": (_i32, [_i64, _i32, _vp, _f32, _vp, _i32, _vp]),
+    # N20: camera models (camera_model, flags, n, ...): the union of the projection entries' arguments
+    "gags_project_fwd_cam": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gags_project_bwd_cam": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_scan_scratch_bytes": (_i64, [_i32]),
     "gags_cumsum_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_cumsum_gather_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -264,6 +269,9 @@ GAGS_ADAM_MAX_TENSORS, GAGS_ADAM_SKIP_ZERO_ROWS, GAGS_ADAM_NO_BIAS_CORRECTION = 
 
 GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instructions (what GAGS_BWD_F32MFMA asks of that kernel)
 GAGS_POSE_RAW, GAGS_POSE_AA = 1, 2  # `flags` of gags_project_bwd_pose
+GAGS_CAM_PINHOLE, GAGS_CAM_ORTHO, GAGS_CAM_FISHEYE = 0, 1, 2  # `camera_model` of gags_project_fwd_cam / gags_project_bwd_cam
+GAGS_PROJ_RAW, GAGS_PROJ_AA, GAGS_PROJ_POSE = 1, 2, 4  # their `flags`
+CAMERA_MODELS = {"pinhole": GAGS_CAM_PINHOLE, "ortho": GAGS_CAM_ORTHO, "fisheye": GAGS_CAM_FISHEYE}  # rasterization(camera_model=)
 GAGS_GEOM_ABSGRAD = 64  # `flags` of gags_raster_bwd_geom: columns 6, 7 of v_geo carry absgrad (rasterization(absgrad=True))
 
 _lib = None

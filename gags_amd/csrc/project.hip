@@ -24,6 +24,149 @@ __device__ __forceinline__ Cam load_cam(const float *__restrict__ vm, const floa
     return c;
 }
 
+// N20: the camera model.  It decides where a centre lands (means2d) and the 2 x 3 Jacobian J that carries the camera-space
+// covariance to the screen (cov2d = J Sc J^T); everything else of the projection is shared.  cam_fwd / cam_bwd are the ONE place
+// where each model's arithmetic stands: the forward kernel and the backward kernel (which recomputes the forward) call cam_fwd,
+// the backward calls cam_bwd, in every RAW / AA / POSE variant.  The pinhole bodies are the expressions the kernels held before
+// N20, token for token: same operation order, same bits.
+//   ortho:    means2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]; no clamp.
+//   fisheye:  equidistant, no distortion, no clamp; eps = 1e-7:  rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
+//             means2d = (fx x theta / rho + cx, fy y theta / rho + cy); x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2,
+//             l2 = s + z^2, b = atan2(rho, z) / rho / s, a = z / (l2 s),
+//             J = [[fx (x2 a + y2 b), fx xy (a - b), -fx x / l2], [fy xy (a - b), fy (y2 a + x2 b), -fy y / l2]].
+//             J is this closed form, guards included (on the axis: fx / z, fy / z, 0 elsewhere), and cam_bwd is its exact
+//             derivative, d sqrt(x^2 + y^2) taken as 0 at x = y = 0.
+struct CamLim { float x_pos, x_neg, y_pos, y_neg; };  // the pinhole's tangent clamp (0.3 of the half field of view past the image)
+
+__device__ __forceinline__ CamLim cam_limits(float fx, float fy, float cx, float cy, int width, int height)
+{
+    const float fw = (float)width, fh = (float)height;
+    const float tan_fovx = 0.5f * fw / fx;
+    const float tan_fovy = 0.5f * fh / fy;
+    CamLim l;
+    l.x_pos = (fw - cx) / fx + 0.3f * tan_fovx;
+    l.x_neg = cx / fx + 0.3f * tan_fovx;
+    l.y_pos = (fh - cy) / fy + 0.3f * tan_fovy;
+    l.y_neg = cy / fy + 0.3f * tan_fovy;
+    return l;
+}
+
+constexpr float GAGS_FISHEYE_EPS = 1e-7f;
+
+template <int CAM>
+__device__ __forceinline__ void cam_fwd(float fx, float fy, float cx, float cy, const CamLim &lim, float x, float y, float z,
+                                        float &m2x, float &m2y, float (&J)[2][3])
+{
+    if constexpr (CAM == GAGS_CAM_PINHOLE) {
+        const float rz = 1.f / z;
+        const float rz2 = rz * rz;
+        const float tx = z * fminf(lim.x_pos, fmaxf(-lim.x_neg, x * rz));
+        const float ty = z * fminf(lim.y_pos, fmaxf(-lim.y_neg, y * rz));
+        J[0][0] = fx * rz; J[0][1] = 0.f; J[0][2] = -fx * tx * rz2;
+        J[1][0] = 0.f; J[1][1] = fy * rz; J[1][2] = -fy * ty * rz2;
+        m2x = fx * x * rz + cx;
+        m2y = fy * y * rz + cy;
+    } else if constexpr (CAM == GAGS_CAM_ORTHO) {
+        J[0][0] = fx; J[0][1] = 0.f; J[0][2] = 0.f;
+        J[1][0] = 0.f; J[1][1] = fy; J[1][2] = 0.f;
+        m2x = fx * x + cx;
+        m2y = fy * y + cy;
+    } else {
+        const float rho = sqrtf(x * x + y * y) + GAGS_FISHEYE_EPS;
+        const float theta = atan2f(rho, z + GAGS_FISHEYE_EPS);
+        const float k = theta / rho;
+        m2x = (fx * x) * k + cx;
+        m2y = (fy * y) * k + cy;
+        const float x2 = x * x + GAGS_FISHEYE_EPS, y2 = y * y, xy = x * y;
+        const float s = x2 + y2, l2 = s + z * z;
+        const float b = atan2f(rho, z) / rho / s, a = z / (l2 * s);
+        const float amb = a - b;
+        J[0][0] = fx * (x2 * a + y2 * b); J[0][1] = (fx * xy) * amb; J[0][2] = -fx * x / l2;
+        J[1][0] = (fy * xy) * amb; J[1][1] = fy * (y2 * a + x2 * b); J[1][2] = -fy * y / l2;
+    }
+}
+
+// (v_means2d, vJ) -> vp, the cotangent of the camera-space point; v_depth (the cotangent of depths = z, when has_depth) joins
+// vp[2] where the pinhole kernel has always added it, between the means2d term and the J terms.
+template <int CAM>
+__device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, float x, float y, float z, float vm2x, float vm2y,
+                                        const float (&vJ)[2][3], bool has_depth, float v_depth, float (&vp)[3])
+{
+    if constexpr (CAM == GAGS_CAM_PINHOLE) {
+        const float rz = 1.f / z, rz2 = rz * rz, rz3 = rz2 * rz;
+        const float xr = x * rz, yr = y * rz;
+        const int x_in = (xr <= lim.x_pos) && (xr >= -lim.x_neg);
+        const int y_in = (yr <= lim.y_pos) && (yr >= -lim.y_neg);
+        const float tx = z * fminf(lim.x_pos, fmaxf(-lim.x_neg, xr));
+        const float ty = z * fminf(lim.y_pos, fmaxf(-lim.y_neg, yr));
+        vp[0] = fx * rz * vm2x;
+        vp[1] = fy * rz * vm2y;
+        vp[2] = -(fx * x * vm2x + fy * y * vm2y) * rz2;
+        if (has_depth) vp[2] += v_depth;
+        if (x_in) vp[0] += -fx * rz2 * vJ[0][2]; else vp[2] += -fx * rz3 * vJ[0][2] * tx;
+        if (y_in) vp[1] += -fy * rz2 * vJ[1][2]; else vp[2] += -fy * rz3 * vJ[1][2] * ty;
+        vp[2] += -fx * rz2 * vJ[0][0] - fy * rz2 * vJ[1][1] + 2.f * fx * tx * rz3 * vJ[0][2] + 2.f * fy * ty * rz3 * vJ[1][2];
+    } else if constexpr (CAM == GAGS_CAM_ORTHO) {
+        vp[0] = fx * vm2x;  // (J is constant: vJ reaches nothing)
+        vp[1] = fy * vm2y;
+        vp[2] = has_depth ? v_depth : 0.f;
+    } else {
+        const float r0 = sqrtf(x * x + y * y);
+        const float rho = r0 + GAGS_FISHEYE_EPS, zt = z + GAGS_FISHEYE_EPS;
+        const float theta = atan2f(rho, zt);
+        const float k = theta / rho;
+        const float x2 = x * x + GAGS_FISHEYE_EPS, y2 = y * y, xy = x * y;
+        const float s = x2 + y2, z2 = z * z, l2 = s + z2;
+        const float tb = atan2f(rho, z);
+        const float b = tb / rho / s, a = z / (l2 * s);
+        // means2d = (fx x k + cx, fy y k + cy), k = theta / rho
+        const float v_k = (fx * x) * vm2x + (fy * y) * vm2y;
+        float vx = (fx * k) * vm2x, vy = (fy * k) * vm2y, vz = has_depth ? v_depth : 0.f;
+        const float v_theta = v_k / rho;
+        float v_rho = -(v_k * k) / rho;
+        // J (the closed form): cotangents of x2, y2, xy, a, b, l2
+        const float g00 = fx * vJ[0][0], g01 = fx * vJ[0][1], g02 = fx * vJ[0][2];
+        const float g10 = fy * vJ[1][0], g11 = fy * vJ[1][1], g12 = fy * vJ[1][2];
+        const float gx = g01 + g10;
+        float v_x2 = g00 * a + g11 * b;
+        float v_y2 = g00 * b + g11 * a;
+        const float v_a = (g00 * x2 + g11 * y2) + gx * xy;
+        const float v_b = (g00 * y2 + g11 * x2) - gx * xy;
+        const float v_xy = gx * (a - b);
+        vx += -g02 / l2;
+        vy += -g12 / l2;
+        float v_l2 = (g02 * x + g12 * y) / (l2 * l2);
+        // a = z / (l2 s)
+        vz += v_a / (l2 * s);
+        v_l2 += -(v_a * a) / l2;
+        float v_s = -(v_a * a) / s;
+        // b = tb / (rho s), tb = atan2(rho, z)
+        const float v_tb = v_b / (rho * s);
+        v_rho += -(v_b * b) / rho;
+        v_s += -(v_b * b) / s;
+        const float hb = rho * rho + z2;
+        v_rho += v_tb * z / hb;
+        vz += -(v_tb * rho) / hb;
+        // l2 = s + z^2, s = x2 + y2, x2 = x^2 + eps, y2 = y^2, xy = x y
+        v_s += v_l2;
+        vz += 2.f * z * v_l2;
+        v_x2 += v_s;
+        v_y2 += v_s;
+        vx += 2.f * x * v_x2 + y * v_xy;
+        vy += 2.f * y * v_y2 + x * v_xy;
+        // theta = atan2(rho, z + eps)
+        const float ht = rho * rho + zt * zt;
+        v_rho += v_theta * zt / ht;
+        vz += -(v_theta * rho) / ht;
+        // rho = sqrt(x^2 + y^2) + eps; its derivative at x = y = 0 is taken as 0
+        if (r0 > 0.f) {
+            vx += v_rho * (x / r0);
+            vy += v_rho * (y / r0);
+        }
+        vp[0] = vx; vp[1] = vy; vp[2] = vz;
+    }
+}
+
 // The activations of scene/gaussian_model.py:116-139 as torch evaluates them on this stack, bit for bit
 // (tools/micro/actprobe.py: 0 of 4 M values differ): get_scaling = exp(_scaling) (* scaling_modifier in render()),
 // get_rotation = F.normalize(_rotation) = q / max(|q|, 1e-12) with |q|^2 summed pairwise, get_opacity = sigmoid(_opacity).
@@ -41,7 +184,7 @@ __device__ __forceinline__ float gags_act_opacity(float o) { return 1.0f / (1.0f
 // AA (rasterize_mode "antialiased", include/gags_raster.h): compensations[i] = sqrt(max(0, det(cov2d) / det(cov2d + eps2d I))),
 // 0 for a culled Gaussian; RAW folds it into the activated opacity and the record.  Nothing else changes: the blurred
 // covariance still decides radius, conic and tile count.
-template <bool RAW, bool AA>
+template <bool RAW, bool AA, int CAM>
 __global__ __launch_bounds__(256) void project_fwd_kernel(
     int n, const float *__restrict__ means, const float *__restrict__ quats,
     const float *__restrict__ scales, const float *__restrict__ viewmat, const float *__restrict__ Kmat,
@@ -68,12 +211,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     }
     const Cam c = load_cam(viewmat, Kmat);
     const float fw = (float)width, fh = (float)height;
-    const float tan_fovx = 0.5f * fw / c.fx;
-    const float tan_fovy = 0.5f * fh / c.fy;
-    const float lim_x_pos = (fw - c.cx) / c.fx + 0.3f * tan_fovx;
-    const float lim_x_neg = c.cx / c.fx + 0.3f * tan_fovx;
-    const float lim_y_pos = (fh - c.cy) / c.fy + 0.3f * tan_fovy;
-    const float lim_y_neg = c.cy / c.fy + 0.3f * tan_fovy;
+    const CamLim lim = cam_limits(c.fx, c.fy, c.cx, c.cy, width, height);
 
     int32_t o_rad = 0, o_tiles = 0;
     float o_mx = 0.f, o_my = 0.f, o_z = 0.f, o_a = 0.f, o_b = 0.f, o_c = 0.f;
@@ -118,22 +256,31 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
         const float v12 = (a10 * c.R20 + a11 * c.R21) + a12 * c.R22;
         const float v22 = (a20 * c.R20 + a21 * c.R21) + a22 * c.R22;
 
-        const float rz = 1.f / z;
-        const float rz2 = rz * rz;
-        const float tx = z * fminf(lim_x_pos, fmaxf(-lim_x_neg, x * rz));
-        const float ty = z * fminf(lim_y_pos, fmaxf(-lim_y_neg, y * rz));
-        const float j00 = c.fx * rz, j02 = -c.fx * tx * rz2;
-        const float j11 = c.fy * rz, j12 = -c.fy * ty * rz2;
-        const float b00 = j00 * v00 + j02 * v02;
-        const float b01 = j00 * v01 + j02 * v12;
-        const float b02 = j00 * v02 + j02 * v22;
-        const float b11 = j11 * v11 + j12 * v12;
-        const float b12 = j11 * v12 + j12 * v22;
-        float s00 = b00 * j00 + b02 * j02;
-        const float s01 = b01 * j11 + b02 * j12;
-        float s11 = b11 * j11 + b12 * j12;
-        const float m2x = c.fx * x * rz + c.cx;
-        const float m2y = c.fy * y * rz + c.cy;
+        float m2x, m2y, J[2][3];
+        cam_fwd<CAM>(c.fx, c.fy, c.cx, c.cy, lim, x, y, z, m2x, m2y, J);
+        float s00, s01, s11;
+        if constexpr (CAM != GAGS_CAM_FISHEYE) {  // J[0][1] = J[1][0] = 0: the products the pinhole kernel has always formed
+            const float j00 = J[0][0], j02 = J[0][2];
+            const float j11 = J[1][1], j12 = J[1][2];
+            const float b00 = j00 * v00 + j02 * v02;
+            const float b01 = j00 * v01 + j02 * v12;
+            const float b02 = j00 * v02 + j02 * v22;
+            const float b11 = j11 * v11 + j12 * v12;
+            const float b12 = j11 * v12 + j12 * v22;
+            s00 = b00 * j00 + b02 * j02;
+            s01 = b01 * j11 + b02 * j12;
+            s11 = b11 * j11 + b12 * j12;
+        } else {  // a full J, in the order of the backward kernel
+            const float b00 = (J[0][0] * v00 + J[0][1] * v01) + J[0][2] * v02;
+            const float b01 = (J[0][0] * v01 + J[0][1] * v11) + J[0][2] * v12;
+            const float b02 = (J[0][0] * v02 + J[0][1] * v12) + J[0][2] * v22;
+            const float b10 = (J[1][0] * v00 + J[1][1] * v01) + J[1][2] * v02;
+            const float b11 = (J[1][0] * v01 + J[1][1] * v11) + J[1][2] * v12;
+            const float b12 = (J[1][0] * v02 + J[1][1] * v12) + J[1][2] * v22;
+            s00 = (b00 * J[0][0] + b01 * J[0][1]) + b02 * J[0][2];
+            s01 = (b00 * J[1][0] + b01 * J[1][1]) + b02 * J[1][2];
+            s11 = (b10 * J[1][0] + b11 * J[1][1]) + b12 * J[1][2];
+        }
 
         float det_o = 0.f;  // (AA: the determinant before the blur)
         if constexpr (AA) det_o = s00 * s11 - s01 * s01;
@@ -177,7 +324,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
 
 namespace {
 
-template <bool RAW, bool AA>
+template <bool RAW, bool AA, int CAM = GAGS_CAM_PINHOLE>
 int project_fwd_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
                        float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
                        float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d, float *depths,
@@ -192,7 +339,7 @@ int project_fwd_launch(int n, const float *means, const float *quats, const floa
     if (RAW && (!opacity_logit || !opacities)) return GAGS_EINVAL;
     if (AA && !compensations) return GAGS_EINVAL;
     const int tile_w = (width + GAGS_TILE - 1) / GAGS_TILE, tile_h = (height + GAGS_TILE - 1) / GAGS_TILE;
-    hipLaunchKernelGGL((project_fwd_kernel<RAW, AA>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
+    hipLaunchKernelGGL((project_fwd_kernel<RAW, AA, CAM>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
                        quats, scales, viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip,
                        tile_w, tile_h, radii, means2d, depths, conics, tiles_per_gauss, opacity_logit, scaling_modifier,
                        opacities, quats_act, scales_act, reinterpret_cast<gags_mfma::GRec *>(grec), compensations);
@@ -276,7 +423,7 @@ namespace {
         if constexpr (POSE) break;     \
         else return;                   \
     }
-template <bool RAW, bool AA, bool POSE>
+template <bool RAW, bool AA, bool POSE, int CAM>
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     int N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmat, const float *__restrict__ Kmat, int width, int height, float eps2d,
@@ -311,10 +458,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
                             {viewmat[8], viewmat[9], viewmat[10]}};
     const float tc[3] = {viewmat[3], viewmat[7], viewmat[11]};
     const float fx = Kmat[0], cx = Kmat[2], fy = Kmat[4], cy = Kmat[5];
-    const float fw = (float)width, fh = (float)height;
-    const float tan_fovx = 0.5f * fw / fx, tan_fovy = 0.5f * fh / fy;
-    const float lim_x_pos = (fw - cx) / fx + 0.3f * tan_fovx, lim_x_neg = cx / fx + 0.3f * tan_fovx;
-    const float lim_y_pos = (fh - cy) / fy + 0.3f * tan_fovy, lim_y_neg = cy / fy + 0.3f * tan_fovy;
+    const CamLim lim = cam_limits(fx, fy, cx, cy, width, height);
         /* ---- recompute forward intermediates ---- */
         const float mu[3] = {means[3 * i], means[3 * i + 1], means[3 * i + 2]};
         float p[3];
@@ -343,13 +487,9 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
             A[r][c] = (Rc[r][0] * S3[0][c] + Rc[r][1] * S3[1][c]) + Rc[r][2] * S3[2][c];
         _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 3; ++c)
             Sc[r][c] = (A[r][0] * Rc[c][0] + A[r][1] * Rc[c][1]) + A[r][2] * Rc[c][2];
-        const float rz = 1.f / z, rz2 = rz * rz, rz3 = rz2 * rz;
-        const float xr = x * rz, yr = y * rz;
-        const int x_in = (xr <= lim_x_pos) && (xr >= -lim_x_neg);
-        const int y_in = (yr <= lim_y_pos) && (yr >= -lim_y_neg);
-        const float tx = z * fminf(lim_x_pos, fmaxf(-lim_x_neg, xr));
-        const float ty = z * fminf(lim_y_pos, fmaxf(-lim_y_neg, yr));
-        const float J[2][3] = {{fx * rz, 0.f, -fx * tx * rz2}, {0.f, fy * rz, -fy * ty * rz2}};
+        float m2x_, m2y_, J[2][3];  // (the centre itself is not needed again)
+        cam_fwd<CAM>(fx, fy, cx, cy, lim, x, y, z, m2x_, m2y_, J);
+        (void)m2x_; (void)m2y_;
         float B[2][3];
         _Pragma("unroll") for (int r = 0; r < 2; ++r) _Pragma("unroll") for (int c = 0; c < 3; ++c)
             B[r][c] = (J[r][0] * Sc[0][c] + J[r][1] * Sc[1][c]) + J[r][2] * Sc[2][c];
@@ -401,13 +541,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         /* ---- 3. J and mean2d/depth -> camera-space point ---- */
         const float vm2x = v_means2d[2 * i], vm2y = v_means2d[2 * i + 1];
         float vp[3];
-        vp[0] = fx * rz * vm2x;
-        vp[1] = fy * rz * vm2y;
-        vp[2] = -(fx * x * vm2x + fy * y * vm2y) * rz2;
-        if (v_depths) vp[2] += v_depths[i];
-        if (x_in) vp[0] += -fx * rz2 * vJ[0][2]; else vp[2] += -fx * rz3 * vJ[0][2] * tx;
-        if (y_in) vp[1] += -fy * rz2 * vJ[1][2]; else vp[2] += -fy * rz3 * vJ[1][2] * ty;
-        vp[2] += -fx * rz2 * vJ[0][0] - fy * rz2 * vJ[1][1] + 2.f * fx * tx * rz3 * vJ[0][2] + 2.f * fy * ty * rz3 * vJ[1][2];
+        cam_bwd<CAM>(fx, fy, lim, x, y, z, vm2x, vm2y, vJ, v_depths != nullptr, v_depths ? v_depths[i] : 0.f, vp);
         if constexpr (POSE) {
             _Pragma("unroll") for (int r = 0; r < 3; ++r) {
                 _Pragma("unroll") for (int c = 0; c < 3; ++c)
@@ -499,7 +633,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(int64_t n_rows, int k, cons
 
 namespace {
 
-template <bool RAW, bool AA>
+template <bool RAW, bool AA, int CAM = GAGS_CAM_PINHOLE>
 int project_bwd_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
                        float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
                        const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
@@ -512,7 +646,7 @@ int project_bwd_launch(int n, const float *means, const float *quats, const floa
     if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics || !v_means || !v_quats || !v_scales)
         return GAGS_EINVAL;
     if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
-    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, false>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
+    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, false, CAM>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
                        quats, scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats,
                        v_scales, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, nullptr);
     GAGS_CHECK_LAUNCH();
@@ -528,7 +662,7 @@ int colsum_launch(int64_t n_rows, int k, const float *table, float sign, float *
     return GAGS_OK;
 }
 
-template <bool RAW, bool AA>
+template <bool RAW, bool AA, int CAM = GAGS_CAM_PINHOLE>
 int project_bwd_pose_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
                             float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
                             const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
@@ -539,7 +673,7 @@ int project_bwd_pose_launch(int n, const float *means, const float *quats, const
     if (n > 0) {
         if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics) return GAGS_EINVAL;
         if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
-        hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, true>), dim3((unsigned)rows), dim3(256), 0, st, n, means, quats, scales,
+        hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, true, CAM>), dim3((unsigned)rows), dim3(256), 0, st, n, means, quats, scales,
                            viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats, v_scales,
                            opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, partials);
         GAGS_CHECK_LAUNCH();
@@ -621,6 +755,90 @@ extern "C" int gags_project_bwd_pose(int flags, int n, const float *means, const
     return aa ? project_bwd_pose_launch<false, true>(GAGS_POSE_ARGS) : project_bwd_pose_launch<false, false>(GAGS_POSE_ARGS);
 #undef GAGS_POSE_ARGS
 }
+
+// ---- N20: camera models -----------------------------------------------------------------------------------------------------
+
+namespace {
+
+#define GAGS_PFWD_ARGS n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, near_plane,       \
+                       far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, opacities, quats_act, scales_act,  \
+                       grec, compensations, stream
+template <int CAM>
+int project_fwd_cam(bool raw, bool aa, int n, const float *means, const float *quats, const float *scales,
+                    const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K, int width, int height,
+                    float eps2d, float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d,
+                    float *depths, float *conics, int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
+                    void *grec, float *compensations, void *stream)
+{
+    if (raw) return aa ? project_fwd_launch<true, true, CAM>(GAGS_PFWD_ARGS) : project_fwd_launch<true, false, CAM>(GAGS_PFWD_ARGS);
+    return aa ? project_fwd_launch<false, true, CAM>(GAGS_PFWD_ARGS) : project_fwd_launch<false, false, CAM>(GAGS_PFWD_ARGS);
+}
+
+#define GAGS_PBWD_ARGS n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d, \
+                       v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit
+template <int CAM>
+int project_bwd_cam(bool raw, bool aa, bool pose, int n, const float *means, const float *quats, const float *scales,
+                    const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K, int width, int height,
+                    float eps2d, const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
+                    const float *v_opacities, const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                    float *v_opacity_logit, float *v_viewmat, float *partials, void *stream)
+{
+    if (pose) {
+        hipStream_t st = (hipStream_t)stream;
+        if (raw) return aa ? project_bwd_pose_launch<true, true, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st)
+                           : project_bwd_pose_launch<true, false, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st);
+        return aa ? project_bwd_pose_launch<false, true, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st)
+                  : project_bwd_pose_launch<false, false, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st);
+    }
+    if (raw) return aa ? project_bwd_launch<true, true, CAM>(GAGS_PBWD_ARGS, stream) : project_bwd_launch<true, false, CAM>(GAGS_PBWD_ARGS, stream);
+    return aa ? project_bwd_launch<false, true, CAM>(GAGS_PBWD_ARGS, stream) : project_bwd_launch<false, false, CAM>(GAGS_PBWD_ARGS, stream);
+}
+
+}  // namespace
+
+extern "C" int gags_project_fwd_cam(int camera_model, int flags, int n, const float *means, const float *quats,
+                                    const float *scales, const float *opacity_logit, float scaling_modifier, const float *viewmat,
+                                    const float *K, int width, int height, float eps2d, float near_plane, float far_plane,
+                                    float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics,
+                                    int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act, void *grec,
+                                    float *compensations, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE || (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA)))
+        return GAGS_EINVAL;
+    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA;
+    // what a variant does not read is ignored, as in the entries without a camera model
+    if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; opacities = nullptr; quats_act = nullptr; scales_act = nullptr; grec = nullptr; }
+    if (!aa) compensations = nullptr;
+    if (camera_model == GAGS_CAM_ORTHO) return project_fwd_cam<GAGS_CAM_ORTHO>(raw, aa, GAGS_PFWD_ARGS);
+    if (camera_model == GAGS_CAM_FISHEYE) return project_fwd_cam<GAGS_CAM_FISHEYE>(raw, aa, GAGS_PFWD_ARGS);
+    return project_fwd_cam<GAGS_CAM_PINHOLE>(raw, aa, GAGS_PFWD_ARGS);
+}
+
+extern "C" int gags_project_bwd_cam(int camera_model, int flags, int n, const float *means, const float *quats,
+                                    const float *scales, const float *opacity_logit, float scaling_modifier, const float *viewmat,
+                                    const float *K, int width, int height, float eps2d, const int32_t *radii,
+                                    const float *v_means2d, const float *v_depths, const float *v_conics, const float *v_opacities,
+                                    const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                                    float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE ||
+        (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA | GAGS_PROJ_POSE)))
+        return GAGS_EINVAL;
+    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
+    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA, pose = flags & GAGS_PROJ_POSE;
+    // (a short partials buffer would be written out of bounds: refused before anything is launched)
+    if (pose && (!v_viewmat || !partials || partials_bytes < gags_project_pose_partials(n) * 12 * (int64_t)sizeof(float)))
+        return GAGS_EINVAL;
+    if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; v_opacities = nullptr; v_opacity_logit = nullptr; }
+    if (raw || !aa) v_compensations = nullptr;
+    if (camera_model == GAGS_CAM_ORTHO) return project_bwd_cam<GAGS_CAM_ORTHO>(raw, aa, pose, GAGS_PBWD_ARGS, v_viewmat, partials, stream);
+    if (camera_model == GAGS_CAM_FISHEYE) return project_bwd_cam<GAGS_CAM_FISHEYE>(raw, aa, pose, GAGS_PBWD_ARGS, v_viewmat, partials, stream);
+    return project_bwd_cam<GAGS_CAM_PINHOLE>(raw, aa, pose, GAGS_PBWD_ARGS, v_viewmat, partials, stream);
+}
+#undef GAGS_PFWD_ARGS
+#undef GAGS_PBWD_ARGS
 
 extern "C" int gags_colsum_f32(int64_t n_rows, int k, const float *table, float sign, float *out, int n_out, void *stream)
 {

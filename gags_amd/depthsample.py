@@ -34,6 +34,10 @@ def camera_matrices(cameras, device="cuda"):
     cameras = list(cameras)
     if not cameras:
         raise ValueError("camera_matrices: no cameras")
+    models = {getattr(c, "camera_model", "pinhole") for c in cameras} - {"pinhole"}
+    if models:  # (N20) the point-to-pixel mapping and the prompt grids behind this are pinhole arithmetic
+        raise NotImplementedError(f"camera_matrices: {sorted(models)} cameras; the min-depth mapping and the prompt grids are "
+                                  "implemented for pinhole cameras only")
     sizes = {(int(c.image_height), int(c.image_width)) for c in cameras}
     if len(sizes) != 1:
         raise ValueError(f"camera_matrices: the cameras differ in size {sorted(sizes)}; depth_SAM needs one (H, W)")

@@ -18,7 +18,31 @@ from .scene import GaussianModel
 # The reference re-uploads K with torch.tensor(..., device="cuda") on every call
 # (gaussian_renderer/__init__.py:31-38).  K depends only on (FoVx, FoVy, W, H); the device copy stays resident in the
 # caller's RasterContext instead of paying a pageable H2D copy per iteration.
+def camera_model_of(viewpoint_camera):
+    """The camera's model (N20): its `camera_model` attribute, "pinhole" for a camera without one (the reference's)."""
+    return getattr(viewpoint_camera, "camera_model", "pinhole")
+
+
 def _intrinsics(viewpoint_camera, device, cache):
+    """K [3,3] on `device`.  A camera that carries a `K` attribute is rendered with that K (N20: the only way to give a fisheye
+    or orthographic camera its intrinsics -- FoV -> focal is a pinhole relation and is not reinterpreted); its nine values are
+    part of the cache key, so that cameras that differ only in K do not share an entry."""
+    explicit = getattr(viewpoint_camera, "K", None)
+    if explicit is not None:
+        vals = tuple(float(v) for v in torch.as_tensor(explicit).detach().reshape(-1).tolist())
+        if len(vals) != 9:
+            raise ValueError("a camera's K must be [3,3]")
+        key = ("K", vals, str(device))
+        K = cache.get(key)
+        if K is None:
+            K = torch.tensor(vals, dtype=torch.float32, device=device).reshape(3, 3)
+            if len(cache) > 4096:
+                cache.clear()
+            cache[key] = K
+        return K
+    if camera_model_of(viewpoint_camera) != "pinhole":
+        raise ValueError(f"a {camera_model_of(viewpoint_camera)!r} camera needs an explicit K [3,3] attribute: FoVx / FoVy define "
+                         "a focal length for a pinhole camera only")
     key = (float(viewpoint_camera.FoVx), float(viewpoint_camera.FoVy), int(viewpoint_camera.image_width),
            int(viewpoint_camera.image_height), str(device))
     K = cache.get(key)
@@ -86,7 +110,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
     raster_flags / context are this package's additions to the reference's signature (kernel selection; the RasterContext
     holding this caller's hooks, capacities and caches -- None = the calling thread's default).
     rasterize_mode / absgrad: gsplat's options of the same names, handed to rasterization() (antialiased opacity
-    compensation; `viewspace_points.absgrad` after backward(), which densify.accumulate(..., absgrad=True) reads)."""
+    compensation; `viewspace_points.absgrad` after backward(), which densify.accumulate(..., absgrad=True) reads).
+    The camera model (N20) is read from the camera: `viewpoint_camera.camera_model` ("pinhole" when absent, "ortho", "fisheye"),
+    and `viewpoint_camera.K` [3,3], when present, replaces the FoV-derived intrinsics; a non-pinhole camera must carry one."""
     rctx = context if context is not None else default_context()
     means3D = pc.get_xyz
     K = _intrinsics(viewpoint_camera, means3D.device, rctx.k_cache)
@@ -115,7 +141,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
         width=int(viewpoint_camera.image_width), height=int(viewpoint_camera.image_height),
         packed=False, sh_degree=sh_degree, render_mode=render_mode, raster_flags=raster_flags,
         raw_params=stored is not None, scaling_modifier=float(scaling_modifier), context=rctx,
-        rasterize_mode=rasterize_mode, absgrad=absgrad)
+        rasterize_mode=rasterize_mode, absgrad=absgrad, camera_model=camera_model_of(viewpoint_camera))
 
     # squeeze (not [0]): its backward is a view, [0]'s is a zero-fill + copy of the whole map
     rendered_image = render_colors.squeeze(0).permute(2, 0, 1)  # [1,H,W,D'] -> [D',H,W]

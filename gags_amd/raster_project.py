@@ -11,29 +11,52 @@ def _c(t):
 
 
 def _project_bwd_pose(lib, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
-                      v_depths, v_conics, v_opac, v_comp, want):
+                      v_depths, v_conics, v_opac, v_comp, want, cam=0):
     """gags_project_bwd_pose (N17): the projection backward when the pose needs a gradient.  want = which of (means, quats,
     scales, opacity logit) need theirs: the others are neither allocated nor stored.  Returns (v_means, v_quats, v_scales,
-    v_logit, v_viewmat [4,4]), None where not wanted."""
+    v_logit, v_viewmat [4,4]), None where not wanted.  cam != 0 (N20): the same through gags_project_bwd_cam."""
     n = means.shape[0]
     dev = means.device
     v_means, v_quats, v_scales, v_logit = (torch.empty(n, *shape, device=dev) if w else None
                                            for w, shape in zip(want, ((3,), (4,), (3,), ())))
     v_viewmat = torch.empty(4, 4, device=dev)
     partials = torch.empty(lib.gags_project_pose_partials(n), 12, device=dev)
-    check(lib.gags_project_bwd_pose(flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
-                                    width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac),
-                                    ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_logit), ptr(v_viewmat),
-                                    ptr(partials), partials.numel() * 4, _lib.stream()), "gags_project_bwd_pose")
+    args = (n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K), width, height, eps2d, ptr(radii),
+            ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac), ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales),
+            ptr(v_logit), ptr(v_viewmat), ptr(partials), partials.numel() * 4, _lib.stream())
+    if cam:  # (GAGS_POSE_RAW / _AA are GAGS_PROJ_RAW / _AA)
+        check(lib.gags_project_bwd_cam(cam, flags | _lib.GAGS_PROJ_POSE, *args), "gags_project_bwd_cam")
+    else:
+        check(lib.gags_project_bwd_pose(flags, *args), "gags_project_bwd_pose")
     return v_means, v_quats, v_scales, v_logit, v_viewmat
+
+
+def _project_fwd_cam(lib, cam, flags, n, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, near, far,
+                     radius_clip, radii, means2d, depths, conics, tiles, opac, grec, comp):
+    """gags_project_fwd_cam (N20): the projection forward of a non-pinhole camera, every variant through one entry."""
+    check(lib.gags_project_fwd_cam(cam, flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
+                                   width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths),
+                                   ptr(conics), ptr(tiles), ptr(opac), None, None, ptr(grec), ptr(comp), _lib.stream()),
+          "gags_project_fwd_cam")
+
+
+def _project_bwd_cam(lib, cam, flags, n, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                     v_depths, v_conics, v_opac, v_comp, v_means, v_quats, v_scales, v_logit):
+    """gags_project_bwd_cam (N20) without the pose."""
+    check(lib.gags_project_bwd_cam(cam, flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
+                                   width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac),
+                                   ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_logit), None, None, 0,
+                                   _lib.stream()), "gags_project_bwd_cam")
 
 
 class _Project(torch.autograd.Function):
     """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
-    cotangent in the backward (gags_project_fwd_aa / gags_project_bwd_aa); the caller multiplies them into the opacities."""
+    cotangent in the backward (gags_project_fwd_aa / gags_project_bwd_aa); the caller multiplies them into the opacities.
+    cam (N20): _lib.GAGS_CAM_*; the pinhole (0) goes through the entries it always went through, any other model through
+    gags_project_fwd_cam / gags_project_bwd_cam."""
 
     @staticmethod
-    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False):
+    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False, cam=0):
         lib = _lib.load()
         means, quats, scales, viewmat, K = _c(means), _c(quats), _c(scales), _c(viewmat), _c(K)
         n = means.shape[0]
@@ -46,11 +69,15 @@ class _Project(torch.autograd.Function):
         comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
         entry, name = (lib.gags_project_fwd_aa, "gags_project_fwd_aa") if aa else (lib.gags_project_fwd, "gags_project_fwd")
         with profiler.stage("project_fwd"):
-            check(entry(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height, eps2d, near, far,
-                        radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(tiles),
-                        *((ptr(comp),) if aa else ()), _lib.stream()), name)
+            if cam:
+                _project_fwd_cam(lib, cam, _lib.GAGS_PROJ_AA if aa else 0, n, means, quats, scales, None, 1.0, viewmat, K, width,
+                                 height, eps2d, near, far, radius_clip, radii, means2d, depths, conics, tiles, None, None, comp)
+            else:
+                check(entry(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height, eps2d, near, far,
+                            radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(tiles),
+                            *((ptr(comp),) if aa else ()), _lib.stream()), name)
         ctx.save_for_backward(means, quats, scales, viewmat, K, radii, conics)
-        ctx.cfg = (width, height, eps2d, aa)
+        ctx.cfg = (width, height, eps2d, aa, cam)
         ctx.mark_non_differentiable(radii, tiles)
         if aa:
             return radii, means2d, depths, conics, tiles, comp
@@ -60,7 +87,7 @@ class _Project(torch.autograd.Function):
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_comp=None):
         lib = _lib.load()
         means, quats, scales, viewmat, K, radii, conics = ctx.saved_tensors
-        width, height, eps2d, aa = ctx.cfg
+        width, height, eps2d, aa, cam = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
@@ -70,12 +97,16 @@ class _Project(torch.autograd.Function):
             v_comp = None if (not aa or v_comp is None) else _c(v_comp)
             v_means, v_quats, v_scales, _, v_viewmat = _project_bwd_pose(
                 lib, _lib.GAGS_POSE_AA if aa else 0, means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii,
-                v_means2d, v_depths, v_conics, None, v_comp, tuple(ctx.needs_input_grad[:3]) + (False,))
-            return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None
+                v_means2d, v_depths, v_conics, None, v_comp, tuple(ctx.needs_input_grad[:3]) + (False,), cam)
+            return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None, None
         v_means = torch.empty(n, 3, device=dev)
         v_quats = torch.empty(n, 4, device=dev)
         v_scales = torch.empty(n, 3, device=dev)
-        if aa:
+        if cam:
+            v_comp = None if (not aa or v_comp is None) else _c(v_comp)
+            _project_bwd_cam(lib, cam, _lib.GAGS_PROJ_AA if aa else 0, n, means, quats, scales, None, 1.0, viewmat, K, width,
+                             height, eps2d, radii, v_means2d, v_depths, v_conics, None, v_comp, v_means, v_quats, v_scales, None)
+        elif aa:
             v_comp = None if v_comp is None else _c(v_comp)
             check(lib.gags_project_bwd_aa(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
                                           eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_comp),
@@ -84,7 +115,7 @@ class _Project(torch.autograd.Function):
             check(lib.gags_project_bwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
                                        eps2d, ptr(radii), ptr(conics), ptr(v_means2d), ptr(v_depths), ptr(v_conics),
                                        ptr(v_means), ptr(v_quats), ptr(v_scales), _lib.stream()), "gags_project_bwd")
-        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None, None
+        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None, None, None
 
 
 class _ProjectRaw(torch.autograd.Function):
@@ -93,11 +124,11 @@ class _ProjectRaw(torch.autograd.Function):
     projection kernel, bit for bit as torch evaluates them; the backward returns gradients of the stored parameters.
     aa (rasterize_mode "antialiased"): the kernel folds the compensation into the activated opacity and the record
     (gags_project_fwd_raw_aa), the compensations [N] are one more -- non-differentiable -- output, and the backward takes the
-    compensation's cotangent from the opacity's (gags_project_bwd_raw_aa)."""
+    compensation's cotangent from the opacity's (gags_project_bwd_raw_aa).  cam (N20): as in _Project."""
 
     @staticmethod
     def forward(ctx, means, rotation, scaling_log, opacity_logit, viewmat, K, width, height, eps2d, near, far, radius_clip,
-                scaling_modifier, want_records, aa=False):
+                scaling_modifier, want_records, aa=False, cam=0):
         lib = _lib.load()
         means, rotation, scaling_log, viewmat, K = _c(means), _c(rotation), _c(scaling_log), _c(viewmat), _c(K)
         logit = _c(opacity_logit.reshape(-1))
@@ -115,12 +146,17 @@ class _ProjectRaw(torch.autograd.Function):
         entry, name = ((lib.gags_project_fwd_raw_aa, "gags_project_fwd_raw_aa") if aa
                        else (lib.gags_project_fwd_raw, "gags_project_fwd_raw"))
         with profiler.stage("project_fwd"):
-            check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier, ptr(viewmat), ptr(K),
-                        width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
-                        ptr(tiles), ptr(opac), None, None, ptr(grec) if want_records else None,
-                        *((ptr(comp),) if aa else ()), _lib.stream()), name)
+            if cam:
+                _project_fwd_cam(lib, cam, _lib.GAGS_PROJ_RAW | (_lib.GAGS_PROJ_AA if aa else 0), n, means, rotation, scaling_log,
+                                 logit, scaling_modifier, viewmat, K, width, height, eps2d, near, far, radius_clip, radii, means2d,
+                                 depths, conics, tiles, opac, grec if want_records else None, comp)
+            else:
+                check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier, ptr(viewmat), ptr(K),
+                            width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
+                            ptr(tiles), ptr(opac), None, None, ptr(grec) if want_records else None,
+                            *((ptr(comp),) if aa else ()), _lib.stream()), name)
         ctx.save_for_backward(means, rotation, scaling_log, logit, viewmat, K, radii)
-        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa)
+        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa, cam)
         if aa:
             ctx.mark_non_differentiable(radii, tiles, grec, comp)
             return radii, means2d, depths, conics, tiles, opac, grec, comp
@@ -131,7 +167,7 @@ class _ProjectRaw(torch.autograd.Function):
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_opac, _v_grec, _v_comp=None):
         lib = _lib.load()
         means, rotation, scaling_log, logit, viewmat, K, radii = ctx.saved_tensors
-        width, height, eps2d, modifier, oshape, aa = ctx.cfg
+        width, height, eps2d, modifier, oshape, aa, cam = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
@@ -142,21 +178,26 @@ class _ProjectRaw(torch.autograd.Function):
             flags = _lib.GAGS_POSE_RAW | (_lib.GAGS_POSE_AA if aa else 0)
             v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd_pose(
                 lib, flags, means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
-                v_depths, v_conics, v_opac, None, tuple(ctx.needs_input_grad[:4]))
+                v_depths, v_conics, v_opac, None, tuple(ctx.needs_input_grad[:4]), cam)
             return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, None, None, None,
-                    None, None, None, None, None, None, None)
+                    None, None, None, None, None, None, None, None)
         v_means = torch.empty(n, 3, device=dev)
         v_rot = torch.empty(n, 4, device=dev)
         v_scal = torch.empty(n, 3, device=dev)
         v_logit = torch.empty(n, device=dev) if ctx.needs_input_grad[3] else None
         entry, name = ((lib.gags_project_bwd_raw_aa, "gags_project_bwd_raw_aa") if aa
                        else (lib.gags_project_bwd_raw, "gags_project_bwd_raw"))
-        check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), modifier, ptr(viewmat),
-                    ptr(K), width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths),
-                    ptr(v_conics), ptr(v_opac), ptr(v_means), ptr(v_rot), ptr(v_scal), ptr(v_logit),
-                    _lib.stream()), name)
+        if cam:
+            _project_bwd_cam(lib, cam, _lib.GAGS_PROJ_RAW | (_lib.GAGS_PROJ_AA if aa else 0), n, means, rotation, scaling_log,
+                             logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_opac, None,
+                             v_means, v_rot, v_scal, v_logit)
+        else:
+            check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), modifier, ptr(viewmat),
+                        ptr(K), width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths),
+                        ptr(v_conics), ptr(v_opac), ptr(v_means), ptr(v_rot), ptr(v_scal), ptr(v_logit),
+                        _lib.stream()), name)
         return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), None, None, None, None, None,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 class _SH(torch.autograd.Function):

@@ -103,6 +103,10 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     with sh_degree row 3 gets what that puts there).  Scene tensors that need no gradient
     get none computed (pose refinement against a frozen scene).  Ks gets NO gradient, as in gsplat.  With viewmats not
     requiring grad nothing changes: same launches, same bits.
+    camera_model (N20): "pinhole", "ortho" (means2d = (fx x + cx, fy y + cy); fx, fy pixels per world unit)
+    or "fisheye" (equidistant, no distortion coefficients; z < near_plane is still culled, so the field of view stays below
+    180 degrees).  Only the projection kernels differ (gags_project_fwd_cam / gags_project_bwd_cam); "pinhole" launches what it
+    always launched.  info["camera_model"] repeats it.
     absgrad=True: after backward(), info["means2d"].absgrad is the [1,N,2] sum over pixels of the absolute per-pixel
     screen-space gradients (AbsGS), overwritten by each backward; set only where a geometry gradient is produced."""
     rctx = context if context is not None else default_context()
@@ -113,9 +117,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     if not isinstance(absgrad, bool):
         raise ValueError("absgrad must be True or False")
     aa = rasterize_mode == "antialiased"
-    if camera_model != "pinhole" or covars is not None or distributed:
+    if not isinstance(camera_model, str) or camera_model not in _lib.CAMERA_MODELS:  # (plain values: before any tensor is looked at)
+        raise ValueError(f"unknown camera_model {camera_model!r} (\"pinhole\", \"ortho\" or \"fisheye\")")
+    cam = _lib.CAMERA_MODELS[camera_model]
+    if covars is not None or distributed:
         raise NotImplementedError("only the options the reference uses are implemented "
-                                  "(pinhole camera, quats+scales, one process per view)")
+                                  "(quats+scales, one process per view)")
     if render_mode not in ("RGB", "D", "ED", "RGB+D", "RGB+ED"):
         raise ValueError(f"unknown render_mode {render_mode}")
     if viewmats.dim() != 3 or viewmats.shape[0] != 1 or Ks.shape[0] != 1:
@@ -140,7 +147,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     if raw_params:
         radii, means2d, depths, conics, tiles, opacities, records, *comp = _ProjectRaw.apply(
             means, quats, scales, opacities, viewmat, K, width, height, float(eps2d), float(near_plane), float(far_plane),
-            float(radius_clip), float(scaling_modifier), route.records and n > 0, aa)
+            float(radius_clip), float(scaling_modifier), route.records and n > 0, aa, cam)
         if records.numel() == 0:
             records = None
         if aa:  # (already folded into `opacities` and the records by the kernel)
@@ -148,7 +155,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     else:
         radii, means2d, depths, conics, tiles, *comp = _Project.apply(means, quats, scales, viewmat, K, width, height,
                                                                       float(eps2d), float(near_plane), float(far_plane),
-                                                                      float(radius_clip), aa)
+                                                                      float(radius_clip), aa, cam)
         if aa:  # a torch multiply: autograd carries both factors
             compensations = comp[0]
             opacities = opacities * compensations
@@ -256,7 +263,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         "tile_width": tile_w, "tile_height": tile_h,
         "tiles_per_gauss": tiles[None], "isect_ids": isect_ids, "flatten_ids": flatten_ids,
         "isect_offsets": p.binning.isect_offsets[None], "last_ids": p.last_ids, "width": width, "height": height,
-        "tile_size": T.TILE, "n_cameras": 1, "n_isects": n_isects,
+        "tile_size": T.TILE, "n_cameras": 1, "n_isects": n_isects, "camera_model": camera_model,
         "n_isects_trimmed": p.n_trimmed,  # (not gsplat's: list entries the raster passes worked on when the lists were trimmed, else None)
     }
     return out[None], alphas[None, ..., None], info

@@ -46,10 +46,19 @@ def fov2focal(fov, pixels):
 
 
 class Camera:
-    """Minimal stand-in for scene.cameras.Camera / MiniCam."""
+    """Minimal stand-in for scene.cameras.Camera / MiniCam.  camera_model / K (N20): "pinhole", "ortho" or "fisheye", and
+    explicit intrinsics [3,3] that render() then uses instead of the FoV-derived ones (required for a non-pinhole camera)."""
 
-    def __init__(self, R, T, FoVx, FoVy, image_width, image_height, device="cuda", uid=0):
+    def __init__(self, R, T, FoVx, FoVy, image_width, image_height, device="cuda", uid=0, camera_model="pinhole", K=None):
         self.uid = uid
+        if camera_model not in ("pinhole", "ortho", "fisheye"):
+            raise ValueError(f"unknown camera_model {camera_model!r} (\"pinhole\", \"ortho\" or \"fisheye\")")
+        self.camera_model = camera_model
+        self.K = None
+        if K is not None:
+            self.K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float32)
+            if self.K.shape != (3, 3):
+                raise ValueError("K must be [3,3]")
         self.R = np.asarray(R, dtype=np.float64)
         self.T = np.asarray(T, dtype=np.float64)
         self.FoVx = float(FoVx)

@@ -451,6 +451,46 @@ int gags_project_bwd_pose(int flags, int n, const float *means, const float *qua
                           const float *v_depths, const float *v_conics, const float *v_opacities,
                           const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
                           float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
+/* N20: camera models.  The model decides where a centre lands and the 2 x 3 Jacobian J of cov2d = J Sc J^T, with
+ * p = (x, y, z) = Rcw mean + t and Sc = Rcw Sigma Rcw^T as above; near / far culling on z, depths = z, eps2d, the det <= 0 cull,
+ * conic, radius, radius_clip / off-screen cull, tile count, the antialiased compensation and the pose terms are those of the
+ * entries above for every model.
+ *   GAGS_CAM_PINHOLE  means2d = (fx x / z + cx, fy y / z + cy), J with the tangent clamp: the entries above, bit for bit.
+ *   GAGS_CAM_ORTHO    means2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]; fx, fy are pixels per world unit; no clamp.
+ *   GAGS_CAM_FISHEYE  equidistant, no distortion coefficients, no clamp.  With eps = 1e-7:
+ *                       rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
+ *                       means2d = (fx x theta / rho + cx, fy y theta / rho + cy),
+ *                       x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2, l2 = s + z^2, b = atan2(rho, z) / rho / s, a = z / (l2 s),
+ *                       J = [[fx (x2 a + y2 b), fx xy (a - b), -fx x / l2], [fy xy (a - b), fy (y2 a + x2 b), -fy y / l2]].
+ *                     J IS this closed form, guards included (on the axis: [[fx / z, 0, 0], [0, fy / z, 0]]), not the derivative
+ *                     of the map; the backward is the exact derivative of this forward, with d sqrt(x^2 + y^2) = 0 at x = y = 0,
+ *                     so every output is finite there.  z < near_plane is culled: the field of view stays below 180 degrees.
+ * flags: GAGS_PROJ_RAW = the stored parameters (gags_project_fwd_raw / _bwd_raw), GAGS_PROJ_AA = rasterize_mode "antialiased",
+ * GAGS_PROJ_POSE (backward only) = v_viewmat on the way (gags_project_bwd_pose).  The arguments are the union of those entries';
+ * what a variant does not read is ignored (forward: opacity_logit, scaling_modifier, opacities, quats_act, scales_act, grec
+ * without RAW, compensations without AA; backward: as gags_project_bwd_pose, and v_viewmat / partials without POSE).  Without
+ * POSE v_means, v_quats, v_scales are required, with POSE each may be NULL.  GAGS_EINVAL before any launch: an unknown
+ * camera_model, unknown flag bits, n < 0, a missing pointer, with POSE a NULL v_viewmat / partials or partials_bytes <
+ * gags_project_pose_partials(n) * 48.  n = 0 is GAGS_OK (with POSE v_viewmat is written, zeros). */
+#define GAGS_CAM_PINHOLE 0
+#define GAGS_CAM_ORTHO 1
+#define GAGS_CAM_FISHEYE 2
+#define GAGS_PROJ_RAW 1
+#define GAGS_PROJ_AA 2
+#define GAGS_PROJ_POSE 4
+int gags_project_fwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
+                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                         int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
+                         int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
+                         float *opacities, float *quats_act, float *scales_act, void *grec, float *compensations,
+                         void *stream);
+int gags_project_bwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
+                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                         int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                         const float *v_depths, const float *v_conics, const float *v_opacities,
+                         const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                         float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
+
 /* Column sums of an fp32 table [n_rows, k], 1 <= k <= 12: out[c] = sign * sum over rows of table[r, c] for c < k, and
  * out[k .. n_out) = 0 (k <= n_out <= 256).  One workgroup, sums in double, fixed order: two calls give the same bits.
  * n_rows = 0 writes zeros.  (Second stage of gags_project_bwd_pose; v_campos = -sum of gags_sh_bwd_dirs' rows.) */
