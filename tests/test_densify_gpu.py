@@ -425,6 +425,12 @@ W, H, N0 = 64, 48, 500
 STORED = tuple(ATTR.values())
 
 
+def atomic_reorder_rel(terms):
+    """Bound, relative to a tensor's largest magnitude, between two runs of a sum of `terms` fp32 terms added with atomics in
+    whatever order they arrive: twice the worst-case reordering error, terms * 2^-23 (also used by tests/test_streams_gpu.py)."""
+    return terms * 2.0 ** -23
+
+
 def _scene(seed=3):
     from gags_amd import synthetic as syn
     pc = syn.make_model(N0, 16, W, H, seed=seed, device=DEV, scale0=syn.SCALE0 * 24)
@@ -487,7 +493,8 @@ def test_steps_across_a_densify_equal_the_stateless_step():
     opt = pc.training_setup_rgb(ARGS)
     pc.cache_activations(True)
     ctx = RasterContext()
-    rel = 3072 * 2.0 ** -23
+    rel = atomic_reorder_rel(W * H)
+    assert rel == 3072 * 2.0 ** -23
     sizes = []
     for step in range(6):
         if step == 3:
