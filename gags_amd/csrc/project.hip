@@ -6,6 +6,7 @@
 #include "common.h"
 #include "raster_mfma_common.h"
 #include "reduce.h"
+#include <type_traits>
 
 namespace {
 
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
 
 namespace {
 
-template <bool RAW, bool AA, int CAM = GAGS_CAM_PINHOLE>
+template <bool RAW, bool AA, int CAM>
 int project_fwd_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
                        float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
                        float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d, float *depths,
@@ -349,15 +350,16 @@ int project_fwd_launch(int n, const float *means, const float *quats, const floa
 
 }  // namespace
 
+// The four named forwards: gags_project_fwd_cam for the pinhole, what a variant lacks filled in (include/gags_raster.h).
 extern "C" int gags_project_fwd(int n, const float *means, const float *quats, const float *scales,
                                 const float *viewmat, const float *K, int width, int height,
                                 float eps2d, float near_plane, float far_plane, float radius_clip,
                                 int32_t *radii, float *means2d, float *depths, float *conics,
                                 int32_t *tiles_per_gauss, void *stream)
 {
-    return project_fwd_launch<false, false>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, near_plane,
-                                            far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr,
-                                            nullptr, nullptr, nullptr, nullptr, stream);
+    return gags_project_fwd_cam(GAGS_CAM_PINHOLE, 0, n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d,
+                                near_plane, far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr,
+                                nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int gags_project_fwd_aa(int n, const float *means, const float *quats, const float *scales,
@@ -366,9 +368,9 @@ extern "C" int gags_project_fwd_aa(int n, const float *means, const float *quats
                                    int32_t *radii, float *means2d, float *depths, float *conics,
                                    int32_t *tiles_per_gauss, float *compensations, void *stream)
 {
-    return project_fwd_launch<false, true>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, near_plane,
-                                           far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, nullptr,
-                                           nullptr, nullptr, nullptr, compensations, stream);
+    return gags_project_fwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_AA, n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height,
+                                eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss,
+                                nullptr, nullptr, nullptr, nullptr, compensations, stream);
 }
 
 extern "C" int gags_project_fwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
@@ -378,9 +380,9 @@ extern "C" int gags_project_fwd_raw(int n, const float *means, const float *rota
                                     int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
                                     void *grec, void *stream)
 {
-    return project_fwd_launch<true, false>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
-                                           height, eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths, conics,
-                                           tiles_per_gauss, opacities, quats_act, scales_act, grec, nullptr, stream);
+    return gags_project_fwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW, n, means, rotation, scaling_log, opacity_logit, scaling_modifier,
+                                viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths,
+                                conics, tiles_per_gauss, opacities, quats_act, scales_act, grec, nullptr, stream);
 }
 
 extern "C" int gags_project_fwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
@@ -390,9 +392,10 @@ extern "C" int gags_project_fwd_raw_aa(int n, const float *means, const float *r
                                        int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
                                        void *grec, float *compensations, void *stream)
 {
-    return project_fwd_launch<true, true>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
-                                          height, eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths, conics,
-                                          tiles_per_gauss, opacities, quats_act, scales_act, grec, compensations, stream);
+    return gags_project_fwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW | GAGS_PROJ_AA, n, means, rotation, scaling_log, opacity_logit,
+                                scaling_modifier, viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip, radii,
+                                means2d, depths, conics, tiles_per_gauss, opacities, quats_act, scales_act, grec, compensations,
+                                stream);
 }
 
 namespace {
@@ -633,7 +636,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(int64_t n_rows, int k, cons
 
 namespace {
 
-template <bool RAW, bool AA, int CAM = GAGS_CAM_PINHOLE>
+template <bool RAW, bool AA, int CAM>
 int project_bwd_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
                        float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
                        const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
@@ -662,7 +665,7 @@ int colsum_launch(int64_t n_rows, int k, const float *table, float sign, float *
     return GAGS_OK;
 }
 
-template <bool RAW, bool AA, int CAM = GAGS_CAM_PINHOLE>
+template <bool RAW, bool AA, int CAM>
 int project_bwd_pose_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
                             float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
                             const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
@@ -684,6 +687,7 @@ int project_bwd_pose_launch(int n, const float *means, const float *quats, const
 
 }  // namespace
 
+// The four named backwards and gags_project_bwd_pose: gags_project_bwd_cam for the pinhole, likewise.
 extern "C" int gags_project_bwd(int n, const float *means, const float *quats, const float *scales,
                                 const float *viewmat, const float *K, int width, int height, float eps2d,
                                 const int32_t *radii, const float *conics, const float *v_means2d,
@@ -691,9 +695,9 @@ extern "C" int gags_project_bwd(int n, const float *means, const float *quats, c
                                 float *v_scales, void *stream)
 {
     (void)conics;  // recomputed in-kernel with the forward's operation order
-    return project_bwd_launch<false, false>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, radii,
-                                            v_means2d, v_depths, v_conics, nullptr, nullptr, v_means, v_quats, v_scales, nullptr,
-                                            stream);
+    return gags_project_bwd_cam(GAGS_CAM_PINHOLE, 0, n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, radii,
+                                v_means2d, v_depths, v_conics, nullptr, nullptr, v_means, v_quats, v_scales, nullptr, nullptr,
+                                nullptr, 0, stream);
 }
 
 extern "C" int gags_project_bwd_aa(int n, const float *means, const float *quats, const float *scales,
@@ -702,9 +706,9 @@ extern "C" int gags_project_bwd_aa(int n, const float *means, const float *quats
                                    const float *v_conics, const float *v_compensations, float *v_means, float *v_quats,
                                    float *v_scales, void *stream)
 {
-    return project_bwd_launch<false, true>(n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height, eps2d, radii,
-                                           v_means2d, v_depths, v_conics, nullptr, v_compensations, v_means, v_quats, v_scales,
-                                           nullptr, stream);
+    return gags_project_bwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_AA, n, means, quats, scales, nullptr, 1.0f, viewmat, K, width, height,
+                                eps2d, radii, v_means2d, v_depths, v_conics, nullptr, v_compensations, v_means, v_quats, v_scales,
+                                nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int gags_project_bwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
@@ -713,9 +717,9 @@ extern "C" int gags_project_bwd_raw(int n, const float *means, const float *rota
                                     const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
                                     float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream)
 {
-    return project_bwd_launch<true, false>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
-                                           height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities, nullptr, v_means,
-                                           v_rotation, v_scaling_log, v_opacity_logit, stream);
+    return gags_project_bwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW, n, means, rotation, scaling_log, opacity_logit, scaling_modifier,
+                                viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities, nullptr,
+                                v_means, v_rotation, v_scaling_log, v_opacity_logit, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int gags_project_bwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
@@ -724,9 +728,10 @@ extern "C" int gags_project_bwd_raw_aa(int n, const float *means, const float *r
                                        const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
                                        float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream)
 {
-    return project_bwd_launch<true, true>(n, means, rotation, scaling_log, opacity_logit, scaling_modifier, viewmat, K, width,
-                                          height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities, nullptr, v_means,
-                                          v_rotation, v_scaling_log, v_opacity_logit, stream);
+    return gags_project_bwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW | GAGS_PROJ_AA, n, means, rotation, scaling_log, opacity_logit,
+                                scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics,
+                                v_opacities, nullptr, v_means, v_rotation, v_scaling_log, v_opacity_logit, nullptr, nullptr, 0,
+                                stream);
 }
 
 // ---- N17: camera pose gradients ---------------------------------------------------------------------------------------------
@@ -741,57 +746,36 @@ extern "C" int gags_project_bwd_pose(int flags, int n, const float *means, const
                                      float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes,
                                      void *stream)
 {
-    GAGS_CLEAR_ERR();
-    if (n < 0 || width <= 0 || height <= 0 || (flags & ~(GAGS_POSE_RAW | GAGS_POSE_AA))) return GAGS_EINVAL;
-    // (a short partials buffer would be written out of bounds: refused before anything is launched)
-    if (!v_viewmat || !partials || partials_bytes < gags_project_pose_partials(n) * 12 * (int64_t)sizeof(float)) return GAGS_EINVAL;
-    const bool raw = flags & GAGS_POSE_RAW, aa = flags & GAGS_POSE_AA;
-    if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; v_opacities = nullptr; v_opacity_logit = nullptr; }
-    if (raw || !aa) v_compensations = nullptr;
-#define GAGS_POSE_ARGS n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d, \
-                       v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit, v_viewmat,    \
-                       partials, (hipStream_t)stream
-    if (raw) return aa ? project_bwd_pose_launch<true, true>(GAGS_POSE_ARGS) : project_bwd_pose_launch<true, false>(GAGS_POSE_ARGS);
-    return aa ? project_bwd_pose_launch<false, true>(GAGS_POSE_ARGS) : project_bwd_pose_launch<false, false>(GAGS_POSE_ARGS);
-#undef GAGS_POSE_ARGS
+    static_assert(GAGS_POSE_RAW == GAGS_PROJ_RAW && GAGS_POSE_AA == GAGS_PROJ_AA, "the pose entry hands its flags on as they are");
+    if (flags & ~(GAGS_POSE_RAW | GAGS_POSE_AA)) return GAGS_EINVAL;  // (GAGS_PROJ_POSE is not a flag of this entry)
+    return gags_project_bwd_cam(GAGS_CAM_PINHOLE, flags | GAGS_PROJ_POSE, n, means, quats, scales, opacity_logit, scaling_modifier,
+                                viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_opacities,
+                                v_compensations, v_means, v_quats, v_scales, v_opacity_logit, v_viewmat, partials, partials_bytes,
+                                stream);
 }
 
 // ---- N20: camera models -----------------------------------------------------------------------------------------------------
 
 namespace {
 
-#define GAGS_PFWD_ARGS n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, near_plane,       \
-                       far_plane, radius_clip, radii, means2d, depths, conics, tiles_per_gauss, opacities, quats_act, scales_act,  \
-                       grec, compensations, stream
-template <int CAM>
-int project_fwd_cam(bool raw, bool aa, int n, const float *means, const float *quats, const float *scales,
-                    const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K, int width, int height,
-                    float eps2d, float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d,
-                    float *depths, float *conics, int32_t *tiles_per_gauss, float *opacities, float *quats_act, float *scales_act,
-                    void *grec, float *compensations, void *stream)
+// Run-time (camera_model, flag, flag ...) to compile-time constants, once for both directions: f is called with a
+// std::integral_constant for the camera model and a std::bool_constant per flag, and instantiates what it names.
+template <class F>
+int with_flags(F &&f) { return f(); }
+template <class F, class... Bs>
+int with_flags(F &&f, bool b, Bs... bs)
 {
-    if (raw) return aa ? project_fwd_launch<true, true, CAM>(GAGS_PFWD_ARGS) : project_fwd_launch<true, false, CAM>(GAGS_PFWD_ARGS);
-    return aa ? project_fwd_launch<false, true, CAM>(GAGS_PFWD_ARGS) : project_fwd_launch<false, false, CAM>(GAGS_PFWD_ARGS);
+    return b ? with_flags([&](auto... cs) { return f(std::true_type{}, cs...); }, bs...)
+             : with_flags([&](auto... cs) { return f(std::false_type{}, cs...); }, bs...);
 }
-
-#define GAGS_PBWD_ARGS n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d, \
-                       v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit
-template <int CAM>
-int project_bwd_cam(bool raw, bool aa, bool pose, int n, const float *means, const float *quats, const float *scales,
-                    const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K, int width, int height,
-                    float eps2d, const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
-                    const float *v_opacities, const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
-                    float *v_opacity_logit, float *v_viewmat, float *partials, void *stream)
+template <class F, class... Bs>
+int with_camera(int camera_model, F &&f, Bs... bs)  // (camera_model is one of the three: the entries have checked)
 {
-    if (pose) {
-        hipStream_t st = (hipStream_t)stream;
-        if (raw) return aa ? project_bwd_pose_launch<true, true, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st)
-                           : project_bwd_pose_launch<true, false, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st);
-        return aa ? project_bwd_pose_launch<false, true, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st)
-                  : project_bwd_pose_launch<false, false, CAM>(GAGS_PBWD_ARGS, v_viewmat, partials, st);
-    }
-    if (raw) return aa ? project_bwd_launch<true, true, CAM>(GAGS_PBWD_ARGS, stream) : project_bwd_launch<true, false, CAM>(GAGS_PBWD_ARGS, stream);
-    return aa ? project_bwd_launch<false, true, CAM>(GAGS_PBWD_ARGS, stream) : project_bwd_launch<false, false, CAM>(GAGS_PBWD_ARGS, stream);
+    if (camera_model == GAGS_CAM_ORTHO)
+        return with_flags([&](auto... cs) { return f(std::integral_constant<int, GAGS_CAM_ORTHO>{}, cs...); }, bs...);
+    if (camera_model == GAGS_CAM_FISHEYE)
+        return with_flags([&](auto... cs) { return f(std::integral_constant<int, GAGS_CAM_FISHEYE>{}, cs...); }, bs...);
+    return with_flags([&](auto... cs) { return f(std::integral_constant<int, GAGS_CAM_PINHOLE>{}, cs...); }, bs...);
 }
 
 }  // namespace
@@ -807,12 +791,15 @@ extern "C" int gags_project_fwd_cam(int camera_model, int flags, int n, const fl
     if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE || (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA)))
         return GAGS_EINVAL;
     const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA;
-    // what a variant does not read is ignored, as in the entries without a camera model
+    // what a variant does not read is ignored
     if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; opacities = nullptr; quats_act = nullptr; scales_act = nullptr; grec = nullptr; }
     if (!aa) compensations = nullptr;
-    if (camera_model == GAGS_CAM_ORTHO) return project_fwd_cam<GAGS_CAM_ORTHO>(raw, aa, GAGS_PFWD_ARGS);
-    if (camera_model == GAGS_CAM_FISHEYE) return project_fwd_cam<GAGS_CAM_FISHEYE>(raw, aa, GAGS_PFWD_ARGS);
-    return project_fwd_cam<GAGS_CAM_PINHOLE>(raw, aa, GAGS_PFWD_ARGS);
+    return with_camera(camera_model, [&](auto CAM, auto RAW, auto AA) {
+        return project_fwd_launch<RAW.value, AA.value, CAM.value>(
+            n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, near_plane, far_plane,
+            radius_clip, radii, means2d, depths, conics, tiles_per_gauss, opacities, quats_act, scales_act, grec, compensations,
+            stream);
+    }, raw, aa);
 }
 
 extern "C" int gags_project_bwd_cam(int camera_model, int flags, int n, const float *means, const float *quats,
@@ -833,12 +820,18 @@ extern "C" int gags_project_bwd_cam(int camera_model, int flags, int n, const fl
         return GAGS_EINVAL;
     if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; v_opacities = nullptr; v_opacity_logit = nullptr; }
     if (raw || !aa) v_compensations = nullptr;
-    if (camera_model == GAGS_CAM_ORTHO) return project_bwd_cam<GAGS_CAM_ORTHO>(raw, aa, pose, GAGS_PBWD_ARGS, v_viewmat, partials, stream);
-    if (camera_model == GAGS_CAM_FISHEYE) return project_bwd_cam<GAGS_CAM_FISHEYE>(raw, aa, pose, GAGS_PBWD_ARGS, v_viewmat, partials, stream);
-    return project_bwd_cam<GAGS_CAM_PINHOLE>(raw, aa, pose, GAGS_PBWD_ARGS, v_viewmat, partials, stream);
+    return with_camera(camera_model, [&](auto CAM, auto RAW, auto AA, auto POSE) {
+        if constexpr (POSE.value)
+            return project_bwd_pose_launch<RAW.value, AA.value, CAM.value>(
+                n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit, v_viewmat, partials,
+                (hipStream_t)stream);
+        else
+            return project_bwd_launch<RAW.value, AA.value, CAM.value>(
+                n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit, stream);
+    }, raw, aa, pose);
 }
-#undef GAGS_PFWD_ARGS
-#undef GAGS_PBWD_ARGS
 
 extern "C" int gags_colsum_f32(int64_t n_rows, int k, const float *table, float sign, float *out, int n_out, void *stream)
 {

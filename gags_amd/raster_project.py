@@ -10,73 +10,66 @@ def _c(t):
     return t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
 
 
-def _project_bwd_pose(lib, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
-                      v_depths, v_conics, v_opac, v_comp, want, cam=0):
-    """gags_project_bwd_pose (N17): the projection backward when the pose needs a gradient.  want = which of (means, quats,
-    scales, opacity logit) need theirs: the others are neither allocated nor stored.  Returns (v_means, v_quats, v_scales,
-    v_logit, v_viewmat [4,4]), None where not wanted.  cam != 0 (N20): the same through gags_project_bwd_cam."""
+def _proj_flags(raw, aa):
+    return (_lib.GAGS_PROJ_RAW if raw else 0) | (_lib.GAGS_PROJ_AA if aa else 0)
+
+
+def _project_fwd(lib, cam, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, near, far, radius_clip,
+                 opac, grec, comp):
+    """gags_project_fwd_cam: the projection forward of every camera model (cam = _lib.GAGS_CAM_*) and variant (flags =
+    _lib.GAGS_PROJ_RAW | _AA) -- the only call of that entry in the package.  opac / grec / comp: the outputs of RAW / RAW / AA,
+    None where the variant has none.  Returns the five outputs every variant has: (radii, means2d, depths, conics, tiles)."""
+    n = means.shape[0]
+    dev = means.device
+    radii = torch.empty(n, dtype=torch.int32, device=dev)
+    means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    depths = torch.empty(n, dtype=torch.float32, device=dev)
+    conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    tiles = torch.empty(n, dtype=torch.int32, device=dev)
+    with profiler.stage("project_fwd"):
+        check(lib.gags_project_fwd_cam(cam, flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat),
+                                       ptr(K), width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths),
+                                       ptr(conics), ptr(tiles), ptr(opac), None, None, ptr(grec), ptr(comp), _lib.stream()),
+              "gags_project_fwd_cam")
+    return radii, means2d, depths, conics, tiles
+
+
+def _project_bwd(lib, cam, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                 v_depths, v_conics, v_opac, v_comp, want, pose):
+    """gags_project_bwd_cam: the projection backward of every camera model and variant, with (pose, N17) or without the
+    cotangent of viewmat -- the only call of that entry in the package.  want = which of (means, quats, scales, opacity logit)
+    get a gradient: the others are neither allocated nor stored (without the pose the entry requires the first three).
+    Returns (v_means, v_quats, v_scales, v_logit, v_viewmat [4,4]), None where not wanted."""
     n = means.shape[0]
     dev = means.device
     v_means, v_quats, v_scales, v_logit = (torch.empty(n, *shape, device=dev) if w else None
                                            for w, shape in zip(want, ((3,), (4,), (3,), ())))
-    v_viewmat = torch.empty(4, 4, device=dev)
-    partials = torch.empty(lib.gags_project_pose_partials(n), 12, device=dev)
-    args = (n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K), width, height, eps2d, ptr(radii),
-            ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac), ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales),
-            ptr(v_logit), ptr(v_viewmat), ptr(partials), partials.numel() * 4, _lib.stream())
-    if cam:  # (GAGS_POSE_RAW / _AA are GAGS_PROJ_RAW / _AA)
-        check(lib.gags_project_bwd_cam(cam, flags | _lib.GAGS_PROJ_POSE, *args), "gags_project_bwd_cam")
-    else:
-        check(lib.gags_project_bwd_pose(flags, *args), "gags_project_bwd_pose")
-    return v_means, v_quats, v_scales, v_logit, v_viewmat
-
-
-def _project_fwd_cam(lib, cam, flags, n, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, near, far,
-                     radius_clip, radii, means2d, depths, conics, tiles, opac, grec, comp):
-    """gags_project_fwd_cam (N20): the projection forward of a non-pinhole camera, every variant through one entry."""
-    check(lib.gags_project_fwd_cam(cam, flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
-                                   width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths),
-                                   ptr(conics), ptr(tiles), ptr(opac), None, None, ptr(grec), ptr(comp), _lib.stream()),
-          "gags_project_fwd_cam")
-
-
-def _project_bwd_cam(lib, cam, flags, n, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
-                     v_depths, v_conics, v_opac, v_comp, v_means, v_quats, v_scales, v_logit):
-    """gags_project_bwd_cam (N20) without the pose."""
+    v_viewmat = partials = None
+    if pose:
+        flags |= _lib.GAGS_PROJ_POSE
+        v_viewmat = torch.empty(4, 4, device=dev)
+        partials = torch.empty(lib.gags_project_pose_partials(n), 12, device=dev)
     check(lib.gags_project_bwd_cam(cam, flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
                                    width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac),
-                                   ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_logit), None, None, 0,
-                                   _lib.stream()), "gags_project_bwd_cam")
+                                   ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_logit), ptr(v_viewmat),
+                                   ptr(partials), partials.numel() * 4 if pose else 0, _lib.stream()), "gags_project_bwd_cam")
+    return v_means, v_quats, v_scales, v_logit, v_viewmat
 
 
 class _Project(torch.autograd.Function):
     """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
-    cotangent in the backward (gags_project_fwd_aa / gags_project_bwd_aa); the caller multiplies them into the opacities.
-    cam (N20): _lib.GAGS_CAM_*; the pinhole (0) goes through the entries it always went through, any other model through
-    gags_project_fwd_cam / gags_project_bwd_cam."""
+    cotangent in the backward; the caller multiplies them into the opacities.  cam (N20): _lib.GAGS_CAM_*; every model, the
+    pinhole (0) included, goes through _project_fwd / _project_bwd."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False, cam=0):
         lib = _lib.load()
         means, quats, scales, viewmat, K = _c(means), _c(quats), _c(scales), _c(viewmat), _c(K)
-        n = means.shape[0]
-        dev = means.device
-        radii = torch.empty(n, dtype=torch.int32, device=dev)
-        means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
-        depths = torch.empty(n, dtype=torch.float32, device=dev)
-        conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        tiles = torch.empty(n, dtype=torch.int32, device=dev)
-        comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
-        entry, name = (lib.gags_project_fwd_aa, "gags_project_fwd_aa") if aa else (lib.gags_project_fwd, "gags_project_fwd")
-        with profiler.stage("project_fwd"):
-            if cam:
-                _project_fwd_cam(lib, cam, _lib.GAGS_PROJ_AA if aa else 0, n, means, quats, scales, None, 1.0, viewmat, K, width,
-                                 height, eps2d, near, far, radius_clip, radii, means2d, depths, conics, tiles, None, None, comp)
-            else:
-                check(entry(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height, eps2d, near, far,
-                            radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(tiles),
-                            *((ptr(comp),) if aa else ()), _lib.stream()), name)
-        ctx.save_for_backward(means, quats, scales, viewmat, K, radii, conics)
+        comp = torch.empty(means.shape[0], dtype=torch.float32, device=means.device) if aa else None
+        radii, means2d, depths, conics, tiles = _project_fwd(lib, cam, _proj_flags(False, aa), means, quats, scales, None, 1.0,
+                                                             viewmat, K, width, height, eps2d, near, far, radius_clip, None, None,
+                                                             comp)
+        ctx.save_for_backward(means, quats, scales, viewmat, K, radii)
         ctx.cfg = (width, height, eps2d, aa, cam)
         ctx.mark_non_differentiable(radii, tiles)
         if aa:
@@ -86,45 +79,29 @@ class _Project(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_comp=None):
         lib = _lib.load()
-        means, quats, scales, viewmat, K, radii, conics = ctx.saved_tensors
+        means, quats, scales, viewmat, K, radii = ctx.saved_tensors
         width, height, eps2d, aa, cam = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
         v_conics = torch.zeros(n, 3, device=dev) if v_conics is None else _c(v_conics)
         v_depths = None if v_depths is None else _c(v_depths)
-        if ctx.needs_input_grad[3]:  # the pose: one more output of the same kernel, and only the scene gradients that are wanted
-            v_comp = None if (not aa or v_comp is None) else _c(v_comp)
-            v_means, v_quats, v_scales, _, v_viewmat = _project_bwd_pose(
-                lib, _lib.GAGS_POSE_AA if aa else 0, means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii,
-                v_means2d, v_depths, v_conics, None, v_comp, tuple(ctx.needs_input_grad[:3]) + (False,), cam)
-            return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None, None
-        v_means = torch.empty(n, 3, device=dev)
-        v_quats = torch.empty(n, 4, device=dev)
-        v_scales = torch.empty(n, 3, device=dev)
-        if cam:
-            v_comp = None if (not aa or v_comp is None) else _c(v_comp)
-            _project_bwd_cam(lib, cam, _lib.GAGS_PROJ_AA if aa else 0, n, means, quats, scales, None, 1.0, viewmat, K, width,
-                             height, eps2d, radii, v_means2d, v_depths, v_conics, None, v_comp, v_means, v_quats, v_scales, None)
-        elif aa:
-            v_comp = None if v_comp is None else _c(v_comp)
-            check(lib.gags_project_bwd_aa(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
-                                          eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_comp),
-                                          ptr(v_means), ptr(v_quats), ptr(v_scales), _lib.stream()), "gags_project_bwd_aa")
-        else:
-            check(lib.gags_project_bwd(n, ptr(means), ptr(quats), ptr(scales), ptr(viewmat), ptr(K), width, height,
-                                       eps2d, ptr(radii), ptr(conics), ptr(v_means2d), ptr(v_depths), ptr(v_conics),
-                                       ptr(v_means), ptr(v_quats), ptr(v_scales), _lib.stream()), "gags_project_bwd")
-        return v_means, v_quats, v_scales, None, None, None, None, None, None, None, None, None, None
+        v_comp = None if (not aa or v_comp is None) else _c(v_comp)
+        # the pose: one more output of the same kernel, and only the scene gradients that are wanted
+        pose = ctx.needs_input_grad[3]
+        want = tuple(ctx.needs_input_grad[:3]) if pose else (True, True, True)
+        v_means, v_quats, v_scales, _, v_viewmat = _project_bwd(
+            lib, cam, _proj_flags(False, aa), means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii, v_means2d,
+            v_depths, v_conics, None, v_comp, want + (False,), pose)
+        return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None, None
 
 
 class _ProjectRaw(torch.autograd.Function):
-    """K1 + K4 on the STORED parameters (gags_project_fwd_raw / gags_project_bwd_raw): the getters of
-    scene/gaussian_model.py:116-139 -- exp, F.normalize, sigmoid -- and render()'s `* scaling_modifier` run inside the
-    projection kernel, bit for bit as torch evaluates them; the backward returns gradients of the stored parameters.
-    aa (rasterize_mode "antialiased"): the kernel folds the compensation into the activated opacity and the record
-    (gags_project_fwd_raw_aa), the compensations [N] are one more -- non-differentiable -- output, and the backward takes the
-    compensation's cotangent from the opacity's (gags_project_bwd_raw_aa).  cam (N20): as in _Project."""
+    """K1 + K4 on the STORED parameters (GAGS_PROJ_RAW): the getters of scene/gaussian_model.py:116-139 -- exp, F.normalize,
+    sigmoid -- and render()'s `* scaling_modifier` run inside the projection kernel, bit for bit as torch evaluates them; the
+    backward returns gradients of the stored parameters.  aa (rasterize_mode "antialiased"): the kernel folds the compensation
+    into the activated opacity and the record, the compensations [N] are one more -- non-differentiable -- output, and the
+    backward takes the compensation's cotangent from the opacity's.  cam (N20): as in _Project."""
 
     @staticmethod
     def forward(ctx, means, rotation, scaling_log, opacity_logit, viewmat, K, width, height, eps2d, near, far, radius_clip,
@@ -134,27 +111,13 @@ class _ProjectRaw(torch.autograd.Function):
         logit = _c(opacity_logit.reshape(-1))
         n = means.shape[0]
         dev = means.device
-        radii = torch.empty(n, dtype=torch.int32, device=dev)
-        means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
-        depths = torch.empty(n, dtype=torch.float32, device=dev)
-        conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        tiles = torch.empty(n, dtype=torch.int32, device=dev)
         opac = torch.empty(n, dtype=torch.float32, device=dev)
         # the per-Gaussian records of the matrix-core raster kernels (K8b), written on the way: no record kernel in the binning
         grec = torch.empty(max(n, 1), 8, dtype=torch.float32, device=dev) if want_records else torch.empty(0, device=dev)
         comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
-        entry, name = ((lib.gags_project_fwd_raw_aa, "gags_project_fwd_raw_aa") if aa
-                       else (lib.gags_project_fwd_raw, "gags_project_fwd_raw"))
-        with profiler.stage("project_fwd"):
-            if cam:
-                _project_fwd_cam(lib, cam, _lib.GAGS_PROJ_RAW | (_lib.GAGS_PROJ_AA if aa else 0), n, means, rotation, scaling_log,
-                                 logit, scaling_modifier, viewmat, K, width, height, eps2d, near, far, radius_clip, radii, means2d,
-                                 depths, conics, tiles, opac, grec if want_records else None, comp)
-            else:
-                check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), scaling_modifier, ptr(viewmat), ptr(K),
-                            width, height, eps2d, near, far, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
-                            ptr(tiles), ptr(opac), None, None, ptr(grec) if want_records else None,
-                            *((ptr(comp),) if aa else ()), _lib.stream()), name)
+        radii, means2d, depths, conics, tiles = _project_fwd(lib, cam, _proj_flags(True, aa), means, rotation, scaling_log, logit,
+                                                             scaling_modifier, viewmat, K, width, height, eps2d, near, far,
+                                                             radius_clip, opac, grec if want_records else None, comp)
         ctx.save_for_backward(means, rotation, scaling_log, logit, viewmat, K, radii)
         ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa, cam)
         if aa:
@@ -174,29 +137,12 @@ class _ProjectRaw(torch.autograd.Function):
         v_conics = torch.zeros(n, 3, device=dev) if v_conics is None else _c(v_conics)
         v_depths = None if v_depths is None else _c(v_depths)
         v_opac = None if v_opac is None else _c(v_opac)
-        if ctx.needs_input_grad[4]:  # the pose (see _Project.backward)
-            flags = _lib.GAGS_POSE_RAW | (_lib.GAGS_POSE_AA if aa else 0)
-            v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd_pose(
-                lib, flags, means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
-                v_depths, v_conics, v_opac, None, tuple(ctx.needs_input_grad[:4]), cam)
-            return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, None, None, None,
-                    None, None, None, None, None, None, None, None)
-        v_means = torch.empty(n, 3, device=dev)
-        v_rot = torch.empty(n, 4, device=dev)
-        v_scal = torch.empty(n, 3, device=dev)
-        v_logit = torch.empty(n, device=dev) if ctx.needs_input_grad[3] else None
-        entry, name = ((lib.gags_project_bwd_raw_aa, "gags_project_bwd_raw_aa") if aa
-                       else (lib.gags_project_bwd_raw, "gags_project_bwd_raw"))
-        if cam:
-            _project_bwd_cam(lib, cam, _lib.GAGS_PROJ_RAW | (_lib.GAGS_PROJ_AA if aa else 0), n, means, rotation, scaling_log,
-                             logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_opac, None,
-                             v_means, v_rot, v_scal, v_logit)
-        else:
-            check(entry(n, ptr(means), ptr(rotation), ptr(scaling_log), ptr(logit), modifier, ptr(viewmat),
-                        ptr(K), width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths),
-                        ptr(v_conics), ptr(v_opac), ptr(v_means), ptr(v_rot), ptr(v_scal), ptr(v_logit),
-                        _lib.stream()), name)
-        return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), None, None, None, None, None,
+        pose = ctx.needs_input_grad[4]  # (see _Project.backward)
+        want = tuple(ctx.needs_input_grad[:4]) if pose else (True, True, True, ctx.needs_input_grad[3])
+        v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd(
+            lib, cam, _proj_flags(True, aa), means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii,
+            v_means2d, v_depths, v_conics, v_opac, None, want, pose)
+        return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, None, None, None, None,
                 None, None, None, None, None, None, None)
 
 

@@ -90,7 +90,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     raw_params=True (not part of gsplat's signature): `quats`, `scales`, `opacities` are the STORED parameters of
     scene/gaussian_model.py:48-61 -- `_rotation` [N,4] un-normalised, `_scaling` [N,3] log-space, `_opacity` [N] or [N,1]
     logits -- and the getters of :116-139 together with `* scaling_modifier` run inside the projection kernel
-    (gags_project_fwd_raw; bit-identical to torch's exp / F.normalize / sigmoid): no elementwise launches, no extra passes
+    (GAGS_PROJ_RAW; bit-identical to torch's exp / F.normalize / sigmoid): no elementwise launches, no extra passes
     over N, and the backward returns the gradients of the stored parameters.
     context (not part of gsplat's signature): the RasterContext that carries this caller's hooks and capacities; None = the
     calling thread's default_context().
@@ -98,15 +98,17 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     from the projection kernel (no constant in the divisor); the opacity every later stage sees --
     and info["opacities"] -- is opacity * comp, and info["compensations"] is [1,N] (None in classic mode).
     viewmats.requires_grad (N17): after backward(), viewmats.grad [1,4,4] is d loss / d viewmats -- the
-    projection backward produces it on the way (gags_project_bwd_pose, a deterministic sum over N, row 3 exactly zero), and the
+    projection backward produces it on the way (GAGS_PROJ_POSE, a deterministic sum over N, row 3 exactly zero), and the
     SH view direction reaches it through campos = inverse(viewmat)[:3, 3], as in gsplat (torch's backward of the 4 x 4 inverse:
     with sh_degree row 3 gets what that puts there).  Scene tensors that need no gradient
     get none computed (pose refinement against a frozen scene).  Ks gets NO gradient, as in gsplat.  With viewmats not
     requiring grad nothing changes: same launches, same bits.
     camera_model (N20): "pinhole", "ortho" (means2d = (fx x + cx, fy y + cy); fx, fy pixels per world unit)
     or "fisheye" (equidistant, no distortion coefficients; z < near_plane is still culled, so the field of view stays below
-    180 degrees).  Only the projection kernels differ (gags_project_fwd_cam / gags_project_bwd_cam); "pinhole" launches what it
-    always launched.  info["camera_model"] repeats it.
+    180 degrees).  Only the projection kernels differ: every model, the pinhole included, goes through the flagged pair
+    gags_project_fwd_cam / gags_project_bwd_cam(camera_model, flags) -- the package calls no other projection entry; the named
+    entries (gags_project_fwd, ..._raw_aa, gags_project_bwd_pose) are compatibility forms of the pair for external callers, and
+    the pinhole kernels are the ones they launch.  info["camera_model"] repeats it.
     absgrad=True: after backward(), info["means2d"].absgrad is the [1,N,2] sum over pixels of the absolute per-pixel
     screen-space gradients (AbsGS), overwritten by each backward; set only where a geometry gradient is produced."""
     rctx = context if context is not None else default_context()

@@ -71,42 +71,156 @@ const char *gags_strerror(int code);
 /* number of HIP devices visible, or a negative error; never throws */
 int gags_device_count(void);
 
-/* K1 + K4: fused projection and tile counting.
- * Replaces the projection stage of gsplat.rasterization reached from
- * gaussian_renderer/__init__.py:56-63 (means, quats wxyz, scales, viewmats, Ks) and the
- * first pass of its tile intersection.  viewmat: row-major 4x4 world-to-camera (the
- * reference's world_view_transform.transpose(0,1), :55); K: row-major 3x3 (:31-38).
- * Outputs: radii[N] (0 = culled), means2d[N,2], depths[N], conics[N,3],
- * tiles_per_gauss[N].  Culled Gaussians get zeros everywhere. */
+/* ---- The projection: K1 + K4 (fused projection and tile counting) forward, K2 backward -------------------------------------
+ * Eleven entries, ONE contract.  gags_project_fwd_cam / gags_project_bwd_cam(camera_model, flags, ...) take the union of all
+ * arguments and are what the package itself calls, for every camera; the nine entries declared behind them are compatibility
+ * forms: each is the flagged entry with GAGS_CAM_PINHOLE and fixed flags, what its argument list lacks filled in (NULL, 1.0f,
+ * 0) -- same launch, same bits, same return codes.
+ *
+ * Forward.  Replaces the projection stage of gsplat.rasterization reached from gaussian_renderer/__init__.py:56-63 (means,
+ * quats wxyz, scales, viewmats, Ks) and the first pass of its tile intersection.  viewmat: row-major 4x4 world-to-camera (the
+ * reference's world_view_transform.transpose(0,1), :55); K: row-major 3x3 (:31-38).  Outputs: radii[N] (0 = culled),
+ * means2d[N,2], depths[N], conics[N,3], tiles_per_gauss[N].  Culled Gaussians get zeros everywhere.
+ * Backward.  The chain rule of the forward for Gaussians with radii > 0 (the forward is recomputed in its operation order).
+ * Inputs v_means2d[N,2], v_depths[N] (may be NULL), v_conics[N,3]; outputs (overwritten) v_means[N,3], v_quats[N,4],
+ * v_scales[N,3].
+ *
+ * camera_model.  The model decides where a centre lands and the 2 x 3 Jacobian J of cov2d = J Sc J^T, with
+ * p = (x, y, z) = Rcw mean + t and Sc = Rcw Sigma Rcw^T; near / far culling on z, depths = z, eps2d, the det <= 0 cull, conic,
+ * radius, radius_clip / off-screen cull, tile count, the antialiased compensation and the pose terms are the same for every
+ * model (N20).
+ *   GAGS_CAM_PINHOLE  means2d = (fx x / z + cx, fy y / z + cy), J with the tangent clamp.
+ *   GAGS_CAM_ORTHO    means2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]; fx, fy are pixels per world unit; no clamp.
+ *   GAGS_CAM_FISHEYE  equidistant, no distortion coefficients, no clamp.  With eps = 1e-7:
+ *                       rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
+ *                       means2d = (fx x theta / rho + cx, fy y theta / rho + cy),
+ *                       x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2, l2 = s + z^2, b = atan2(rho, z) / rho / s, a = z / (l2 s),
+ *                       J = [[fx (x2 a + y2 b), fx xy (a - b), -fx x / l2], [fy xy (a - b), fy (y2 a + x2 b), -fy y / l2]].
+ *                     J IS this closed form, guards included (on the axis: [[fx / z, 0, 0], [0, fy / z, 0]]), not the derivative
+ *                     of the map; the backward is the exact derivative of this forward, with d sqrt(x^2 + y^2) = 0 at x = y = 0,
+ *                     so every output is finite there.  z < near_plane is culled: the field of view stays below 180 degrees.
+ *
+ * flags.  What a variant does not read is ignored, NULL or not.
+ * GAGS_PROJ_RAW: quats / scales / opacity_logit are the STORED parameters (R2 folded into R4; SURVEY 8a R2: "4 elementwise
+ *   kernels/iter over N (fusable into projection)"): rotation[N,4] un-normalised, scaling_log[N,3], opacity_logit[N] exactly
+ *   as scene/gaussian_model.py:48-61 holds them; the kernel applies the getters of :116-139 -- exp (* scaling_modifier,
+ *   gaussian_renderer/__init__.py:41), F.normalize, sigmoid -- bit for bit as torch evaluates them (tools/micro/actprobe.py),
+ *   then projects.  Extra outputs: opacities[N] (activated: what the raster kernels read); quats_act[N,4] / scales_act[N,3]
+ *   (activated; NULL = not wanted); grec (N * GAGS_PACKED_BYTES bytes, or NULL): the per-Gaussian record table of K8b for
+ *   every Gaussian with radii > 0 -- the bytes gags_pack_isects(packed = NULL) would write -- so that the binning needs no
+ *   record kernel.  The backward takes the gradients back to the stored parameters, v_opacities[N] (from the rasterizer;
+ *   NULL = zeros) included; v_opacity_logit may be NULL.  Without RAW opacity_logit, scaling_modifier, opacities, quats_act,
+ *   scales_act, grec, v_opacities and v_opacity_logit are ignored.
+ * GAGS_PROJ_AA: rasterize_mode "antialiased" (Mip-Splatting's opacity compensation; N16).  The rule, in fp32:
+ *   s00, s01, s11 = the 2-D covariance BEFORE eps2d is added;  det_o = s00 s11 - s01^2;  det_b = the blurred determinant
+ *   (s00 + eps2d)(s11 + eps2d) - s01^2;  compensations[i] = sqrt(max(0, det_o / det_b)), and 0 for a culled Gaussian (radius 0).
+ *   No constant is added to the divisor.  The opacity that reaches the binning records, the raster forward and backward is
+ *   fl(opacity * compensation): the caller multiplies (without RAW), or the kernel does on the activated opacity,
+ *   fl(fl(sigmoid(logit)) * compensation), in `opacities` and in the record it writes (with RAW).  Radius, conic, means2d,
+ *   depth and tile count are those without AA bit for bit: the blurred covariance still decides them.  compensations[N] is
+ *   written in full; without AA it is ignored.
+ *   Backward: the exact derivative.  With r = det_o / det_b and (a, b, c) the conic, v_r = v_comp / (2 comp) where comp > 0,
+ *   else 0, and
+ *     d r / d s00 = (1 - r) a - eps2d / det_b,   d r / d s11 = (1 - r) c - eps2d / det_b,   d r / d s01 = 2 (1 - r) b
+ *   are added to the covariance cotangent built from v_conics.  Without RAW v_comp is v_compensations[N] (NULL = zeros); with
+ *   RAW v_opacities is the cotangent of the COMPENSATED opacity: v_comp = v_opacities * sigmoid(logit), v_opacity_logit gets
+ *   the extra factor comp (0 for a culled Gaussian), and v_compensations is ignored (as it is without AA).
+ * GAGS_PROJ_POSE (backward only; N17): the camera pose's cotangent on the way (pose refinement, relocalisation against a
+ *   frozen scene).  v_viewmat[16] (overwritten): d loss / d viewmat, row-major 4 x 4, row 3 exactly zero.  With Rcw, t the
+ *   upper 3 x 4, vp the cotangent of the camera-space point, GSc that of the camera-space covariance and A = Rcw Sigma, a
+ *   Gaussian with radii > 0 contributes
+ *     v_t[r] += vp[r],   v_Rcw[r][c] += vp[r] mean[c] + sum_k (GSc[r][k] + GSc[k][r]) A[k][c]
+ *   and a culled one exactly zero.  K is not differentiated.  The sum over N is deterministic (no atomics): a wave sum, the
+ *   four waves of a workgroup in double, one row of 12 floats per workgroup into `partials`, then gags_colsum_f32 over the
+ *   rows.  partials: gags_project_pose_partials(n) rows of 12 floats, partials_bytes >= rows * 48.  With POSE v_means,
+ *   v_quats / v_rotation, v_scales / v_scaling_log, v_opacity_logit may each be NULL (not wanted: not stored); where given
+ *   they are bit for bit what the call without POSE writes.  Without POSE v_means, v_quats, v_scales are required and
+ *   v_viewmat, partials, partials_bytes are ignored.
+ *
+ * GAGS_EINVAL before any launch: an unknown camera_model, unknown flag bits, n < 0 (before any pointer is looked at), width
+ * or height <= 0, a missing pointer, with POSE a NULL v_viewmat / partials or a short partials_bytes.  n = 0 is GAGS_OK with
+ * NULLs (with POSE v_viewmat is written, zeros). */
+#define GAGS_CAM_PINHOLE 0
+#define GAGS_CAM_ORTHO 1
+#define GAGS_CAM_FISHEYE 2
+#define GAGS_PROJ_RAW 1
+#define GAGS_PROJ_AA 2
+#define GAGS_PROJ_POSE 4
+int64_t gags_project_pose_partials(int n);
+int gags_project_fwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
+                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                         int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
+                         int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
+                         float *opacities, float *quats_act, float *scales_act, void *grec, float *compensations,
+                         void *stream);
+int gags_project_bwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
+                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                         int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                         const float *v_depths, const float *v_conics, const float *v_opacities,
+                         const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                         float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
+
+/* The compatibility forms: nothing of their own but the argument list. */
+/* = gags_project_fwd_cam(GAGS_CAM_PINHOLE, 0): opacity_logit, opacities, quats_act, scales_act, grec, compensations NULL,
+ * scaling_modifier 1.0f. */
 int gags_project_fwd(int n, const float *means, const float *quats, const float *scales,
                      const float *viewmat, const float *K, int width, int height,
                      float eps2d, float near_plane, float far_plane, float radius_clip,
                      int32_t *radii, float *means2d, float *depths, float *conics,
                      int32_t *tiles_per_gauss, void *stream);
-
-/* K1 + K4 in rasterize_mode "antialiased" (Mip-Splatting's opacity compensation; N16).  The rule, in fp32:
- *   s00, s01, s11 = the 2-D covariance BEFORE eps2d is added;  det_o = s00 s11 - s01^2;  det_b = the blurred determinant
- *   (s00 + eps2d)(s11 + eps2d) - s01^2;  compensations[i] = sqrt(max(0, det_o / det_b)), and 0 for a culled Gaussian (radius 0).
- * No constant is added to the divisor.  The opacity that reaches the binning records, the raster forward and backward is
- * fl(opacity * compensation): the caller multiplies (gags_project_fwd_aa), or the kernel does on the activated opacity,
- * fl(fl(sigmoid(logit)) * compensation), in `opacities` and in the record it writes (gags_project_fwd_raw_aa).  Radius, conic,
- * means2d, depth and tile count are those of gags_project_fwd / gags_project_fwd_raw bit for bit: the blurred covariance
- * still decides them.  Same arguments as those entries plus compensations[N] (written in full).
- * Backward: the exact derivative.  With r = det_o / det_b and (a, b, c) the conic, v_r = v_comp / (2 comp) where comp > 0, else
- * 0, and
- *   d r / d s00 = (1 - r) a - eps2d / det_b,   d r / d s11 = (1 - r) c - eps2d / det_b,   d r / d s01 = 2 (1 - r) b
- * are added to the covariance cotangent built from v_conics.  gags_project_bwd_aa takes v_compensations[N] (NULL = zeros);
- * gags_project_bwd_raw_aa takes v_opacities as the cotangent of the COMPENSATED opacity: v_comp = v_opacities * sigmoid(logit),
- * and v_opacity_logit gets the extra factor comp (0 for a culled Gaussian). */
+/* = gags_project_fwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_AA): as gags_project_fwd, compensations passed on. */
 int gags_project_fwd_aa(int n, const float *means, const float *quats, const float *scales,
                         const float *viewmat, const float *K, int width, int height,
                         float eps2d, float near_plane, float far_plane, float radius_clip,
                         int32_t *radii, float *means2d, float *depths, float *conics,
                         int32_t *tiles_per_gauss, float *compensations, void *stream);
+/* = gags_project_fwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW): compensations NULL. */
+int gags_project_fwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
+                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                         int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
+                         int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
+                         float *opacities, float *quats_act, float *scales_act, void *grec, void *stream);
+/* = gags_project_fwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW | GAGS_PROJ_AA): every argument passed on. */
+int gags_project_fwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
+                            const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                            int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
+                            int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
+                            float *opacities, float *quats_act, float *scales_act, void *grec, float *compensations,
+                            void *stream);
+/* = gags_project_bwd_cam(GAGS_CAM_PINHOLE, 0): opacity_logit, v_opacities, v_compensations, v_opacity_logit, v_viewmat, partials
+ * NULL, scaling_modifier 1.0f, partials_bytes 0; `conics` is not read (recomputed in the forward's operation order). */
+int gags_project_bwd(int n, const float *means, const float *quats, const float *scales,
+                     const float *viewmat, const float *K, int width, int height, float eps2d,
+                     const int32_t *radii, const float *conics,
+                     const float *v_means2d, const float *v_depths, const float *v_conics,
+                     float *v_means, float *v_quats, float *v_scales, void *stream);
+/* = gags_project_bwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_AA): as gags_project_bwd, v_compensations passed on. */
 int gags_project_bwd_aa(int n, const float *means, const float *quats, const float *scales,
                         const float *viewmat, const float *K, int width, int height, float eps2d,
                         const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
                         const float *v_compensations, float *v_means, float *v_quats, float *v_scales, void *stream);
+/* = gags_project_bwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW): v_compensations, v_viewmat, partials NULL, partials_bytes 0. */
+int gags_project_bwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
+                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                         int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                         const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
+                         float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream);
+/* = gags_project_bwd_cam(GAGS_CAM_PINHOLE, GAGS_PROJ_RAW | GAGS_PROJ_AA): likewise. */
+int gags_project_bwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
+                            const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                            int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                            const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
+                            float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream);
+/* = gags_project_bwd_cam(GAGS_CAM_PINHOLE, flags | GAGS_PROJ_POSE): every argument passed on.  flags: GAGS_POSE_RAW |
+ * GAGS_POSE_AA (= GAGS_PROJ_RAW, GAGS_PROJ_AA) and nothing else -- GAGS_PROJ_POSE itself is GAGS_EINVAL here. */
+#define GAGS_POSE_RAW 1
+#define GAGS_POSE_AA 2
+int gags_project_bwd_pose(int flags, int n, const float *means, const float *quats, const float *scales,
+                          const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                          int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                          const float *v_depths, const float *v_conics, const float *v_opacities,
+                          const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                          float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
 
 /* K5: inclusive prefix sum of tiles_per_gauss -> cum[N]; the grand total (n_isects) is
  * also written to total[0], or -1 when it does not fit an int32 (the caller must refuse the view; the entries of cum
@@ -386,110 +500,6 @@ int gags_raster_bwd_colors_staged(int d, int n, int width, int height, const int
 int gags_raster_stats(int width, int height, const float *means2d, const float *conics,
                       const float *opacities, const int32_t *isect_offsets, const int32_t *flatten_ids,
                       int64_t n_isects, int64_t *counts, void *stream);
-
-/* K1 + K4 on the STORED parameters (R2 folded into R4; SURVEY 8a R2: "4 elementwise kernels/iter over N (fusable into
- * projection)"): rotation[N,4] un-normalised, scaling_log[N,3], opacity_logit[N] exactly as scene/gaussian_model.py:48-61
- * holds them; the kernel applies the getters of :116-139 -- exp (* scaling_modifier, gaussian_renderer/__init__.py:41),
- * F.normalize, sigmoid -- bit for bit as torch evaluates them (tools/micro/actprobe.py), then projects as gags_project_fwd.
- * Extra outputs: opacities[N] (activated: what the raster kernels read); quats_act[N,4] / scales_act[N,3] (activated; NULL
- * = not wanted); grec (N * GAGS_PACKED_BYTES bytes, or NULL): the per-Gaussian record table of K8b for every Gaussian with
- * radii > 0 -- the bytes gags_pack_isects(packed = NULL) would write -- so that the binning needs no record kernel.  The backward takes the gradients back to the stored parameters, v_opacities[N] (from the rasterizer;
- * NULL = zeros) included; v_opacity_logit may be NULL. */
-int gags_project_fwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
-                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                         int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
-                         int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
-                         float *opacities, float *quats_act, float *scales_act, void *grec, void *stream);
-int gags_project_bwd_raw(int n, const float *means, const float *rotation, const float *scaling_log,
-                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                         int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
-                         const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
-                         float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream);
-/* ... in rasterize_mode "antialiased" (the rule stands at gags_project_fwd_aa): compensations[N] is one more output, and
- * `opacities` and the records carry fl(fl(sigmoid(logit)) * compensation). */
-int gags_project_fwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
-                            const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                            int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
-                            int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
-                            float *opacities, float *quats_act, float *scales_act, void *grec, float *compensations,
-                            void *stream);
-int gags_project_bwd_raw_aa(int n, const float *means, const float *rotation, const float *scaling_log,
-                            const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                            int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
-                            const float *v_depths, const float *v_conics, const float *v_opacities, float *v_means,
-                            float *v_rotation, float *v_scaling_log, float *v_opacity_logit, void *stream);
-
-/* K2: projection backward: chain rule of gags_project_fwd for Gaussians with radii>0.
- * Inputs v_means2d[N,2], v_depths[N] (may be NULL), v_conics[N,3];
- * outputs (overwritten) v_means[N,3], v_quats[N,4], v_scales[N,3]. */
-int gags_project_bwd(int n, const float *means, const float *quats, const float *scales,
-                     const float *viewmat, const float *K, int width, int height, float eps2d,
-                     const int32_t *radii, const float *conics,
-                     const float *v_means2d, const float *v_depths, const float *v_conics,
-                     float *v_means, float *v_quats, float *v_scales, void *stream);
-
-/* N17: the projection backward with the camera pose's cotangent (pose refinement, relocalisation against a frozen scene).
- * flags: GAGS_POSE_RAW = the stored parameters, as gags_project_bwd_raw[_aa]; GAGS_POSE_AA = rasterize_mode "antialiased", as
- * gags_project_bwd_aa / _raw_aa.  The arguments are the union of those entries' (what a variant does not read is ignored:
- * opacity_logit, scaling_modifier, v_opacities, v_opacity_logit without RAW; v_compensations unless AA without RAW).
- * v_viewmat[16] (overwritten): d loss / d viewmat, row-major 4 x 4, row 3 exactly zero.  With Rcw, t the upper 3 x 4, vp the
- * cotangent of the camera-space point, GSc that of the camera-space covariance and A = Rcw Sigma, a Gaussian with radii > 0
- * contributes
- *   v_t[r] += vp[r],   v_Rcw[r][c] += vp[r] mean[c] + sum_k (GSc[r][k] + GSc[k][r]) A[k][c]
- * and a culled one exactly zero.  K is not differentiated.  The sum over N is deterministic (no atomics): a wave sum, the four
- * waves of a workgroup in double, one row of 12 floats per workgroup into `partials`, then gags_colsum_f32 over the rows.
- * v_means, v_quats / v_rotation, v_scales / v_scaling_log, v_opacity_logit may each be NULL (not wanted: not stored); where
- * given they are bit for bit what gags_project_bwd* writes.  partials: gags_project_pose_partials(n) rows of 12 floats
- * (partials_bytes >= rows * 48, else GAGS_EINVAL before any launch; NULL v_viewmat or partials likewise).  n = 0: v_viewmat
- * is written (zeros). */
-#define GAGS_POSE_RAW 1
-#define GAGS_POSE_AA 2
-int64_t gags_project_pose_partials(int n);
-int gags_project_bwd_pose(int flags, int n, const float *means, const float *quats, const float *scales,
-                          const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                          int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
-                          const float *v_depths, const float *v_conics, const float *v_opacities,
-                          const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
-                          float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
-/* N20: camera models.  The model decides where a centre lands and the 2 x 3 Jacobian J of cov2d = J Sc J^T, with
- * p = (x, y, z) = Rcw mean + t and Sc = Rcw Sigma Rcw^T as above; near / far culling on z, depths = z, eps2d, the det <= 0 cull,
- * conic, radius, radius_clip / off-screen cull, tile count, the antialiased compensation and the pose terms are those of the
- * entries above for every model.
- *   GAGS_CAM_PINHOLE  means2d = (fx x / z + cx, fy y / z + cy), J with the tangent clamp: the entries above, bit for bit.
- *   GAGS_CAM_ORTHO    means2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]; fx, fy are pixels per world unit; no clamp.
- *   GAGS_CAM_FISHEYE  equidistant, no distortion coefficients, no clamp.  With eps = 1e-7:
- *                       rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
- *                       means2d = (fx x theta / rho + cx, fy y theta / rho + cy),
- *                       x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2, l2 = s + z^2, b = atan2(rho, z) / rho / s, a = z / (l2 s),
- *                       J = [[fx (x2 a + y2 b), fx xy (a - b), -fx x / l2], [fy xy (a - b), fy (y2 a + x2 b), -fy y / l2]].
- *                     J IS this closed form, guards included (on the axis: [[fx / z, 0, 0], [0, fy / z, 0]]), not the derivative
- *                     of the map; the backward is the exact derivative of this forward, with d sqrt(x^2 + y^2) = 0 at x = y = 0,
- *                     so every output is finite there.  z < near_plane is culled: the field of view stays below 180 degrees.
- * flags: GAGS_PROJ_RAW = the stored parameters (gags_project_fwd_raw / _bwd_raw), GAGS_PROJ_AA = rasterize_mode "antialiased",
- * GAGS_PROJ_POSE (backward only) = v_viewmat on the way (gags_project_bwd_pose).  The arguments are the union of those entries';
- * what a variant does not read is ignored (forward: opacity_logit, scaling_modifier, opacities, quats_act, scales_act, grec
- * without RAW, compensations without AA; backward: as gags_project_bwd_pose, and v_viewmat / partials without POSE).  Without
- * POSE v_means, v_quats, v_scales are required, with POSE each may be NULL.  GAGS_EINVAL before any launch: an unknown
- * camera_model, unknown flag bits, n < 0, a missing pointer, with POSE a NULL v_viewmat / partials or partials_bytes <
- * gags_project_pose_partials(n) * 48.  n = 0 is GAGS_OK (with POSE v_viewmat is written, zeros). */
-#define GAGS_CAM_PINHOLE 0
-#define GAGS_CAM_ORTHO 1
-#define GAGS_CAM_FISHEYE 2
-#define GAGS_PROJ_RAW 1
-#define GAGS_PROJ_AA 2
-#define GAGS_PROJ_POSE 4
-int gags_project_fwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
-                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                         int width, int height, float eps2d, float near_plane, float far_plane, float radius_clip,
-                         int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
-                         float *opacities, float *quats_act, float *scales_act, void *grec, float *compensations,
-                         void *stream);
-int gags_project_bwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
-                         const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
-                         int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
-                         const float *v_depths, const float *v_conics, const float *v_opacities,
-                         const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
-                         float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
 
 /* Column sums of an fp32 table [n_rows, k], 1 <= k <= 12: out[c] = sign * sum over rows of table[r, c] for c < k, and
  * out[k .. n_out) = 0 (k <= n_out <= 256).  One workgroup, sums in double, fixed order: two calls give the same bits.

@@ -32,12 +32,12 @@ def _kscene(model, eps2d=0.3):
     return cm.model_scene(model, 700, 0, W, H, cm.KERNEL_SEEDS[model]), dict(cm.KERNEL_CULL, eps2d=eps2d)
 
 
-def _cut(s, n):
-    """The first n Gaussians of a scene."""
+def _cut(s, n, start=0):
+    """n Gaussians of a scene, the first n or those from `start` on."""
     out = dict(s)
     for k in ("means", "quats", "scales", "opacities"):
-        out[k] = s[k][:n]
-    out["raw"] = {k: (v[:n] if torch.is_tensor(v) else v) for k, v in s["raw"].items()}
+        out[k] = s[k][start:start + n]
+    out["raw"] = {k: (v[start:start + n] if torch.is_tensor(v) else v) for k, v in s["raw"].items()}
     return out
 
 
@@ -49,31 +49,60 @@ def _inputs(s, flags):
     return to_dev(s["means"]), to_dev(s["quats"]), to_dev(s["scales"]), None
 
 
-def k_fwd(model, flags, s, cull, modifier=1.0):
-    """gags_project_fwd_cam on a scene: dict of GPU tensors (radii, means2d, depths, conics, tiles, opac | None, comp | None)."""
+def _fwd_outputs(n, flags, extras):
+    """The forward's outputs, pre-filled: what an entry does not write shows.  extras (RAW): quats_act, scales_act and the
+    [max(n, 1), 8] record table too, else None (passed as NULL)."""
+    extra = lambda *shape: torch.full(shape, 7.0, device="cuda") if (extras and flags & RAW) else None  # noqa: E731
+    return dict(radii=torch.full((n,), -7, dtype=torch.int32, device="cuda"), means2d=torch.full((n, 2), 7.0, device="cuda"),
+                depths=torch.full((n,), 7.0, device="cuda"), conics=torch.full((n, 3), 7.0, device="cuda"),
+                tiles=torch.full((n,), -7, dtype=torch.int32, device="cuda"),
+                opac=torch.full((n,), 7.0, device="cuda") if flags & RAW else None,
+                quats_act=extra(n, 4), scales_act=extra(n, 3), grec=extra(max(n, 1), 8),
+                comp=torch.full((n,), 7.0, device="cuda") if flags & AA else None)
+
+
+def k_fwd(model, flags, s, cull, modifier=1.0, extras=False):
+    """gags_project_fwd_cam on a scene: dict of GPU tensors (radii, means2d, depths, conics, tiles, opac | None, quats_act |
+    None, scales_act | None, grec | None, comp | None)."""
     from gags_amd import _lib
     from gags_amd._lib import check, ptr
     lib = _lib.load()
     means, quats, scales, logit = _inputs(s, flags)
     vm, K = to_dev(s["viewmat"]), to_dev(s["K"])      # (held here: a temporary's memory would be reused before the launch)
     n = means.shape[0]
-    o = dict(radii=torch.full((n,), -7, dtype=torch.int32, device="cuda"), means2d=torch.full((n, 2), 7.0, device="cuda"),
-             depths=torch.full((n,), 7.0, device="cuda"), conics=torch.full((n, 3), 7.0, device="cuda"),
-             tiles=torch.full((n,), -7, dtype=torch.int32, device="cuda"),
-             opac=torch.full((n,), 7.0, device="cuda") if flags & RAW else None,
-             comp=torch.full((n,), 7.0, device="cuda") if flags & AA else None)
+    o = _fwd_outputs(n, flags, extras)
     check(lib.gags_project_fwd_cam(cm.MODELS[model], flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier,
                                    ptr(vm), ptr(K), W, H, cull["eps2d"], cull["near_plane"],
                                    cull["far_plane"], cull["radius_clip"], ptr(o["radii"]), ptr(o["means2d"]), ptr(o["depths"]),
-                                   ptr(o["conics"]), ptr(o["tiles"]), ptr(o["opac"]), None, None, None, ptr(o["comp"]),
-                                   _lib.stream()), "gags_project_fwd_cam")
+                                   ptr(o["conics"]), ptr(o["tiles"]), ptr(o["opac"]), ptr(o["quats_act"]), ptr(o["scales_act"]),
+                                   ptr(o["grec"]), ptr(o["comp"]), _lib.stream()), "gags_project_fwd_cam")
+    torch.cuda.synchronize()
+    return o
+
+
+def named_fwd(flags, s, cull, modifier=1.0, extras=False):
+    """k_fwd's dict from the named pinhole entry of `flags`: gags_project_fwd / _aa / _raw / _raw_aa, called directly."""
+    from gags_amd import _lib
+    from gags_amd._lib import check, ptr
+    lib = _lib.load()
+    means, quats, scales, logit = _inputs(s, flags)
+    vm, K = to_dev(s["viewmat"]), to_dev(s["K"])
+    n = means.shape[0]
+    o = _fwd_outputs(n, flags, extras)
+    name = "gags_project_fwd" + ("_raw" if flags & RAW else "") + ("_aa" if flags & AA else "")
+    check(getattr(lib, name)(n, ptr(means), ptr(quats), ptr(scales), *((ptr(logit), modifier) if flags & RAW else ()), ptr(vm),
+                             ptr(K), W, H, cull["eps2d"], cull["near_plane"], cull["far_plane"], cull["radius_clip"],
+                             ptr(o["radii"]), ptr(o["means2d"]), ptr(o["depths"]), ptr(o["conics"]), ptr(o["tiles"]),
+                             *((ptr(o["opac"]), ptr(o["quats_act"]), ptr(o["scales_act"]), ptr(o["grec"])) if flags & RAW else ()),
+                             *((ptr(o["comp"]),) if flags & AA else ()), _lib.stream()), name)
     torch.cuda.synchronize()
     return o
 
 
 def k_bwd(model, flags, s, cull, radii, cot, modifier=1.0, skip=(), entry="cam"):
     """gags_project_bwd_cam: dict(means, quats, scales, opacities | None, viewmat [4,4] | None) of GPU tensors.  skip: outputs
-    passed as NULL (POSE only).  entry="old": the same through the entries without a camera model (pinhole)."""
+    passed as NULL (POSE only).  entry="old": the same through the entry without a camera model (pinhole) that `flags` names,
+    gags_project_bwd_pose with POSE, else gags_project_bwd / _aa / _raw / _raw_aa."""
     from gags_amd import _lib
     from gags_amd._lib import check, ptr
     lib = _lib.load()
@@ -97,9 +126,18 @@ def k_bwd(model, flags, s, cull, radii, cot, modifier=1.0, skip=(), entry="cam")
               ptr(g["opacities"]), ptr(g["viewmat"]), ptr(partials), 0 if partials is None else partials.numel() * 4, _lib.stream())
     if entry == "cam":
         check(lib.gags_project_bwd_cam(cm.MODELS[model], flags, *common), "gags_project_bwd_cam")
-    else:
-        assert model == "pinhole" and pose
+    elif pose:
+        assert model == "pinhole"
         check(lib.gags_project_bwd_pose(flags & 3, *common), "gags_project_bwd_pose")
+    else:  # the named pinhole entry of `flags`: gags_project_bwd / _aa / _raw / _raw_aa
+        assert model == "pinhole"
+        name = "gags_project_bwd" + ("_raw" if raw else "") + ("_aa" if aa else "")
+        conics = torch.full((n, 3), 7.0, device="cuda")   # gags_project_bwd's ignored argument: a real tensor
+        check(getattr(lib, name)(n, ptr(means), ptr(quats), ptr(scales), *((ptr(logit), modifier) if raw else ()), ptr(vm), ptr(K),
+                                 W, H, cull["eps2d"], ptr(radii), *(() if (raw or aa) else (ptr(conics),)), ptr(v_m2), ptr(v_z),
+                                 ptr(v_con), *((ptr(v_opac),) if raw else ()), *((ptr(v_comp),) if (aa and not raw) else ()),
+                                 ptr(g["means"]), ptr(g["quats"]), ptr(g["scales"]), *((ptr(g["opacities"]),) if raw else ()),
+                                 _lib.stream()), name)
     torch.cuda.synchronize()
     return g
 
@@ -254,7 +292,8 @@ def test_backward_against_float64_autograd(model, n):
 
 
 def test_pinhole_through_the_new_entries_is_the_existing_entries():
-    """GAGS_CAM_PINHOLE: torch.equal to gags_project_fwd / _aa / _raw / _raw_aa, gags_project_bwd* and gags_project_bwd_pose."""
+    """GAGS_CAM_PINHOLE: torch.equal to gags_project_fwd / _aa / _raw / _raw_aa, gags_project_bwd* and gags_project_bwd_pose,
+    each called directly; _Project / _ProjectRaw (which go through the flagged pair) are the third party to the same equalities."""
     from gags_amd.raster_project import _Project, _ProjectRaw
     n = 700
     s = cm.model_scene("pinhole", n, 0, W, H, 13)
@@ -265,6 +304,10 @@ def test_pinhole_through_the_new_entries_is_the_existing_entries():
     for flags in (0, AA, RAW, RAW | AA):
         aa = bool(flags & AA)
         got = k_fwd("pinhole", flags, s, cull)
+        named = named_fwd(flags, s, cull)
+        for k in got:
+            if got[k] is not None:
+                assert torch.equal(got[k], named[k]), (k, flags)
         means, quats, scales, logit = _inputs(s, flags)
         leaves = [t.clone().requires_grad_(True) for t in (means, quats, scales) + ((logit,) if flags & RAW else ())]
         if flags & RAW:
@@ -276,8 +319,8 @@ def test_pinhole_through_the_new_entries_is_the_existing_entries():
         assert int((got["radii"] > 0).sum()) >= 100
         for t, k in zip(old, names):
             if k is not None:
-                assert torch.equal(t, got[k]), (k, flags)
-        # the backward without the pose, through autograd on the existing entries
+                assert torch.equal(t, got[k]) and torch.equal(t, named[k]), (k, flags)
+        # the backward without the pose: the flagged entry, the named entry, and autograd through the python wrapper
         o = dict(zip(names, old))
         loss = (o["means2d"] * to_dev(cot["means2d"])).sum() + (o["depths"] * to_dev(cot["depths"])).sum() + \
             (o["conics"] * to_dev(cot["conics"])).sum()
@@ -287,14 +330,48 @@ def test_pinhole_through_the_new_entries_is_the_existing_entries():
             loss = loss + (o["comp"] * to_dev(cot["comp"])).sum()
         loss.backward()
         g = k_bwd("pinhole", flags, s, cull, got["radii"], cot)
+        g_named = k_bwd("pinhole", flags, s, cull, got["radii"], cot, entry="old")
         for t, k in zip(leaves, ("means", "quats", "scales", "opacities")):
-            assert torch.equal(t.grad, g[k]), (k, flags)
+            assert torch.equal(g[k], g_named[k]), (k, flags)
+            assert torch.equal(t.grad, g[k]) and torch.equal(t.grad, g_named[k]), (k, flags)
         gp_new = k_bwd("pinhole", flags | POSE, s, cull, got["radii"], cot)
         gp_old = k_bwd("pinhole", flags | POSE, s, cull, got["radii"], cot, entry="old")
         for k in gp_new:
             if gp_new[k] is not None:
                 assert torch.equal(gp_new[k], gp_old[k]), (k, flags)
         assert bool(gp_new["viewmat"][:3].any())
+
+
+@pytest.mark.parametrize("n", (1, 257))   # one lane of one wave; two workgroups with a one-lane tail
+def test_named_entries_forward_to_the_flagged_pair(n):
+    """Each named forward, each named backward and gags_project_bwd_pose against the flagged entry with GAGS_CAM_PINHOLE: the same
+    inputs and cotangents, every output pre-filled on both sides (an output a forward fails to pass through keeps its fill on
+    one side only), torch.equal on all of them -- RAW with quats_act, scales_act and the record table non-NULL."""
+    full = cm.model_scene("pinhole", 700, 0, W, H, 13)
+    cull = dict(eps2d=0.3, near_plane=0.01, far_plane=1e10, radius_clip=0.0)
+    # rows n0 .. n0 + n, n0 the first Gaussian the float32 restatement sees on screen and away from every decision boundary
+    _, dec, _ = _truth("pinhole", full, cull, 0, torch.float32)
+    n0 = int(np.flatnonzero((dec["radii"] > 0) & ~dec["close"])[0])
+    assert n0 + n <= 700
+    s = _cut(full, n, n0)
+    cot = cm.cotangents(n, 5)
+    for flags in (0, AA, RAW, RAW | AA):
+        got, named = k_fwd("pinhole", flags, s, cull, modifier=1.25, extras=True), named_fwd(flags, s, cull, modifier=1.25, extras=True)
+        assert bool((got["radii"] > 0).any()) and not bool((got["radii"] == -7).any())
+        wrote = ("radii", "means2d", "depths", "conics", "tiles") + (("opac", "quats_act", "scales_act", "grec") if flags & RAW else ()) \
+            + (("comp",) if flags & AA else ())
+        assert sorted(wrote) == sorted(k for k in got if got[k] is not None)
+        for k in wrote:
+            assert torch.equal(got[k], named[k]), (k, flags)
+            assert not bool((got[k][got["radii"] > 0] == 7).all()), (k, flags)   # (the flagged entry wrote it)
+        for fl in (flags, flags | POSE):
+            g = k_bwd("pinhole", fl, s, cull, got["radii"], cot, modifier=1.25)
+            g_named = k_bwd("pinhole", fl, s, cull, got["radii"], cot, modifier=1.25, entry="old")
+            wrote = ("means", "quats", "scales") + (("opacities",) if flags & RAW else ()) + (("viewmat",) if fl & POSE else ())
+            assert sorted(wrote) == sorted(k for k in g if g[k] is not None)
+            for k in wrote:
+                assert torch.equal(g[k], g_named[k]), (k, fl)
+                assert not bool((g[k] == 7).all()), (k, fl)
 
 
 ON_AXIS_MEASURED = 1.84e-7   # worst relative difference below, as measured on an MI355X (v_quats; docs/LAB_NOTES.md)
