@@ -31,7 +31,7 @@ __device__ __forceinline__ Cam load_cam(const float *__restrict__ vm, const floa
 // the backward calls cam_bwd, in every RAW / AA / POSE variant.  The pinhole bodies are the expressions the kernels held before
 // N20, token for token: same operation order, same bits.
 //   ortho:    means2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]; no clamp.
-//   fisheye:  equidistant, no distortion, no clamp; eps = 1e-7:  rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
+//   fisheye:  equidistant, no clamp (with distortion coefficients: N21, below); eps = 1e-7:  rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
 //             means2d = (fx x theta / rho + cx, fy y theta / rho + cy); x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2,
 //             l2 = s + z^2, b = atan2(rho, z) / rho / s, a = z / (l2 s),
 //             J = [[fx (x2 a + y2 b), fx xy (a - b), -fx x / l2], [fy xy (a - b), fy (y2 a + x2 b), -fy y / l2]].
@@ -54,9 +54,35 @@ __device__ __forceinline__ CamLim cam_limits(float fx, float fy, float cx, float
 
 constexpr float GAGS_FISHEYE_EPS = 1e-7f;
 
+// N21: the fisheye with distortion coefficients (GAGS_PROJ_KB: K carries k1 .. k4 behind its nine floats) is a fourth value of
+// CAM, private to this file.  theta_d = g(theta) = theta P(theta^2) stands where the fisheye has theta (in k and in b), and
+// dg = g'(tb) = P'(tb^2) multiplies a and the third column of J; by Horner in t = theta^2:
+//   P(t) = 1 + t (k1 + t (k2 + t (k3 + t k4))),  P'(t) = 1 + t (3 k1 + t (5 k2 + t (7 k3 + t 9 k4))),
+//   g''(theta) = theta (6 k1 + t (20 k2 + t (42 k3 + t 72 k4))).
+// With k1 .. k4 = 0: P = P' = 1 and g'' = 0 exactly, and every expression below rounds as the plain fisheye's does (same bits,
+// forward and backward).  dg <= 0 (the image folds back on itself) is a cull: cam_fwd returns dg, 1 for every other model.
+constexpr int GAGS_CAM_FISHEYE_KB = 3;
+struct Kb { float k1, k2, k3, k4; };
+
 template <int CAM>
-__device__ __forceinline__ void cam_fwd(float fx, float fy, float cx, float cy, const CamLim &lim, float x, float y, float z,
-                                        float &m2x, float &m2y, float (&J)[2][3])
+__device__ __forceinline__ Kb load_kb(const float *__restrict__ K)
+{
+    if constexpr (CAM == GAGS_CAM_FISHEYE_KB) return Kb{K[9], K[10], K[11], K[12]};
+    else return Kb{0.f, 0.f, 0.f, 0.f};  // (K is nine floats: nothing behind them is read)
+}
+__device__ __forceinline__ float kb_P(const Kb &c, float t) { return 1.f + t * (c.k1 + t * (c.k2 + t * (c.k3 + t * c.k4))); }
+__device__ __forceinline__ float kb_dP(const Kb &c, float t)
+{
+    return 1.f + t * (3.f * c.k1 + t * (5.f * c.k2 + t * (7.f * c.k3 + t * (9.f * c.k4))));
+}
+__device__ __forceinline__ float kb_ddg(const Kb &c, float theta, float t)
+{
+    return theta * (6.f * c.k1 + t * (20.f * c.k2 + t * (42.f * c.k3 + t * (72.f * c.k4))));
+}
+
+template <int CAM>
+__device__ __forceinline__ float cam_fwd(float fx, float fy, float cx, float cy, const CamLim &lim, const Kb &kb, float x, float y,
+                                         float z, float &m2x, float &m2y, float (&J)[2][3])
 {
     if constexpr (CAM == GAGS_CAM_PINHOLE) {
         const float rz = 1.f / z;
@@ -72,6 +98,21 @@ __device__ __forceinline__ void cam_fwd(float fx, float fy, float cx, float cy, 
         J[1][0] = 0.f; J[1][1] = fy; J[1][2] = 0.f;
         m2x = fx * x + cx;
         m2y = fy * y + cy;
+    } else if constexpr (CAM == GAGS_CAM_FISHEYE_KB) {
+        const float rho = sqrtf(x * x + y * y) + GAGS_FISHEYE_EPS;
+        const float theta = atan2f(rho, z + GAGS_FISHEYE_EPS);
+        const float k = (theta * kb_P(kb, theta * theta)) / rho;
+        m2x = (fx * x) * k + cx;
+        m2y = (fy * y) * k + cy;
+        const float x2 = x * x + GAGS_FISHEYE_EPS, y2 = y * y, xy = x * y;
+        const float s = x2 + y2, l2 = s + z * z;
+        const float tb = atan2f(rho, z), tt = tb * tb;
+        const float dg = kb_dP(kb, tt);
+        const float b = (tb * kb_P(kb, tt)) / rho / s, a = dg * (z / (l2 * s));
+        const float amb = a - b;
+        J[0][0] = fx * (x2 * a + y2 * b); J[0][1] = (fx * xy) * amb; J[0][2] = -fx * x / l2 * dg;
+        J[1][0] = (fy * xy) * amb; J[1][1] = fy * (y2 * a + x2 * b); J[1][2] = -fy * y / l2 * dg;
+        return dg;
     } else {
         const float rho = sqrtf(x * x + y * y) + GAGS_FISHEYE_EPS;
         const float theta = atan2f(rho, z + GAGS_FISHEYE_EPS);
@@ -85,13 +126,14 @@ __device__ __forceinline__ void cam_fwd(float fx, float fy, float cx, float cy, 
         J[0][0] = fx * (x2 * a + y2 * b); J[0][1] = (fx * xy) * amb; J[0][2] = -fx * x / l2;
         J[1][0] = (fy * xy) * amb; J[1][1] = fy * (y2 * a + x2 * b); J[1][2] = -fy * y / l2;
     }
+    return 1.f;
 }
 
 // (v_means2d, vJ) -> vp, the cotangent of the camera-space point; v_depth (the cotangent of depths = z, when has_depth) joins
 // vp[2] where the pinhole kernel has always added it, between the means2d term and the J terms.
 template <int CAM>
-__device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, float x, float y, float z, float vm2x, float vm2y,
-                                        const float (&vJ)[2][3], bool has_depth, float v_depth, float (&vp)[3])
+__device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, const Kb &kb, float x, float y, float z, float vm2x,
+                                        float vm2y, const float (&vJ)[2][3], bool has_depth, float v_depth, float (&vp)[3])
 {
     if constexpr (CAM == GAGS_CAM_PINHOLE) {
         const float rz = 1.f / z, rz2 = rz * rz, rz3 = rz2 * rz;
@@ -111,6 +153,66 @@ __device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, f
         vp[0] = fx * vm2x;  // (J is constant: vJ reaches nothing)
         vp[1] = fy * vm2y;
         vp[2] = has_depth ? v_depth : 0.f;
+    } else if constexpr (CAM == GAGS_CAM_FISHEYE_KB) {  // the fisheye's chain below with g, dg and their three cotangents
+        const float r0 = sqrtf(x * x + y * y);
+        const float rho = r0 + GAGS_FISHEYE_EPS, zt = z + GAGS_FISHEYE_EPS;
+        const float theta = atan2f(rho, zt);
+        const float k = (theta * kb_P(kb, theta * theta)) / rho;
+        const float x2 = x * x + GAGS_FISHEYE_EPS, y2 = y * y, xy = x * y;
+        const float s = x2 + y2, z2 = z * z, l2 = s + z2;
+        const float tb = atan2f(rho, z), tt = tb * tb;
+        const float dg = kb_dP(kb, tt);
+        const float a0 = z / (l2 * s);
+        const float b = (tb * kb_P(kb, tt)) / rho / s, a = dg * a0;
+        // means2d = (fx x k + cx, fy y k + cy), k = g(theta) / rho
+        const float v_k = (fx * x) * vm2x + (fy * y) * vm2y;
+        float vx = (fx * k) * vm2x, vy = (fy * k) * vm2y, vz = has_depth ? v_depth : 0.f;
+        const float v_g = v_k / rho;
+        float v_rho = -(v_k * k) / rho;
+        // J (the closed form): cotangents of x2, y2, xy, a, b, l2, dg
+        const float g00 = fx * vJ[0][0], g01 = fx * vJ[0][1], g02 = fx * vJ[0][2];
+        const float g10 = fy * vJ[1][0], g11 = fy * vJ[1][1], g12 = fy * vJ[1][2];
+        const float gx = g01 + g10;
+        float v_x2 = g00 * a + g11 * b;
+        float v_y2 = g00 * b + g11 * a;
+        const float v_a = (g00 * x2 + g11 * y2) + gx * xy;
+        const float v_b = (g00 * y2 + g11 * x2) - gx * xy;
+        const float v_xy = gx * (a - b);
+        vx += -g02 / l2 * dg;
+        vy += -g12 / l2 * dg;
+        float v_l2 = (g02 * x + g12 * y) / (l2 * l2) * dg;
+        float v_dg = -(g02 * x + g12 * y) / l2;
+        // a = dg a0, a0 = z / (l2 s)
+        vz += (v_a * dg) / (l2 * s);
+        v_l2 += -(v_a * a) / l2;
+        float v_s = -(v_a * a) / s;
+        v_dg += v_a * a0;
+        // b = g(tb) / (rho s), dg = g'(tb), tb = atan2(rho, z)
+        const float v_gb = v_b / (rho * s);
+        v_rho += -(v_b * b) / rho;
+        v_s += -(v_b * b) / s;
+        const float v_tb = v_gb * dg + v_dg * kb_ddg(kb, tb, tt);
+        const float hb = rho * rho + z2;
+        v_rho += v_tb * z / hb;
+        vz += -(v_tb * rho) / hb;
+        // l2 = s + z^2, s = x2 + y2, x2 = x^2 + eps, y2 = y^2, xy = x y
+        v_s += v_l2;
+        vz += 2.f * z * v_l2;
+        v_x2 += v_s;
+        v_y2 += v_s;
+        vx += 2.f * x * v_x2 + y * v_xy;
+        vy += 2.f * y * v_y2 + x * v_xy;
+        // g(theta), theta = atan2(rho, z + eps)
+        const float v_theta = v_g * kb_dP(kb, theta * theta);
+        const float ht = rho * rho + zt * zt;
+        v_rho += v_theta * zt / ht;
+        vz += -(v_theta * rho) / ht;
+        // rho = sqrt(x^2 + y^2) + eps; its derivative at x = y = 0 is taken as 0
+        if (r0 > 0.f) {
+            vx += v_rho * (x / r0);
+            vy += v_rho * (y / r0);
+        }
+        vp[0] = vx; vp[1] = vy; vp[2] = vz;
     } else {
         const float r0 = sqrtf(x * x + y * y);
         const float rho = r0 + GAGS_FISHEYE_EPS, zt = z + GAGS_FISHEYE_EPS;
@@ -258,9 +360,9 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
         const float v22 = (a20 * c.R20 + a21 * c.R21) + a22 * c.R22;
 
         float m2x, m2y, J[2][3];
-        cam_fwd<CAM>(c.fx, c.fy, c.cx, c.cy, lim, x, y, z, m2x, m2y, J);
+        const float dg = cam_fwd<CAM>(c.fx, c.fy, c.cx, c.cy, lim, load_kb<CAM>(Kmat), x, y, z, m2x, m2y, J);
         float s00, s01, s11;
-        if constexpr (CAM != GAGS_CAM_FISHEYE) {  // J[0][1] = J[1][0] = 0: the products the pinhole kernel has always formed
+        if constexpr (CAM != GAGS_CAM_FISHEYE && CAM != GAGS_CAM_FISHEYE_KB) {  // J[0][1] = J[1][0] = 0: the products the pinhole kernel has always formed
             const float j00 = J[0][0], j02 = J[0][2];
             const float j11 = J[1][1], j12 = J[1][2];
             const float b00 = j00 * v00 + j02 * v02;
@@ -287,7 +389,9 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
         if constexpr (AA) det_o = s00 * s11 - s01 * s01;
         s00 += eps2d; s11 += eps2d;
         const float det = s00 * s11 - s01 * s01;
-        if (det > 0.f) {
+        bool keep = det > 0.f;
+        if constexpr (CAM == GAGS_CAM_FISHEYE_KB) keep = keep && dg > 0.f;  // (past the fold: culled)
+        if (keep) {
             const float inv_det = 1.f / det;
             const float hb = 0.5f * (s00 + s11);
             const float v1 = hb + sqrtf(fmaxf(0.01f, hb * hb - det));
@@ -491,7 +595,8 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 3; ++c)
             Sc[r][c] = (A[r][0] * Rc[c][0] + A[r][1] * Rc[c][1]) + A[r][2] * Rc[c][2];
         float m2x_, m2y_, J[2][3];  // (the centre itself is not needed again)
-        cam_fwd<CAM>(fx, fy, cx, cy, lim, x, y, z, m2x_, m2y_, J);
+        const Kb kb = load_kb<CAM>(Kmat);
+        cam_fwd<CAM>(fx, fy, cx, cy, lim, kb, x, y, z, m2x_, m2y_, J);
         (void)m2x_; (void)m2y_;
         float B[2][3];
         _Pragma("unroll") for (int r = 0; r < 2; ++r) _Pragma("unroll") for (int c = 0; c < 3; ++c)
@@ -544,7 +649,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         /* ---- 3. J and mean2d/depth -> camera-space point ---- */
         const float vm2x = v_means2d[2 * i], vm2y = v_means2d[2 * i + 1];
         float vp[3];
-        cam_bwd<CAM>(fx, fy, lim, x, y, z, vm2x, vm2y, vJ, v_depths != nullptr, v_depths ? v_depths[i] : 0.f, vp);
+        cam_bwd<CAM>(fx, fy, lim, kb, x, y, z, vm2x, vm2y, vJ, v_depths != nullptr, v_depths ? v_depths[i] : 0.f, vp);
         if constexpr (POSE) {
             _Pragma("unroll") for (int r = 0; r < 3; ++r) {
                 _Pragma("unroll") for (int c = 0; c < 3; ++c)
@@ -769,8 +874,10 @@ int with_flags(F &&f, bool b, Bs... bs)
              : with_flags([&](auto... cs) { return f(std::false_type{}, cs...); }, bs...);
 }
 template <class F, class... Bs>
-int with_camera(int camera_model, F &&f, Bs... bs)  // (camera_model is one of the three: the entries have checked)
+int with_camera(int camera_model, bool kb, F &&f, Bs... bs)  // (one of the three, kb only with the fisheye: the entries have checked)
 {
+    if (kb)
+        return with_flags([&](auto... cs) { return f(std::integral_constant<int, GAGS_CAM_FISHEYE_KB>{}, cs...); }, bs...);
     if (camera_model == GAGS_CAM_ORTHO)
         return with_flags([&](auto... cs) { return f(std::integral_constant<int, GAGS_CAM_ORTHO>{}, cs...); }, bs...);
     if (camera_model == GAGS_CAM_FISHEYE)
@@ -788,13 +895,14 @@ extern "C" int gags_project_fwd_cam(int camera_model, int flags, int n, const fl
                                     float *compensations, void *stream)
 {
     GAGS_CLEAR_ERR();
-    if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE || (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA)))
+    if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE || (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA | GAGS_PROJ_KB)))
         return GAGS_EINVAL;
-    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA;
+    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA, kb = flags & GAGS_PROJ_KB;
+    if (kb && camera_model != GAGS_CAM_FISHEYE) return GAGS_EINVAL;  // (the coefficients are the fisheye's)
     // what a variant does not read is ignored
     if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; opacities = nullptr; quats_act = nullptr; scales_act = nullptr; grec = nullptr; }
     if (!aa) compensations = nullptr;
-    return with_camera(camera_model, [&](auto CAM, auto RAW, auto AA) {
+    return with_camera(camera_model, kb, [&](auto CAM, auto RAW, auto AA) {
         return project_fwd_launch<RAW.value, AA.value, CAM.value>(
             n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, near_plane, far_plane,
             radius_clip, radii, means2d, depths, conics, tiles_per_gauss, opacities, quats_act, scales_act, grec, compensations,
@@ -811,16 +919,17 @@ extern "C" int gags_project_bwd_cam(int camera_model, int flags, int n, const fl
 {
     GAGS_CLEAR_ERR();
     if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE ||
-        (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA | GAGS_PROJ_POSE)))
+        (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA | GAGS_PROJ_POSE | GAGS_PROJ_KB)))
         return GAGS_EINVAL;
+    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA, pose = flags & GAGS_PROJ_POSE, kb = flags & GAGS_PROJ_KB;
+    if (kb && camera_model != GAGS_CAM_FISHEYE) return GAGS_EINVAL;
     if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
-    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA, pose = flags & GAGS_PROJ_POSE;
     // (a short partials buffer would be written out of bounds: refused before anything is launched)
     if (pose && (!v_viewmat || !partials || partials_bytes < gags_project_pose_partials(n) * 12 * (int64_t)sizeof(float)))
         return GAGS_EINVAL;
     if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; v_opacities = nullptr; v_opacity_logit = nullptr; }
     if (raw || !aa) v_compensations = nullptr;
-    return with_camera(camera_model, [&](auto CAM, auto RAW, auto AA, auto POSE) {
+    return with_camera(camera_model, kb, [&](auto CAM, auto RAW, auto AA, auto POSE) {
         if constexpr (POSE.value)
             return project_bwd_pose_launch<RAW.value, AA.value, CAM.value>(
                 n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d,

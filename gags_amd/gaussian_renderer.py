@@ -61,6 +61,28 @@ def _intrinsics(viewpoint_camera, device, cache):
     return K
 
 
+def _intrinsics_kb(viewpoint_camera, device, cache):
+    """(K [3,3], radial_coeffs [4]) of a camera that carries distortion coefficients (N21): two views of ONE resident block of
+    13 floats, [K row-major, k1 .. k4], which is what the projection kernels read behind GAGS_PROJ_KB -- rasterization()
+    recognises the layout and launches nothing to build it.  The block lives in `cache` as K does; the nine values of K and
+    the four coefficients are the key, so that cameras that differ only in their coefficients do not share an entry."""
+    explicit = getattr(viewpoint_camera, "K", None)
+    if explicit is None:
+        raise ValueError("a camera with radial_coeffs needs an explicit K [3,3] attribute")
+    vals = tuple(float(v) for v in torch.as_tensor(explicit).detach().reshape(-1).tolist())
+    coeffs = tuple(float(v) for v in torch.as_tensor(viewpoint_camera.radial_coeffs).detach().reshape(-1).tolist())
+    if len(vals) != 9 or len(coeffs) != 4:
+        raise ValueError("a camera's K must be [3,3] and its radial_coeffs [4]")
+    key = ("KB", vals, coeffs, str(device))
+    block = cache.get(key)
+    if block is None:
+        block = torch.tensor(vals + coeffs, dtype=torch.float32, device=device)
+        if len(cache) > 4096:
+            cache.clear()
+        cache[key] = block
+    return block[:9].view(3, 3), block[9:]
+
+
 # R2 folded into R4 (SURVEY 8a: the getters are "4 elementwise kernels/iter over N (fusable into projection)"): when `pc`
 # stores its parameters the way scene/gaussian_model.py:48-61 does and activates them the way :36-42 does (exp, sigmoid,
 # F.normalize), render() hands the STORED tensors to the projection kernel, which applies those getters itself -- bit for
@@ -112,10 +134,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
     rasterize_mode / absgrad: gsplat's options of the same names, handed to rasterization() (antialiased opacity
     compensation; `viewspace_points.absgrad` after backward(), which densify.accumulate(..., absgrad=True) reads).
     The camera model (N20) is read from the camera: `viewpoint_camera.camera_model` ("pinhole" when absent, "ortho", "fisheye"),
-    and `viewpoint_camera.K` [3,3], when present, replaces the FoV-derived intrinsics; a non-pinhole camera must carry one."""
+    and `viewpoint_camera.K` [3,3], when present, replaces the FoV-derived intrinsics; a non-pinhole camera must carry one.  `viewpoint_camera.radial_coeffs` (N21; None when
+    absent): a fisheye camera's distortion coefficients (k1 .. k4), resident on the device next to K after the first render."""
     rctx = context if context is not None else default_context()
     means3D = pc.get_xyz
-    K = _intrinsics(viewpoint_camera, means3D.device, rctx.k_cache)
+    radial_coeffs = None
+    if getattr(viewpoint_camera, "radial_coeffs", None) is not None:
+        K, radial_coeffs = _intrinsics_kb(viewpoint_camera, means3D.device, rctx.k_cache)
+    else:
+        K = _intrinsics(viewpoint_camera, means3D.device, rctx.k_cache)
     stored = _stored_parameters(pc)
     if stored is not None:
         rotations, scales, opacity = stored
@@ -141,7 +168,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
         width=int(viewpoint_camera.image_width), height=int(viewpoint_camera.image_height),
         packed=False, sh_degree=sh_degree, render_mode=render_mode, raster_flags=raster_flags,
         raw_params=stored is not None, scaling_modifier=float(scaling_modifier), context=rctx,
-        rasterize_mode=rasterize_mode, absgrad=absgrad, camera_model=camera_model_of(viewpoint_camera))
+        rasterize_mode=rasterize_mode, absgrad=absgrad, camera_model=camera_model_of(viewpoint_camera),
+        radial_coeffs=radial_coeffs)
 
     # squeeze (not [0]): its backward is a view, [0]'s is a zero-fill + copy of the whole map
     rendered_image = render_colors.squeeze(0).permute(2, 0, 1)  # [1,H,W,D'] -> [D',H,W]

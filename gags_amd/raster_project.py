@@ -10,14 +10,15 @@ def _c(t):
     return t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float()
 
 
-def _proj_flags(raw, aa):
-    return (_lib.GAGS_PROJ_RAW if raw else 0) | (_lib.GAGS_PROJ_AA if aa else 0)
+def _proj_flags(raw, aa, kb=False):
+    return (_lib.GAGS_PROJ_RAW if raw else 0) | (_lib.GAGS_PROJ_AA if aa else 0) | (_lib.GAGS_PROJ_KB if kb else 0)
 
 
 def _project_fwd(lib, cam, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, near, far, radius_clip,
                  opac, grec, comp):
     """gags_project_fwd_cam: the projection forward of every camera model (cam = _lib.GAGS_CAM_*) and variant (flags =
-    _lib.GAGS_PROJ_RAW | _AA) -- the only call of that entry in the package.  opac / grec / comp: the outputs of RAW / RAW / AA,
+    _lib.GAGS_PROJ_RAW | _AA | _KB; with _KB, N21, K is the 13-float block [K, k1 .. k4]) -- the only call of that entry in the
+    package.  opac / grec / comp: the outputs of RAW / RAW / AA,
     None where the variant has none.  Returns the five outputs every variant has: (radii, means2d, depths, conics, tiles)."""
     n = means.shape[0]
     dev = means.device
@@ -59,18 +60,19 @@ def _project_bwd(lib, cam, flags, means, quats, scales, logit, modifier, viewmat
 class _Project(torch.autograd.Function):
     """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
     cotangent in the backward; the caller multiplies them into the opacities.  cam (N20): _lib.GAGS_CAM_*; every model, the
-    pinhole (0) included, goes through _project_fwd / _project_bwd."""
+    pinhole (0) included, goes through _project_fwd / _project_bwd.  kb (N21, fisheye only): K is the 13-float block, the
+    matrix then the distortion coefficients (GAGS_PROJ_KB); it gets no gradient, as K gets none."""
 
     @staticmethod
-    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False, cam=0):
+    def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False, cam=0, kb=False):
         lib = _lib.load()
         means, quats, scales, viewmat, K = _c(means), _c(quats), _c(scales), _c(viewmat), _c(K)
         comp = torch.empty(means.shape[0], dtype=torch.float32, device=means.device) if aa else None
-        radii, means2d, depths, conics, tiles = _project_fwd(lib, cam, _proj_flags(False, aa), means, quats, scales, None, 1.0,
+        radii, means2d, depths, conics, tiles = _project_fwd(lib, cam, _proj_flags(False, aa, kb), means, quats, scales, None, 1.0,
                                                              viewmat, K, width, height, eps2d, near, far, radius_clip, None, None,
                                                              comp)
         ctx.save_for_backward(means, quats, scales, viewmat, K, radii)
-        ctx.cfg = (width, height, eps2d, aa, cam)
+        ctx.cfg = (width, height, eps2d, aa, cam, kb)
         ctx.mark_non_differentiable(radii, tiles)
         if aa:
             return radii, means2d, depths, conics, tiles, comp
@@ -80,7 +82,7 @@ class _Project(torch.autograd.Function):
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_comp=None):
         lib = _lib.load()
         means, quats, scales, viewmat, K, radii = ctx.saved_tensors
-        width, height, eps2d, aa, cam = ctx.cfg
+        width, height, eps2d, aa, cam, kb = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
@@ -91,9 +93,9 @@ class _Project(torch.autograd.Function):
         pose = ctx.needs_input_grad[3]
         want = tuple(ctx.needs_input_grad[:3]) if pose else (True, True, True)
         v_means, v_quats, v_scales, _, v_viewmat = _project_bwd(
-            lib, cam, _proj_flags(False, aa), means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii, v_means2d,
+            lib, cam, _proj_flags(False, aa, kb), means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii, v_means2d,
             v_depths, v_conics, None, v_comp, want + (False,), pose)
-        return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None, None
+        return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None, None, None
 
 
 class _ProjectRaw(torch.autograd.Function):
@@ -101,11 +103,11 @@ class _ProjectRaw(torch.autograd.Function):
     sigmoid -- and render()'s `* scaling_modifier` run inside the projection kernel, bit for bit as torch evaluates them; the
     backward returns gradients of the stored parameters.  aa (rasterize_mode "antialiased"): the kernel folds the compensation
     into the activated opacity and the record, the compensations [N] are one more -- non-differentiable -- output, and the
-    backward takes the compensation's cotangent from the opacity's.  cam (N20): as in _Project."""
+    backward takes the compensation's cotangent from the opacity's.  cam (N20), kb (N21): as in _Project."""
 
     @staticmethod
     def forward(ctx, means, rotation, scaling_log, opacity_logit, viewmat, K, width, height, eps2d, near, far, radius_clip,
-                scaling_modifier, want_records, aa=False, cam=0):
+                scaling_modifier, want_records, aa=False, cam=0, kb=False):
         lib = _lib.load()
         means, rotation, scaling_log, viewmat, K = _c(means), _c(rotation), _c(scaling_log), _c(viewmat), _c(K)
         logit = _c(opacity_logit.reshape(-1))
@@ -115,11 +117,11 @@ class _ProjectRaw(torch.autograd.Function):
         # the per-Gaussian records of the matrix-core raster kernels (K8b), written on the way: no record kernel in the binning
         grec = torch.empty(max(n, 1), 8, dtype=torch.float32, device=dev) if want_records else torch.empty(0, device=dev)
         comp = torch.empty(n, dtype=torch.float32, device=dev) if aa else None
-        radii, means2d, depths, conics, tiles = _project_fwd(lib, cam, _proj_flags(True, aa), means, rotation, scaling_log, logit,
+        radii, means2d, depths, conics, tiles = _project_fwd(lib, cam, _proj_flags(True, aa, kb), means, rotation, scaling_log, logit,
                                                              scaling_modifier, viewmat, K, width, height, eps2d, near, far,
                                                              radius_clip, opac, grec if want_records else None, comp)
         ctx.save_for_backward(means, rotation, scaling_log, logit, viewmat, K, radii)
-        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa, cam)
+        ctx.cfg = (width, height, eps2d, scaling_modifier, tuple(opacity_logit.shape), aa, cam, kb)
         if aa:
             ctx.mark_non_differentiable(radii, tiles, grec, comp)
             return radii, means2d, depths, conics, tiles, opac, grec, comp
@@ -130,7 +132,7 @@ class _ProjectRaw(torch.autograd.Function):
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, _v_tiles, v_opac, _v_grec, _v_comp=None):
         lib = _lib.load()
         means, rotation, scaling_log, logit, viewmat, K, radii = ctx.saved_tensors
-        width, height, eps2d, modifier, oshape, aa, cam = ctx.cfg
+        width, height, eps2d, modifier, oshape, aa, cam, kb = ctx.cfg
         n = means.shape[0]
         dev = means.device
         v_means2d = torch.zeros(n, 2, device=dev) if v_means2d is None else _c(v_means2d)
@@ -140,10 +142,10 @@ class _ProjectRaw(torch.autograd.Function):
         pose = ctx.needs_input_grad[4]  # (see _Project.backward)
         want = tuple(ctx.needs_input_grad[:4]) if pose else (True, True, True, ctx.needs_input_grad[3])
         v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd(
-            lib, cam, _proj_flags(True, aa), means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii,
+            lib, cam, _proj_flags(True, aa, kb), means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii,
             v_means2d, v_depths, v_conics, v_opac, None, want, pose)
         return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, None, None, None, None,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
 
 
 class _SH(torch.autograd.Function):

@@ -71,6 +71,16 @@ def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrou
             (proj, proj, v_cols, v_opac, rg(backgrounds)))
 
 
+def _kb_block(K, coeffs):
+    """The 13 floats GAGS_PROJ_KB reads, [K row-major, k1 .. k4] (N21).  When K [3,3] and coeffs already lie so in memory
+    (render() keeps the block in its context's k_cache and hands over two views of it) that memory is the block: no launch."""
+    K, c = K.detach(), coeffs.detach().reshape(4)
+    if (K.dtype == torch.float32 and K.is_contiguous() and c.is_contiguous() and K.device == c.device
+            and K.untyped_storage().data_ptr() == c.untyped_storage().data_ptr() and c.storage_offset() == K.storage_offset() + 9):
+        return torch.as_strided(K, (13,), (1,))
+    return torch.cat([K.reshape(9).float(), c])
+
+
 class _Pass(NamedTuple):
     """One binning + rasterize pass of rasterization() (`run` there)."""
     binning: Binning
@@ -84,7 +94,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
                   near_plane=0.01, far_plane=1e10, radius_clip=0.0, eps2d=0.3, sh_degree=None, packed=False,
                   tile_size=16, backgrounds=None, render_mode="RGB", sparse_grad=False, absgrad=False,
                   rasterize_mode="classic", channel_chunk=32, distributed=False, camera_model="pinhole",
-                  covars=None, raster_flags=0, raw_params=False, scaling_modifier=1.0, context=None):
+                  covars=None, raster_flags=0, raw_params=False, scaling_modifier=1.0, context=None, radial_coeffs=None):
     """See module docstring.  `channel_chunk` is accepted and ignored: any D is composited in a
     single pass over the sorted lists (SURVEY A12 shows this is identical per channel).
     raw_params=True (not part of gsplat's signature): `quats`, `scales`, `opacities` are the STORED parameters of
@@ -104,11 +114,18 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     get none computed (pose refinement against a frozen scene).  Ks gets NO gradient, as in gsplat.  With viewmats not
     requiring grad nothing changes: same launches, same bits.
     camera_model (N20): "pinhole", "ortho" (means2d = (fx x + cx, fy y + cy); fx, fy pixels per world unit)
-    or "fisheye" (equidistant, no distortion coefficients; z < near_plane is still culled, so the field of view stays below
+    or "fisheye" (equidistant, distortion coefficients through radial_coeffs; z < near_plane is still culled, so the field of view stays below
     180 degrees).  Only the projection kernels differ: every model, the pinhole included, goes through the flagged pair
     gags_project_fwd_cam / gags_project_bwd_cam(camera_model, flags) -- the package calls no other projection entry; the named
     entries (gags_project_fwd, ..._raw_aa, gags_project_bwd_pose) are compatibility forms of the pair for external callers, and
     the pinhole kernels are the ones they launch.  info["camera_model"] repeats it.
+    radial_coeffs (N21; only with camera_model="fisheye"): the lens' distortion coefficients (k1, k2, k3, k4) of OpenCV's fisheye
+    model / COLMAP's OPENCV_FISHEYE, theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), a float32 tensor
+    [4] or [1,4] on the GPU.  They reach the projection kernels as 13 floats [K, k1 .. k4] behind GAGS_PROJ_KB and go through
+    the same linearisation (cov2d = J Sc J^T) as every model; a Gaussian past the angle where theta_d stops growing is culled;
+    they get no gradient, as Ks gets none.  The block is built on the device with one copy kernel -- unless Ks[0] and
+    radial_coeffs already lie so in memory, as the views render() hands over do.  None: the call without the argument, same
+    launches, flags and bits.  info["radial_coeffs"] repeats the tensor (or None).
     absgrad=True: after backward(), info["means2d"].absgrad is the [1,N,2] sum over pixels of the absolute per-pixel
     screen-space gradients (AbsGS), overwritten by each backward; set only where a geometry gradient is produced."""
     rctx = context if context is not None else default_context()
@@ -122,6 +139,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     if not isinstance(camera_model, str) or camera_model not in _lib.CAMERA_MODELS:  # (plain values: before any tensor is looked at)
         raise ValueError(f"unknown camera_model {camera_model!r} (\"pinhole\", \"ortho\" or \"fisheye\")")
     cam = _lib.CAMERA_MODELS[camera_model]
+    kb = radial_coeffs is not None
+    if kb:
+        if camera_model != "fisheye":
+            raise ValueError(f"radial_coeffs are the distortion coefficients of camera_model=\"fisheye\", not of {camera_model!r}")
+        if not torch.is_tensor(radial_coeffs) or tuple(radial_coeffs.shape) not in ((4,), (1, 4)) or radial_coeffs.dtype != torch.float32:
+            raise ValueError("radial_coeffs must be a float32 tensor [4] or [1,4]: (k1, k2, k3, k4)")
     if covars is not None or distributed:
         raise NotImplementedError("only the options the reference uses are implemented "
                                   "(quats+scales, one process per view)")
@@ -143,13 +166,15 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     route = _route(n, d, f16, needs, int(raster_flags), profiler.ENABLED, rctx.capacity_mode, rctx.early_rowmap,
                    rctx.overlap_zero_fill, rctx.grad_range_hook is not None, rctx.trim_lists, absgrad=absgrad)
     _check_absgrad_route(route, d)  # (before any launch, and before the tensors are looked at: plain values decide it)
-    _need_cuda(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds)
+    _need_cuda(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, radial_coeffs)
+    if kb:
+        K = _kb_block(K, radial_coeffs)
 
     records, compensations = None, None
     if raw_params:
         radii, means2d, depths, conics, tiles, opacities, records, *comp = _ProjectRaw.apply(
             means, quats, scales, opacities, viewmat, K, width, height, float(eps2d), float(near_plane), float(far_plane),
-            float(radius_clip), float(scaling_modifier), route.records and n > 0, aa, cam)
+            float(radius_clip), float(scaling_modifier), route.records and n > 0, aa, cam, kb)
         if records.numel() == 0:
             records = None
         if aa:  # (already folded into `opacities` and the records by the kernel)
@@ -157,7 +182,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     else:
         radii, means2d, depths, conics, tiles, *comp = _Project.apply(means, quats, scales, viewmat, K, width, height,
                                                                       float(eps2d), float(near_plane), float(far_plane),
-                                                                      float(radius_clip), aa, cam)
+                                                                      float(radius_clip), aa, cam, kb)
         if aa:  # a torch multiply: autograd carries both factors
             compensations = comp[0]
             opacities = opacities * compensations
@@ -266,6 +291,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         "tiles_per_gauss": tiles[None], "isect_ids": isect_ids, "flatten_ids": flatten_ids,
         "isect_offsets": p.binning.isect_offsets[None], "last_ids": p.last_ids, "width": width, "height": height,
         "tile_size": T.TILE, "n_cameras": 1, "n_isects": n_isects, "camera_model": camera_model,
+        "radial_coeffs": radial_coeffs,
         "n_isects_trimmed": p.n_trimmed,  # (not gsplat's: list entries the raster passes worked on when the lists were trimmed, else None)
     }
     return out[None], alphas[None, ..., None], info

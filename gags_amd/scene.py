@@ -47,13 +47,23 @@ def fov2focal(fov, pixels):
 
 class Camera:
     """Minimal stand-in for scene.cameras.Camera / MiniCam.  camera_model / K (N20): "pinhole", "ortho" or "fisheye", and
-    explicit intrinsics [3,3] that render() then uses instead of the FoV-derived ones (required for a non-pinhole camera)."""
+    explicit intrinsics [3,3] that render() then uses instead of the FoV-derived ones (required for a non-pinhole camera).
+    radial_coeffs (N21; fisheye only): the distortion coefficients (k1, k2, k3, k4) of OpenCV's fisheye model, kept as float32 [4]."""
 
-    def __init__(self, R, T, FoVx, FoVy, image_width, image_height, device="cuda", uid=0, camera_model="pinhole", K=None):
+    def __init__(self, R, T, FoVx, FoVy, image_width, image_height, device="cuda", uid=0, camera_model="pinhole", K=None,
+                 radial_coeffs=None):
         self.uid = uid
         if camera_model not in ("pinhole", "ortho", "fisheye"):
             raise ValueError(f"unknown camera_model {camera_model!r} (\"pinhole\", \"ortho\" or \"fisheye\")")
         self.camera_model = camera_model
+        self.radial_coeffs = None
+        if radial_coeffs is not None:
+            if camera_model != "fisheye":
+                raise ValueError(f"radial_coeffs are the distortion coefficients of a \"fisheye\" camera, not of a {camera_model!r} one")
+            self.radial_coeffs = np.asarray(radial_coeffs.detach().cpu() if torch.is_tensor(radial_coeffs) else radial_coeffs,
+                                            dtype=np.float32).reshape(-1)
+            if self.radial_coeffs.shape != (4,):
+                raise ValueError("radial_coeffs must be (k1, k2, k3, k4)")
         self.K = None
         if K is not None:
             self.K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float32)
@@ -70,6 +80,20 @@ class Camera:
         w2c = getWorld2View2(self.R, self.T)
         self.world_view_transform = torch.tensor(w2c).transpose(0, 1).contiguous().to(device)
         self.camera_center = torch.tensor(np.linalg.inv(w2c.astype(np.float64))[:3, 3], dtype=torch.float32).to(device)
+
+    @classmethod
+    def from_opencv_fisheye(cls, params, R, T, width, height, device="cuda", uid=0):
+        """A fisheye camera from a calibration in COLMAP's OPENCV_FISHEYE order: params = (fx, fy, cx, cy, k1, k2, k3, k4).
+        FoVx / FoVy (which render() does not read for this model) are the angles the equidistant map puts at the image's edges."""
+        params = [float(v) for v in np.asarray(params, dtype=np.float64).reshape(-1)]
+        if len(params) != 8:
+            raise ValueError("params must be (fx, fy, cx, cy, k1, k2, k3, k4)")
+        fx, fy, cx, cy = params[:4]
+        if not (fx > 0 and fy > 0):
+            raise ValueError("fx and fy must be positive")
+        K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32)
+        return cls(R, T, width / fx, height / fy, width, height, device=device, uid=uid, camera_model="fisheye", K=K,
+                   radial_coeffs=params[4:])
 
 
 def inverse_sigmoid(x):

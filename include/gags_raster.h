@@ -91,7 +91,7 @@ int gags_device_count(void);
  * model (N20).
  *   GAGS_CAM_PINHOLE  means2d = (fx x / z + cx, fy y / z + cy), J with the tangent clamp.
  *   GAGS_CAM_ORTHO    means2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]; fx, fy are pixels per world unit; no clamp.
- *   GAGS_CAM_FISHEYE  equidistant, no distortion coefficients, no clamp.  With eps = 1e-7:
+ *   GAGS_CAM_FISHEYE  equidistant, no clamp; distortion coefficients with GAGS_PROJ_KB (below).  With eps = 1e-7:
  *                       rho = sqrt(x^2 + y^2) + eps, theta = atan2(rho, z + eps),
  *                       means2d = (fx x theta / rho + cx, fy y theta / rho + cy),
  *                       x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2, l2 = s + z^2, b = atan2(rho, z) / rho / s, a = z / (l2 s),
@@ -136,16 +136,35 @@ int gags_device_count(void);
  *   v_quats / v_rotation, v_scales / v_scaling_log, v_opacity_logit may each be NULL (not wanted: not stored); where given
  *   they are bit for bit what the call without POSE writes.  Without POSE v_means, v_quats, v_scales are required and
  *   v_viewmat, partials, partials_bytes are ignored.
+ * GAGS_PROJ_KB (both directions, only with GAGS_CAM_FISHEYE; N21): the fisheye's distortion coefficients, OpenCV's fisheye
+ *   model / COLMAP's OPENCV_FISHEYE: theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8).  K then points to
+ *   13 floats: the row-major 3 x 3 matrix, then k1, k2, k3, k4 (without the flag K is 9 floats and nothing behind them is
+ *   read).  By Horner in t = theta^2:
+ *     P(t) = 1 + t (k1 + t (k2 + t (k3 + t k4))),   P'(t) = 1 + t (3 k1 + t (5 k2 + t (7 k3 + t 9 k4))),
+ *     g(theta) = theta P(theta^2),   g'(theta) = P'(theta^2),   g''(theta) = theta (6 k1 + t (20 k2 + t (42 k3 + t 72 k4))).
+ *   The rule, with the guards of GAGS_CAM_FISHEYE (eps = 1e-7):
+ *     rho = sqrt(x^2 + y^2) + eps,  theta = atan2(rho, z + eps),  tb = atan2(rho, z),
+ *     means2d = (fx x g(theta) / rho + cx, fy y g(theta) / rho + cy),
+ *     x2 = x^2 + eps, y2 = y^2, xy = x y, s = x2 + y2, l2 = s + z^2, b = g(tb) / rho / s, dg = g'(tb), a = dg * (z / (l2 s)),
+ *     J = [[fx (x2 a + y2 b), fx xy (a - b), -fx x / l2 * dg], [fy xy (a - b), fy (y2 a + x2 b), -fy y / l2 * dg]]:
+ *   the closed form above with g(theta) in the two places theta stands, and g'(tb) on a and on the third column.  With
+ *   k1 .. k4 = 0, P = P' = 1 and g'' = 0 exactly, and every output, forward and backward, is bit for bit the one without the
+ *   flag.  A Gaussian with dg <= 0 is culled (radius 0, zeros everywhere): there the image folds back on itself, and no lens
+ *   maps that way; every other cull is shared and unchanged.  The backward is the exact derivative of this forward: the
+ *   cotangents v_g (from g(theta) / rho), v_gb (from b) and v_dg (from a and the third column) return through
+ *   v_theta += v_g g'(theta) and v_tb += v_gb g'(tb) + v_dg g''(tb), then the fisheye's chain.  K and the coefficients get no
+ *   gradient.  POSE as for every model.
  *
- * GAGS_EINVAL before any launch: an unknown camera_model, unknown flag bits, n < 0 (before any pointer is looked at), width
- * or height <= 0, a missing pointer, with POSE a NULL v_viewmat / partials or a short partials_bytes.  n = 0 is GAGS_OK with
- * NULLs (with POSE v_viewmat is written, zeros). */
+ * GAGS_EINVAL before any launch: an unknown camera_model, unknown flag bits, GAGS_PROJ_KB with a camera_model other than
+ * GAGS_CAM_FISHEYE, n < 0 (before any pointer is looked at), width or height <= 0, a missing pointer, with POSE a NULL
+ * v_viewmat / partials or a short partials_bytes.  n = 0 is GAGS_OK with NULLs (with POSE v_viewmat is written, zeros). */
 #define GAGS_CAM_PINHOLE 0
 #define GAGS_CAM_ORTHO 1
 #define GAGS_CAM_FISHEYE 2
 #define GAGS_PROJ_RAW 1
 #define GAGS_PROJ_AA 2
 #define GAGS_PROJ_POSE 4
+#define GAGS_PROJ_KB 32
 int64_t gags_project_pose_partials(int n);
 int gags_project_fwd_cam(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
                          const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
