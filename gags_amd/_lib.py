@@ -161,6 +161,12 @@ SIGNATURES = {
     "gags_depthsample_scratch_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "gags_depthsample_map": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_depthsample_scatter": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # N22: ... for a rig of any camera models (cam_models: a HOST int32 array or NULL, radial_coeffs: device [C, 4] or NULL)
+    "gags_rig_depth_scratch_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "gags_rig_depth_map": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _i64,
+                                  _vp]),
+    "gags_rig_depth_scatter": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _i64,
+                                      _vp]),
     # N7: the photometric loss of the RGB stage
     "gags_photometric_partials": (_i64, [_i32, _i32, _i32]),
     "gags_photometric_fwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _f64, _f64, _f64,

@@ -41,6 +41,17 @@ __device__ __forceinline__ float gags_exp_neg(float sigma)
     return __builtin_ldexpf(p, (int)n);
 }
 
+// The fisheye's guard (include/gags_raster.h "GAGS_CAM_FISHEYE") and its distortion polynomial (N21, "GAGS_PROJ_KB"), by Horner
+// in t = theta^2: P(t) = 1 + t (k1 + t (k2 + t (k3 + t k4))), P'(t) = 1 + t (3 k1 + t (5 k2 + t (7 k3 + t 9 k4))).  Zero
+// coefficients give P = P' = 1 exactly.  Shared by the projection (project.hip) and the min-depth mapping (depthsample.hip).
+constexpr float GAGS_FISHEYE_EPS = 1e-7f;
+struct Kb { float k1, k2, k3, k4; };
+__device__ __forceinline__ float kb_P(const Kb &c, float t) { return 1.f + t * (c.k1 + t * (c.k2 + t * (c.k3 + t * c.k4))); }
+__device__ __forceinline__ float kb_dP(const Kb &c, float t)
+{
+    return 1.f + t * (3.f * c.k1 + t * (5.f * c.k2 + t * (7.f * c.k3 + t * (9.f * c.k4))));
+}
+
 __device__ __forceinline__ void gags_tile_aabb(float mx, float my, int radius, int tile_w, int tile_h,
                                                int &x0, int &x1, int &y0, int &y1)
 {

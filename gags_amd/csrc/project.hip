@@ -52,8 +52,6 @@ __device__ __forceinline__ CamLim cam_limits(float fx, float fy, float cx, float
     return l;
 }
 
-constexpr float GAGS_FISHEYE_EPS = 1e-7f;
-
 // N21: the fisheye with distortion coefficients (GAGS_PROJ_KB: K carries k1 .. k4 behind its nine floats) is a fourth value of
 // CAM, private to this file.  theta_d = g(theta) = theta P(theta^2) stands where the fisheye has theta (in k and in b), and
 // dg = g'(tb) = P'(tb^2) multiplies a and the third column of J; by Horner in t = theta^2:
@@ -61,19 +59,14 @@ constexpr float GAGS_FISHEYE_EPS = 1e-7f;
 //   g''(theta) = theta (6 k1 + t (20 k2 + t (42 k3 + t 72 k4))).
 // With k1 .. k4 = 0: P = P' = 1 and g'' = 0 exactly, and every expression below rounds as the plain fisheye's does (same bits,
 // forward and backward).  dg <= 0 (the image folds back on itself) is a cull: cam_fwd returns dg, 1 for every other model.
+// (GAGS_FISHEYE_EPS, Kb, kb_P and kb_dP stand in common.h: the min-depth mapping of depthsample.hip projects with them too.)
 constexpr int GAGS_CAM_FISHEYE_KB = 3;
-struct Kb { float k1, k2, k3, k4; };
 
 template <int CAM>
 __device__ __forceinline__ Kb load_kb(const float *__restrict__ K)
 {
     if constexpr (CAM == GAGS_CAM_FISHEYE_KB) return Kb{K[9], K[10], K[11], K[12]};
     else return Kb{0.f, 0.f, 0.f, 0.f};  // (K is nine floats: nothing behind them is read)
-}
-__device__ __forceinline__ float kb_P(const Kb &c, float t) { return 1.f + t * (c.k1 + t * (c.k2 + t * (c.k3 + t * c.k4))); }
-__device__ __forceinline__ float kb_dP(const Kb &c, float t)
-{
-    return 1.f + t * (3.f * c.k1 + t * (5.f * c.k2 + t * (7.f * c.k3 + t * (9.f * c.k4))));
 }
 __device__ __forceinline__ float kb_ddg(const Kb &c, float theta, float t)
 {

@@ -328,6 +328,7 @@ def prompt_scene(gaussians, cameras, mode, depths=None, names=None, bg_color=Non
       "depth"     the ED depth of every camera (rendered here unless `depths` [C, H, W] is given) -> depth_point_grids
       "mindepth"  depthsample.depth_sample_scene -> mindepth_point_grids
       "pcd"       depth_sample_scene with the dense mapping -> sample_from_pcd(round(pcd_fraction N)) -> project_from_sampled_pcd
+    The cameras may be of any model the rasterizer renders, mixed freely (N22: depthsample.camera_rig).
     Returns {"names": [C], "point_grids": per camera a list with one [P, 2] array per layer, points (x, y) in [0, 1]^2}."""
     from . import depthsample as DS
     if mode not in MODES:

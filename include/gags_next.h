@@ -333,6 +333,35 @@ int gags_depthsample_scatter(int64_t n, int n_cams, int h, int w, const float *x
                              const float *depths, float vis_thresh, int cut_bound, const float *min_depth, float *samples,
                              void *scratch, int64_t scratch_bytes, void *stream);
 
+/* N22: the same mapping for a rig of any cameras the rasterizer renders (gags_raster.h: GAGS_CAM_PINHOLE / _ORTHO / _FISHEYE,
+ * the fisheye's distortion coefficients k1 .. k4 of GAGS_PROJ_KB), models mixed freely.  Steps 1 and 3-5 above hold for every
+ * model; only step 2 depends on the camera's model, all fp32, no FMA, IEEE division:
+ *   pinhole   step 2 above, verbatim.  No cull.
+ *   ortho     u = xc fx + cx,  v = yc fy + cy
+ *   fisheye   the quantities of the projection (gags_raster.h "GAGS_CAM_FISHEYE", "GAGS_PROJ_KB"), eps = 1e-7:
+ *               rho = sqrt(xc xc + yc yc) + eps,  theta = atan2f(rho, zc + eps),  t = theta theta,
+ *               P(t) = 1 + t (k1 + t (k2 + t (k3 + t k4))),  P'(t) = 1 + t (3 k1 + t (5 k2 + t (7 k3 + t 9 k4))),
+ *               k = (theta P(t)) / rho,  u = (fx xc) k + cx,  v = (fy yc) k + cy
+ *             zero coefficients give P = P' = 1 exactly: one code path, the plain fisheye is its zero-coefficient case.
+ *   Position culls, ortho and fisheye only: a point with !(zc >= 0.01f) (render()'s near plane; NaN included) and, for a
+ *   fisheye, one with P'(t) <= 0 (the fold, where the projection culls) is OUTSIDE, before any depth is read -- a centre the
+ *   rasterizer never drew must not agree with whatever depth lies at the pixel it would land on.
+ * The rendered depth is camera-space z for every model, so step 5 compares against zc unchanged.
+ * cam_models: a HOST array of n_cams model ids, read completely before the call returns; NULL = all pinhole; an id outside the
+ * three: GAGS_EINVAL before any launch.  radial_coeffs: a DEVICE array [n_cams, 4] or NULL (all zero); the rows of cameras
+ * that are not fisheyes are not read.  Every other argument, the limits, the error codes and n == 0 are those of the two
+ * entries above.  An all-pinhole rig (NULL or all ids 0) runs the very kernels of the entries above: the same bits.  The
+ * scratch is a little larger than theirs (a wider camera block) and does not depend on the models. */
+int64_t gags_rig_depth_scratch_bytes(int64_t n, int n_cams, int h, int w);
+int gags_rig_depth_map(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats, const float *Ks,
+                       const int32_t *cam_models, const float *radial_coeffs, const float *depths, float vis_thresh,
+                       int cut_bound, float *min_depth, int32_t *mapping, unsigned char *visible, void *scratch,
+                       int64_t scratch_bytes, void *stream);
+int gags_rig_depth_scatter(int64_t n, int n_cams, int h, int w, const float *xyz, const float *viewmats, const float *Ks,
+                           const int32_t *cam_models, const float *radial_coeffs, const float *depths, float vis_thresh,
+                           int cut_bound, const float *min_depth, float *samples, void *scratch, int64_t scratch_bytes,
+                           void *stream);
+
 /* ---- N7: the photometric loss of the RGB stage (utils/loss_utils.py:20, 158-198; utils/image_utils.py:17-19) ------------
  * 3DGS's (1 - lambda) L1 + lambda (1 - SSIM) on images of `planes` = images x channels planes of h x w pixels, one forward and
  * one backward kernel (csrc/photometric.hip).  SSIM is the reference's: an 11 x 11 zero-padded window whose weight is the

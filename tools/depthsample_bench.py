@@ -9,7 +9,12 @@ maps' memset, atomics and finalise reads (8 C H W) + samples (4 C H W) + the win
 Also the float32 restatement's host time per camera (tests/depthsample_ref.py, numpy) on --host-cams cameras, labelled
 as such and not extrapolated.  Prints one JSON line.
 
-    python tools/depthsample_bench.py [--n 1500000,4000000] [--cams 100,300] [--reps 5] [--host-cams 2]"""
+--camera-model (N22) gives every camera that model through gags_rig_depth_map / _scatter, the entries the package calls for
+every rig: "pinhole" (the default: the N6 kernels), "ortho" (137 px per unit), "fisheye" (0.9 W px per radian) or "kb" (that
+fisheye with the distortion coefficients of set A of tests/fisheye_kb_ref.py).
+
+    python tools/depthsample_bench.py [--n 1500000,4000000] [--cams 100,300] [--reps 5] [--host-cams 2]
+                                      [--camera-model {pinhole,ortho,fisheye,kb}]"""
 import argparse
 import json
 import math
@@ -42,9 +47,19 @@ def timed(fn, reps):
     return round(ts[len(ts) // 2], 3)
 
 
-def cameras(c, w=1920, h=1080):
+KB_A = (-0.0290, -0.0049, 0.0012, -0.0004)
+
+
+def cameras(c, w=1920, h=1080, model="pinhole"):
     """c cameras at the origin looking into the synthetic frustum, yaw in [-40, 40] degrees, pitch in [-10, 10]."""
     base = syn.make_camera(w, h)
+    kw = {}
+    if model == "ortho":
+        kw = dict(camera_model="ortho", K=np.array([[137.0, 0, w / 2], [0, 137.0, h / 2], [0, 0, 1]], np.float32))
+    elif model in ("fisheye", "kb"):
+        kw = dict(camera_model="fisheye", K=np.array([[0.9 * w, 0, w / 2], [0, 0.9 * w, h / 2], [0, 0, 1]], np.float32))
+        if model == "kb":
+            kw["radial_coeffs"] = KB_A
     out = []
     for k in range(c):
         yaw = math.radians(-40 + 80 * k / max(c - 1, 1))
@@ -52,7 +67,7 @@ def cameras(c, w=1920, h=1080):
         cy, sy, cp, sp = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch)
         Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
         Rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
-        out.append(Camera(Ry @ Rx, np.zeros(3), base.FoVx, base.FoVy, w, h, uid=k))
+        out.append(Camera(Ry @ Rx, np.zeros(3), base.FoVx, base.FoVy, w, h, uid=k, **kw))
     return out
 
 
@@ -62,33 +77,38 @@ def main():
     ap.add_argument("--cams", default="100,300")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-cams", type=int, default=2)
+    ap.add_argument("--camera-model", default="pinhole", choices=("pinhole", "ortho", "fisheye", "kb"))
     args = ap.parse_args()
-    res = {"tool": "depthsample_bench", "unit": "ms", "reps": args.reps, "width": 1920, "height": 1080, "runs": []}
+    res = {"tool": "depthsample_bench", "unit": "ms", "reps": args.reps, "width": 1920, "height": 1080,
+           "camera_model": args.camera_model, "runs": []}
     bg = torch.zeros(3, device="cuda")
     for n in [int(v) for v in args.n.split(",")]:
         model = syn.make_model(n, 0, 1920, 1080, seed=0, device="cuda", gen_device="cuda")
         xyz = model.get_xyz.contiguous()
         for c in [int(v) for v in args.cams.split(",")]:
-            cams = cameras(c)
-            vm, K, (h, w) = DS.camera_matrices(cams)
+            cams = cameras(c, model=args.camera_model)
+            vm, K, models, coeffs, (h, w) = DS.camera_rig(cams)
+            rig = {} if args.camera_model == "pinhole" else dict(camera_models=models, radial_coeffs=coeffs)
+            ids, _ = DS._rig(rig.get("camera_models"), coeffs if rig else None, depths=None)
             t_render = timed(lambda: DS.render_depths(model, cams, bg), max(1, min(args.reps, 3)))
             depths = DS.render_depths(model, cams, bg)
-            t_map = timed(lambda: DS.point_min_depth(xyz, vm, K, depths), args.reps)
-            md = DS.point_min_depth(xyz, vm, K, depths)
+            t_map = timed(lambda: DS.point_min_depth(xyz, vm, K, depths, **rig), args.reps)
+            md = DS.point_min_depth(xyz, vm, K, depths, **rig)
             lib = DS._lib.load()
             samples = torch.empty(c, h, w, device="cuda")
             scratch, nb = DS._scratch(lib, n, c, h, w, xyz.device)
 
             def scatter():
-                DS.check(lib.gags_depthsample_scatter(n, c, h, w, DS.ptr(xyz), DS.ptr(vm), DS.ptr(K), DS.ptr(depths), 0.25,
-                                                      0, DS.ptr(md), DS.ptr(samples), DS.ptr(scratch), nb, DS._lib.stream()),
+                DS.check(lib.gags_rig_depth_scatter(n, c, h, w, DS.ptr(xyz), DS.ptr(vm), DS.ptr(K), ids,
+                                                    DS.ptr(coeffs if rig else None), DS.ptr(depths), 0.25, 0, DS.ptr(md),
+                                                    DS.ptr(samples), DS.ptr(scratch), nb, DS._lib.stream()),
                          "scatter")
             t_scatter = timed(scatter, args.reps)
             row = {"n": n, "cams": c, "render_ms": t_render, "map_ms": t_map, "scatter_ms": t_scatter}
             dense_bytes = 9 * n * c
             if dense_bytes < 24 << 30:
-                t_dense = timed(lambda: DS.point_pixel_mapping(xyz, vm, K, depths), args.reps)
-                mapping, visible = DS.point_pixel_mapping(xyz, vm, K, depths)
+                t_dense = timed(lambda: DS.point_pixel_mapping(xyz, vm, K, depths, **rig), args.reps)
+                mapping, visible = DS.point_pixel_mapping(xyz, vm, K, depths, **rig)
                 inside_vis = int(visible.sum())
                 del mapping
                 row["dense_ms"] = t_dense
@@ -111,10 +131,10 @@ def main():
             del depths, samples, scratch, md
             torch.cuda.empty_cache()
         # the float32 restatement on the host, per camera, on a few cameras (not extrapolated)
-        if args.host_cams > 0:
+        if args.host_cams > 0 and args.camera_model == "pinhole":
             import depthsample_ref as R
             cams = cameras(args.host_cams)
-            vm, K, _ = DS.camera_matrices(cams)
+            vm, K, _, _, _ = DS.camera_rig(cams)
             depths = DS.render_depths(model, cams, bg).cpu().numpy()
             X, VM, KK = xyz.cpu().numpy(), vm.cpu().numpy(), K.cpu().numpy()
             t0 = time.perf_counter()

@@ -9,6 +9,13 @@ needed.  tests/test_scratch_layout_cpu.py compares the library under test with t
 from the commit BEFORE a change to a scratch layout, never from the change itself.  Per function the table holds a tiny
 shape, shapes that are no multiple of 64, a workload-sized shape (1.5 M Gaussians, 1920 x 1080, D = 512, ~30 M
 intersections) and every rejected case the CPU tests name.
+
+A size function that is added later (LATER) has no earlier commit to be recorded from, and the first file stays as it was
+recorded: such a function gets a fixture of its own next to it, written once by
+
+    python tools/record_scratch_bytes.py --later tests/golden
+
+and checked by the tests of the change that adds it, together with the arithmetic that ties it to an existing layout.
 """
 import json
 import os
@@ -22,6 +29,15 @@ EXTRA = ("gags_bwd_rowmap_elems", "gags_photometric_partials", "gags_segment_sta
 N, W, H, D, ISECTS, ROWS = 1_500_000, 1920, 1080, 512, 30_000_000, 9_000_000  # the workload
 HW = W * H
 I31 = (1 << 31) - 1
+
+
+DEPTH = [(1, 1, 1, 1), (1000, 2, 32, 40), (1000, 3, 32, 40), (1000, 2, 32, 32), (999, 17, 33, 41),
+         (1000, 300, H, W), (N, 300, H, W), (N, 16, H, W), (0, 2, 32, 32), (-1, 2, 32, 32),
+         (10, 0, 32, 32), (10, 2, 0, 32), (10, 2, 32, -1), (10, 2, 1 << 16, 1 << 15),
+         (I31, 2, 8, 8)]
+# added after the first file was recorded: function -> (its own fixture under tests/golden, its table)
+# (N22: gags_depthsample_scratch_bytes with a 96-byte camera block where that one has 64 bytes)
+LATER = {"gags_rig_depth_scratch_bytes": ("scratch_bytes_rig_depth.json", DEPTH)}
 
 
 def table(lib):
@@ -67,10 +83,7 @@ def table(lib):
                                             (3, 8, -2), (3, 0, 8)],
         "gags_point_relevancy_mask_scratch_bytes": kn,
         "gags_point_mask_smooth_scratch_bytes": kn,
-        "gags_depthsample_scratch_bytes": [(1, 1, 1, 1), (1000, 2, 32, 40), (1000, 3, 32, 40), (1000, 2, 32, 32), (999, 17, 33, 41),
-                                           (1000, 300, H, W), (N, 300, H, W), (N, 16, H, W), (0, 2, 32, 32), (-1, 2, 32, 32),
-                                           (10, 0, 32, 32), (10, 2, 0, 32), (10, 2, 32, -1), (10, 2, 1 << 16, 1 << 15),
-                                           (I31, 2, 8, 8)],
+        "gags_depthsample_scratch_bytes": DEPTH,
         "gags_masks_nms_scratch_bytes": [(1, 1), (5, 17 * 19), (40, 37 * 70), (63, 65), (300, HW), (cap, HW), (cap, (1 << 24) - 1),
                                          (-1, 37 * 70), (cap + 1, 37 * 70), (40, 0), (40, -5), (40, 1 << 24), (0, 37 * 70)],
         "gags_featvis_moments_scratch_bytes": [(c, p) for c in (16, 3, 8, 32, 64, 128, 512, 24, 0, -16, 1024)
@@ -88,7 +101,8 @@ def table(lib):
 
 
 def functions():
-    return sorted(k for k in _lib.SIGNATURES if k.endswith("_scratch_bytes") or k.endswith("_scratch_bytes_h16") or k in EXTRA)
+    return sorted(k for k in _lib.SIGNATURES
+                  if (k.endswith("_scratch_bytes") or k.endswith("_scratch_bytes_h16") or k in EXTRA) and k not in LATER)
 
 
 def record(lib):
@@ -98,11 +112,25 @@ def record(lib):
     return [{"fn": fn, "args": list(a), "value": int(getattr(lib, fn)(*a))} for fn in functions() for a in tab[fn]]
 
 
+def record_later(lib, fn):
+    return [{"fn": fn, "args": list(a), "value": int(getattr(lib, fn)(*a))} for a in LATER[fn][1]]
+
+
+def _write(path, rows):
+    with open(path, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--later":
+        directory = sys.argv[2] if len(sys.argv) > 2 else os.path.join("tests", "golden")
+        for fn, (name, _) in LATER.items():
+            _write(os.path.join(directory, name), record_later(_lib.load(), fn))
+            print(f"{fn} -> {os.path.join(directory, name)}")
+        return
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join("tests", "golden", "scratch_bytes.json")
     rows = record(_lib.load())
-    with open(out, "w") as f:
-        f.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
+    _write(out, rows)
     print(f"{len(rows)} entries of {len(functions())} functions -> {out}")
 
 
