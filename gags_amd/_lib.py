@@ -52,6 +52,10 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_project_bwd_cam": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # N23: intrinsics gradients: gags_project_bwd_cam's arguments, then v_K, v_coeffs behind v_viewmat
+    "gags_project_calib_partials": (_i64, [_i32]),
+    "gags_project_bwd_calib": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_scan_scratch_bytes": (_i64, [_i32]),
     "gags_cumsum_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gags_cumsum_gather_i32": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -277,7 +281,8 @@ GAGS_GEOM_F32MFMA = 32  # `flags` of gags_raster_bwd_geom: the fp32 matrix instr
 GAGS_POSE_RAW, GAGS_POSE_AA = 1, 2  # `flags` of gags_project_bwd_pose
 GAGS_CAM_PINHOLE, GAGS_CAM_ORTHO, GAGS_CAM_FISHEYE = 0, 1, 2  # `camera_model` of gags_project_fwd_cam / gags_project_bwd_cam
 GAGS_PROJ_RAW, GAGS_PROJ_AA, GAGS_PROJ_POSE = 1, 2, 4  # their `flags`
-GAGS_PROJ_KB = 32  # ... and (N21, fisheye only): K is 13 floats, the 3 x 3 matrix then the distortion coefficients k1 .. k4
+GAGS_CALIB_PARTIAL_FLOATS = 22  # floats per row of gags_project_bwd_calib's partials (N23): 12 pose, 6 K, 4 coefficients
+GAGS_PROJ_KB = 32  #... and (N21, fisheye only): K is 13 floats, the 3 x 3 matrix then the distortion coefficients k1 .. k4
 CAMERA_MODELS = {"pinhole": GAGS_CAM_PINHOLE, "ortho": GAGS_CAM_ORTHO, "fisheye": GAGS_CAM_FISHEYE}  # rasterization(camera_model=)
 GAGS_GEOM_ABSGRAD = 64  # `flags` of gags_raster_bwd_geom: columns 6, 7 of v_geo carry absgrad (rasterization(absgrad=True))
 

@@ -124,9 +124,16 @@ __device__ __forceinline__ float cam_fwd(float fx, float fy, float cx, float cy,
 
 // (v_means2d, vJ) -> vp, the cotangent of the camera-space point; v_depth (the cotangent of depths = z, when has_depth) joins
 // vp[2] where the pinhole kernel has always added it, between the means2d term and the J terms.
-template <int CAM>
+// CALIB (N23): cal[8] = this Gaussian's terms of the cotangents of (fx, cx, fy, cy, k1, k2, k3, k4), the exact derivative of
+// cam_fwd as it is written (k1 .. k4 only with GAGS_CAM_FISHEYE_KB; the others are left as they come in).  The pinhole's clamp
+// limits are functions of K -- x_pos = (1.15 W - cx) / fx, x_neg = (cx + 0.15 W) / fx -- so past the clamp, on either side,
+// J[0][2] = -(fx lim) / z does not depend on fx and d J[0][2] / d cx = 1 / z.  The fisheye's rows of J are linear in fx / fy:
+// the unscaled row is formed once, nothing is divided.  Everything CALIB adds stands behind `if constexpr`: without it the
+// bodies, and their bits, are those of before N23.
+template <int CAM, bool CALIB = false>
 __device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, const Kb &kb, float x, float y, float z, float vm2x,
-                                        float vm2y, const float (&vJ)[2][3], bool has_depth, float v_depth, float (&vp)[3])
+                                        float vm2y, const float (&vJ)[2][3], bool has_depth, float v_depth, float (&vp)[3],
+                                        float *cal = nullptr)
 {
     if constexpr (CAM == GAGS_CAM_PINHOLE) {
         const float rz = 1.f / z, rz2 = rz * rz, rz3 = rz2 * rz;
@@ -142,10 +149,24 @@ __device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, c
         if (x_in) vp[0] += -fx * rz2 * vJ[0][2]; else vp[2] += -fx * rz3 * vJ[0][2] * tx;
         if (y_in) vp[1] += -fy * rz2 * vJ[1][2]; else vp[2] += -fy * rz3 * vJ[1][2] * ty;
         vp[2] += -fx * rz2 * vJ[0][0] - fy * rz2 * vJ[1][1] + 2.f * fx * tx * rz3 * vJ[0][2] + 2.f * fy * ty * rz3 * vJ[1][2];
+        if constexpr (CALIB) {
+            cal[0] = (vm2x * x) * rz + vJ[0][0] * rz;
+            cal[1] = vm2x;
+            if (x_in) cal[0] -= (vJ[0][2] * tx) * rz2; else cal[1] += vJ[0][2] * rz;
+            cal[2] = (vm2y * y) * rz + vJ[1][1] * rz;
+            cal[3] = vm2y;
+            if (y_in) cal[2] -= (vJ[1][2] * ty) * rz2; else cal[3] += vJ[1][2] * rz;
+        }
     } else if constexpr (CAM == GAGS_CAM_ORTHO) {
         vp[0] = fx * vm2x;  // (J is constant: vJ reaches nothing)
         vp[1] = fy * vm2y;
         vp[2] = has_depth ? v_depth : 0.f;
+        if constexpr (CALIB) {
+            cal[0] = vm2x * x + vJ[0][0];
+            cal[1] = vm2x;
+            cal[2] = vm2y * y + vJ[1][1];
+            cal[3] = vm2y;
+        }
     } else if constexpr (CAM == GAGS_CAM_FISHEYE_KB) {  // the fisheye's chain below with g, dg and their three cotangents
         const float r0 = sqrtf(x * x + y * y);
         const float rho = r0 + GAGS_FISHEYE_EPS, zt = z + GAGS_FISHEYE_EPS;
@@ -185,6 +206,23 @@ __device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, c
         v_rho += -(v_b * b) / rho;
         v_s += -(v_b * b) / s;
         const float v_tb = v_gb * dg + v_dg * kb_ddg(kb, tb, tt);
+        if constexpr (CALIB) {
+            const float amb = a - b, u01 = xy * amb;  // (the rows of J without fx / fy)
+            cal[0] = vm2x * (x * k) + ((vJ[0][0] * (x2 * a + y2 * b) + vJ[0][1] * u01) + vJ[0][2] * (-x / l2 * dg));
+            cal[1] = vm2x;
+            cal[2] = vm2y * (y * k) + ((vJ[1][0] * u01 + vJ[1][1] * (y2 * a + x2 * b)) + vJ[1][2] * (-y / l2 * dg));
+            cal[3] = vm2y;
+            // k_j: g(theta) = theta (1 + sum k_j t^j), likewise g(tb); dg = 1 + sum (2 j + 1) k_j tt^j (v_dg is final here)
+            const float t = theta * theta, wg = v_g * theta, wgb = v_gb * tb;
+            float pt = t, ptt = tt;
+            cal[4] = (wg * pt + wgb * ptt) + (3.f * v_dg) * ptt;
+            pt *= t; ptt *= tt;
+            cal[5] = (wg * pt + wgb * ptt) + (5.f * v_dg) * ptt;
+            pt *= t; ptt *= tt;
+            cal[6] = (wg * pt + wgb * ptt) + (7.f * v_dg) * ptt;
+            pt *= t; ptt *= tt;
+            cal[7] = (wg * pt + wgb * ptt) + (9.f * v_dg) * ptt;
+        }
         const float hb = rho * rho + z2;
         v_rho += v_tb * z / hb;
         vz += -(v_tb * rho) / hb;
@@ -229,6 +267,13 @@ __device__ __forceinline__ void cam_bwd(float fx, float fy, const CamLim &lim, c
         const float v_a = (g00 * x2 + g11 * y2) + gx * xy;
         const float v_b = (g00 * y2 + g11 * x2) - gx * xy;
         const float v_xy = gx * (a - b);
+        if constexpr (CALIB) {
+            const float amb = a - b, u01 = xy * amb;  // (the rows of J without fx / fy)
+            cal[0] = vm2x * (x * k) + ((vJ[0][0] * (x2 * a + y2 * b) + vJ[0][1] * u01) + vJ[0][2] * (-x / l2));
+            cal[1] = vm2x;
+            cal[2] = vm2y * (y * k) + ((vJ[1][0] * u01 + vJ[1][1] * (y2 * a + x2 * b)) + vJ[1][2] * (-y / l2));
+            cal[3] = vm2y;
+        }
         vx += -g02 / l2;
         vy += -g12 / l2;
         float v_l2 = (g02 * x + g12 * y) / (l2 * l2);
@@ -523,8 +568,17 @@ namespace {
         if constexpr (POSE) break;     \
         else return;                   \
     }
-template <bool RAW, bool AA, bool POSE, int CAM>
-__global__ __launch_bounds__(256) void project_bwd_kernel(
+// MODE (N23): none / pose / pose + calib.  GAGS_PBWD_CALIB is the pose kernel -- same structure, the twelve pose terms formed by
+// the very same operations -- with eight more sums on the way: the cotangents of (fx, cx, fy, cy) and, with GAGS_CAM_FISHEYE_KB,
+// of (k1 .. k4), per Gaussian from cam_bwd<CAM, true>, exact zeros for a lane past N or a culled Gaussian.  First stage as the
+// pose's; per workgroup one row (fx, 0, cx, 0, fy, cy) into the table behind the pose rows and, with the coefficients, one row
+// (k1 .. k4) into the table behind that: pose_partials is then [rows, 12] [rows, 6] [rows, 4], rows = gridDim.x.
+constexpr int GAGS_PBWD_NONE = 0, GAGS_PBWD_POSE = 1, GAGS_PBWD_CALIB = 2;
+// (The calib kernels ask for three waves per SIMD, at most 168 registers: the compiler meets it without scratch, where it takes
+// 176 - 178 for the fisheye with coefficients when left alone.  A second launch-bound argument of 1 asks for nothing: the
+// kernels of before N23 compile to the instructions they had.)
+template <bool RAW, bool AA, int MODE, int CAM>
+__global__ __launch_bounds__(256, MODE == GAGS_PBWD_CALIB ? 3 : 1) void project_bwd_kernel(
     int N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmat, const float *__restrict__ Kmat, int width, int height, float eps2d,
     const int32_t *__restrict__ radii, const float *__restrict__ v_means2d, const float *__restrict__ v_depths,
@@ -533,9 +587,12 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     const float *__restrict__ v_opacities, float *__restrict__ v_opacity_logits, const float *__restrict__ v_compensations,
     float *__restrict__ pose_partials)
 {
+    constexpr bool POSE = MODE != GAGS_PBWD_NONE, CALIB = MODE == GAGS_PBWD_CALIB;
     const int i = blockIdx.x * 256 + threadIdx.x;
     float pose[12];
     if constexpr (POSE) { _Pragma("unroll") for (int k = 0; k < 12; ++k) pose[k] = 0.f; }
+    float cal[CALIB ? 8 : 1];
+    if constexpr (CALIB) { _Pragma("unroll") for (int k = 0; k < 8; ++k) cal[k] = 0.f; }
     do {
     if (i >= N) GAGS_PBWD_LEAVE()
     const bool w_means = !POSE || v_means, w_quats = !POSE || v_quats, w_scales = !POSE || v_scales;
@@ -642,7 +699,10 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         /* ---- 3. J and mean2d/depth -> camera-space point ---- */
         const float vm2x = v_means2d[2 * i], vm2y = v_means2d[2 * i + 1];
         float vp[3];
-        cam_bwd<CAM>(fx, fy, lim, kb, x, y, z, vm2x, vm2y, vJ, v_depths != nullptr, v_depths ? v_depths[i] : 0.f, vp);
+        if constexpr (CALIB)
+            cam_bwd<CAM, true>(fx, fy, lim, kb, x, y, z, vm2x, vm2y, vJ, v_depths != nullptr, v_depths ? v_depths[i] : 0.f, vp, cal);
+        else
+            cam_bwd<CAM>(fx, fy, lim, kb, x, y, z, vm2x, vm2y, vJ, v_depths != nullptr, v_depths ? v_depths[i] : 0.f, vp);
         if constexpr (POSE) {
             _Pragma("unroll") for (int r = 0; r < 3; ++r) {
                 _Pragma("unroll") for (int c = 0; c < 3; ++c)
@@ -693,15 +753,37 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     } while (0);
 #undef GAGS_PBWD_LEAVE
     if constexpr (POSE) {
-        __shared__ double red[4][12];
+        __shared__ double red[4][CALIB ? 20 : 12];
         _Pragma("unroll") for (int k = 0; k < 12; ++k) {
             const float w = gags_wave_sum(pose[k]);
             if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = (double)w;
+        }
+        if constexpr (CALIB) {
+            _Pragma("unroll") for (int k = 0; k < (CAM == GAGS_CAM_FISHEYE_KB ? 8 : 4); ++k) {
+                const float w = gags_wave_sum(cal[k]);
+                if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][12 + k] = (double)w;
+            }
         }
         __syncthreads();
         if (threadIdx.x < 12) {
             const int k = threadIdx.x;
             pose_partials[(int64_t)blockIdx.x * 12 + k] = (float)(((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]);
+        }
+        if constexpr (CALIB) {
+            const int64_t rows = gridDim.x;
+            const int c = (int)threadIdx.x - 64;  // (the second wave: columns 0 .. 5 of the K row, 6 .. 9 the coefficients)
+            if (c >= 0 && c < 6) {
+                const int k = c == 0 ? 12 : c == 2 ? 13 : c == 4 ? 14 : c == 5 ? 15 : -1;  // (fx, 0, cx, 0, fy, cy)
+                pose_partials[rows * 12 + (int64_t)blockIdx.x * 6 + c] =
+                    k < 0 ? 0.f : (float)(((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]);
+            }
+            if constexpr (CAM == GAGS_CAM_FISHEYE_KB) {
+                if (c >= 6 && c < 10) {
+                    const int k = 10 + c;
+                    pose_partials[rows * 18 + (int64_t)blockIdx.x * 4 + (c - 6)] =
+                        (float)(((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]);
+                }
+            }
         }
     }
 }
@@ -730,6 +812,40 @@ __global__ __launch_bounds__(256) void colsum_kernel(int64_t n_rows, int k, cons
     if (t < n_out) out[t] = t < k ? (float)((double)sign * red[0][t]) : 0.f;
 }
 
+// N23's second stage in ONE launch: the column sums of the three tables of a calib partials buffer -- [n_rows, 12] pose,
+// [n_rows, 6] = (fx, 0, cx, 0, fy, cy), [n_rows, 4] coefficients -- each column summed exactly as colsum_kernel sums it (the same
+// rows per thread in the same order, the same pairwise fold, in double), so that v_viewmat has the pose entry's bits.
+// v_viewmat[16] (row 3 zeros) and v_coeffs[4] are summed and written only where given; v_K[9] always (entries 6 .. 8 zeros).
+constexpr int GAGS_CALIB_COLS = 22;
+__global__ __launch_bounds__(256) void calib_colsum_kernel(int64_t n_rows, const float *__restrict__ partials,
+                                                           float *__restrict__ v_viewmat, float *__restrict__ v_K,
+                                                           float *__restrict__ v_coeffs)
+{
+    __shared__ double red[256][GAGS_CALIB_COLS];
+    const int t = threadIdx.x;
+    const float *pose = partials, *kt = partials + n_rows * 12, *ct = partials + n_rows * 18;
+    double acc[GAGS_CALIB_COLS];
+    _Pragma("unroll") for (int c = 0; c < GAGS_CALIB_COLS; ++c) acc[c] = 0.0;
+    for (int64_t r = t; r < n_rows; r += 256) {
+        if (v_viewmat) { _Pragma("unroll") for (int c = 0; c < 12; ++c) acc[c] += (double)pose[r * 12 + c]; }
+        _Pragma("unroll") for (int c = 0; c < 6; ++c) acc[12 + c] += (double)kt[r * 6 + c];
+        if (v_coeffs) { _Pragma("unroll") for (int c = 0; c < 4; ++c) acc[18 + c] += (double)ct[r * 4 + c]; }
+    }
+    _Pragma("unroll") for (int c = 0; c < GAGS_CALIB_COLS; ++c) red[t][c] = acc[c];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { _Pragma("unroll") for (int c = 0; c < GAGS_CALIB_COLS; ++c) red[t][c] += red[t + s][c]; }
+        __syncthreads();
+    }
+    if (t < 16) {
+        if (v_viewmat) v_viewmat[t] = t < 12 ? (float)red[0][t] : 0.f;
+    } else if (t >= 64 && t < 64 + 9) {
+        v_K[t - 64] = t - 64 < 6 ? (float)red[0][12 + (t - 64)] : 0.f;
+    } else if (t >= 128 && t < 128 + 4) {
+        if (v_coeffs) v_coeffs[t - 128] = (float)red[0][18 + (t - 128)];
+    }
+}
+
 }  // namespace
 
 namespace {
@@ -747,7 +863,7 @@ int project_bwd_launch(int n, const float *means, const float *quats, const floa
     if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics || !v_means || !v_quats || !v_scales)
         return GAGS_EINVAL;
     if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
-    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, false, CAM>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
+    hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, GAGS_PBWD_NONE, CAM>), dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, means,
                        quats, scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats,
                        v_scales, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, nullptr);
     GAGS_CHECK_LAUNCH();
@@ -774,13 +890,40 @@ int project_bwd_pose_launch(int n, const float *means, const float *quats, const
     if (n > 0) {
         if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics) return GAGS_EINVAL;
         if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
-        hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, true, CAM>), dim3((unsigned)rows), dim3(256), 0, st, n, means, quats, scales,
+        hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, GAGS_PBWD_POSE, CAM>), dim3((unsigned)rows), dim3(256), 0, st, n, means, quats, scales,
                            viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats, v_scales,
                            opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, partials);
         GAGS_CHECK_LAUNCH();
     }
     // second stage: the rows of `partials` in row order; entries 12 .. 15 (row 3 of the 4 x 4) are written as zeros
     return colsum_launch(rows, 12, partials, 1.0f, v_viewmat, 16, st);
+}
+
+// N23: the pose launch with the calibration sums.  partials: [rows, 12] (pose), [rows, 6] (K), [rows, 4] (coefficients), as the
+// kernel lays them out; second stage: calib_colsum_kernel, one launch -- the pose rows only when v_viewmat is asked for, the K
+// rows straight into the row-major 3 x 3 (entries 6 .. 8 written as zeros, 1 and 3 summed from zeros), the coefficient rows with
+// GAGS_CAM_FISHEYE_KB.
+template <bool RAW, bool AA, int CAM>
+int project_bwd_calib_launch(int n, const float *means, const float *quats, const float *scales, const float *opacity_logit,
+                             float scaling_modifier, const float *viewmat, const float *K, int width, int height, float eps2d,
+                             const int32_t *radii, const float *v_means2d, const float *v_depths, const float *v_conics,
+                             const float *v_opacities, const float *v_compensations, float *v_means, float *v_quats,
+                             float *v_scales, float *v_opacity_logit, float *v_viewmat, float *v_K, float *v_coeffs,
+                             float *partials, hipStream_t st)
+{
+    const int64_t rows = n > 0 ? gags_project_calib_partials(n) : 0;
+    if (n > 0) {
+        if (!means || !quats || !scales || !viewmat || !K || !radii || !v_means2d || !v_conics) return GAGS_EINVAL;
+        if (RAW && (v_opacity_logit || (AA && v_opacities)) && !opacity_logit) return GAGS_EINVAL;
+        hipLaunchKernelGGL((project_bwd_kernel<RAW, AA, GAGS_PBWD_CALIB, CAM>), dim3((unsigned)rows), dim3(256), 0, st, n, means, quats,
+                           scales, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_means, v_quats,
+                           v_scales, opacity_logit, scaling_modifier, v_opacities, v_opacity_logit, v_compensations, partials);
+        GAGS_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(calib_colsum_kernel, dim3(1), dim3(256), 0, st, rows, partials, v_viewmat, v_K,
+                       CAM == GAGS_CAM_FISHEYE_KB ? v_coeffs : nullptr);
+    GAGS_CHECK_LAUNCH();
+    return GAGS_OK;
 }
 
 }  // namespace
@@ -933,6 +1076,40 @@ extern "C" int gags_project_bwd_cam(int camera_model, int flags, int n, const fl
                 n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
                 v_depths, v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit, stream);
     }, raw, aa, pose);
+}
+
+// ---- N23: intrinsics gradients ----------------------------------------------------------------------------------------------
+
+extern "C" int64_t gags_project_calib_partials(int n) { return gags_project_pose_partials(n); }
+
+extern "C" int gags_project_bwd_calib(int camera_model, int flags, int n, const float *means, const float *quats,
+                                      const float *scales, const float *opacity_logit, float scaling_modifier, const float *viewmat,
+                                      const float *K, int width, int height, float eps2d, const int32_t *radii,
+                                      const float *v_means2d, const float *v_depths, const float *v_conics,
+                                      const float *v_opacities, const float *v_compensations, float *v_means, float *v_quats,
+                                      float *v_scales, float *v_opacity_logit, float *v_viewmat, float *v_K, float *v_coeffs,
+                                      float *partials, int64_t partials_bytes, void *stream)
+{
+    GAGS_CLEAR_ERR();
+    if (camera_model < GAGS_CAM_PINHOLE || camera_model > GAGS_CAM_FISHEYE ||
+        (flags & ~(GAGS_PROJ_RAW | GAGS_PROJ_AA | GAGS_PROJ_POSE | GAGS_PROJ_KB)))
+        return GAGS_EINVAL;
+    const bool raw = flags & GAGS_PROJ_RAW, aa = flags & GAGS_PROJ_AA, pose = flags & GAGS_PROJ_POSE, kb = flags & GAGS_PROJ_KB;
+    if (kb && camera_model != GAGS_CAM_FISHEYE) return GAGS_EINVAL;
+    if (n < 0 || width <= 0 || height <= 0) return GAGS_EINVAL;
+    // (a short partials buffer would be written out of bounds: refused before anything is launched)
+    if (!v_K || (kb && !v_coeffs) || (pose && !v_viewmat) || !partials ||
+        partials_bytes < gags_project_calib_partials(n) * GAGS_CALIB_PARTIAL_FLOATS * (int64_t)sizeof(float))
+        return GAGS_EINVAL;
+    if (!raw) { opacity_logit = nullptr; scaling_modifier = 1.0f; v_opacities = nullptr; v_opacity_logit = nullptr; }
+    if (raw || !aa) v_compensations = nullptr;
+    if (!pose) v_viewmat = nullptr;  // (not asked for: not stored)
+    return with_camera(camera_model, kb, [&](auto CAM, auto RAW, auto AA) {
+        return project_bwd_calib_launch<RAW.value, AA.value, CAM.value>(
+            n, means, quats, scales, opacity_logit, scaling_modifier, viewmat, K, width, height, eps2d, radii, v_means2d, v_depths,
+            v_conics, v_opacities, v_compensations, v_means, v_quats, v_scales, v_opacity_logit, v_viewmat, v_K, v_coeffs, partials,
+            (hipStream_t)stream);
+    }, raw, aa);
 }
 
 extern "C" int gags_colsum_f32(int64_t n_rows, int k, const float *table, float sign, float *out, int n_out, void *stream)

@@ -83,6 +83,35 @@ def _intrinsics_kb(viewpoint_camera, device, cache):
     return block[:9].view(3, 3), block[9:]
 
 
+def _trainable(t):
+    return torch.is_tensor(t) and t.requires_grad
+
+
+def _intrinsics_trainable(viewpoint_camera, device):
+    """(K [3,3], radial_coeffs [4] or None) of a camera whose K or radial_coeffs is a tensor that requires grad (N23): the
+    tensors are handed through as they are, so that rasterization()'s gradient reaches whatever they were computed from
+    (pose.IntrinsicsDelta) -- no cache entry, no host readback.  They must already be what the kernels read: float32, on the
+    scene's device, [3,3] / [4]; anything else is a ValueError before any launch.  The one of the two that does not require
+    grad may be anything torch.as_tensor takes: it is brought to that form here."""
+    K = getattr(viewpoint_camera, "K", None)
+    coeffs = getattr(viewpoint_camera, "radial_coeffs", None)
+    if K is None:
+        raise ValueError("a camera with trainable intrinsics needs an explicit K [3,3] attribute")
+
+    def as_given(t, shape, name):
+        if _trainable(t):
+            if t.device != device or t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise ValueError(f"a camera's trainable {name} must be a float32 tensor {list(shape)} on {device}, not "
+                                 f"{t.dtype} {list(t.shape)} on {t.device}")
+            return t
+        t = torch.as_tensor(t).detach()
+        if t.numel() != shape[0] * (shape[1] if len(shape) > 1 else 1):
+            raise ValueError("a camera's K must be [3,3] and its radial_coeffs [4]")
+        return t.to(device=device, dtype=torch.float32).reshape(shape)
+
+    return as_given(K, (3, 3), "K"), None if coeffs is None else as_given(coeffs, (4,), "radial_coeffs")
+
+
 # R2 folded into R4 (SURVEY 8a: the getters are "4 elementwise kernels/iter over N (fusable into projection)"): when `pc`
 # stores its parameters the way scene/gaussian_model.py:48-61 does and activates them the way :36-42 does (exp, sigmoid,
 # F.normalize), render() hands the STORED tensors to the projection kernel, which applies those getters itself -- bit for
@@ -135,11 +164,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
     compensation; `viewspace_points.absgrad` after backward(), which densify.accumulate(..., absgrad=True) reads).
     The camera model (N20) is read from the camera: `viewpoint_camera.camera_model` ("pinhole" when absent, "ortho", "fisheye"),
     and `viewpoint_camera.K` [3,3], when present, replaces the FoV-derived intrinsics; a non-pinhole camera must carry one.  `viewpoint_camera.radial_coeffs` (N21; None when
-    absent): a fisheye camera's distortion coefficients (k1 .. k4), resident on the device next to K after the first render."""
+    absent): a fisheye camera's distortion coefficients (k1 .. k4), resident on the device next to K after the first render.
+    A `K` or `radial_coeffs` that is a tensor requiring grad (N23; pose.IntrinsicsDelta.camera makes such cameras) is handed to
+    rasterization() as it is -- float32, on the scene's device, [3,3] / [4], else ValueError -- and gets its gradient; no cache
+    entry is made for such a camera."""
     rctx = context if context is not None else default_context()
     means3D = pc.get_xyz
     radial_coeffs = None
-    if getattr(viewpoint_camera, "radial_coeffs", None) is not None:
+    if _trainable(getattr(viewpoint_camera, "K", None)) or _trainable(getattr(viewpoint_camera, "radial_coeffs", None)):
+        K, radial_coeffs = _intrinsics_trainable(viewpoint_camera, means3D.device)  # (N23)
+    elif getattr(viewpoint_camera, "radial_coeffs", None) is not None:
         K, radial_coeffs = _intrinsics_kb(viewpoint_camera, means3D.device, rctx.k_cache)
     else:
         K = _intrinsics(viewpoint_camera, means3D.device, rctx.k_cache)

@@ -57,11 +57,36 @@ def _project_bwd(lib, cam, flags, means, quats, scales, logit, modifier, viewmat
     return v_means, v_quats, v_scales, v_logit, v_viewmat
 
 
+def _project_bwd_calib(lib, cam, flags, means, quats, scales, logit, modifier, viewmat, K, width, height, eps2d, radii, v_means2d,
+                       v_depths, v_conics, v_opac, v_comp, want, pose):
+    """gags_project_bwd_calib (N23): _project_bwd with the cotangent of K on the way -- the only call of that entry in the
+    package.  Returns _project_bwd's five and v_K, shaped like the K the projection was given: [3,3], or with GAGS_PROJ_KB the
+    13-float block [v_K row-major, v_k1 .. v_k4].  Every scene gradient may be unwanted, with or without the pose."""
+    n = means.shape[0]
+    dev = means.device
+    v_means, v_quats, v_scales, v_logit = (torch.empty(n, *shape, device=dev) if w else None
+                                           for w, shape in zip(want, ((3,), (4,), (3,), ())))
+    kb = bool(flags & _lib.GAGS_PROJ_KB)
+    v_block = torch.empty(13 if kb else 9, device=dev)
+    v_viewmat = None
+    if pose:
+        flags |= _lib.GAGS_PROJ_POSE
+        v_viewmat = torch.empty(4, 4, device=dev)
+    partials = torch.empty(lib.gags_project_calib_partials(n), _lib.GAGS_CALIB_PARTIAL_FLOATS, device=dev)
+    check(lib.gags_project_bwd_calib(cam, flags, n, ptr(means), ptr(quats), ptr(scales), ptr(logit), modifier, ptr(viewmat), ptr(K),
+                                     width, height, eps2d, ptr(radii), ptr(v_means2d), ptr(v_depths), ptr(v_conics), ptr(v_opac),
+                                     ptr(v_comp), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_logit), ptr(v_viewmat),
+                                     ptr(v_block), ptr(v_block[9:]) if kb else None, ptr(partials), partials.numel() * 4,
+                                     _lib.stream()), "gags_project_bwd_calib")
+    return v_means, v_quats, v_scales, v_logit, v_viewmat, (v_block if kb else v_block.view(3, 3))
+
+
 class _Project(torch.autograd.Function):
     """K1 + K4 forward, K2 backward.  aa (rasterize_mode "antialiased"): one more output, the compensations [N], and its
     cotangent in the backward; the caller multiplies them into the opacities.  cam (N20): _lib.GAGS_CAM_*; every model, the
     pinhole (0) included, goes through _project_fwd / _project_bwd.  kb (N21, fisheye only): K is the 13-float block, the
-    matrix then the distortion coefficients (GAGS_PROJ_KB); it gets no gradient, as K gets none."""
+    matrix then the distortion coefficients (GAGS_PROJ_KB).  A K that requires grad (N23) gets its gradient, shaped like it,
+    from _project_bwd_calib; otherwise the backward is _project_bwd's, as before."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, viewmat, K, width, height, eps2d, near, far, radius_clip, aa=False, cam=0, kb=False):
@@ -91,11 +116,15 @@ class _Project(torch.autograd.Function):
         v_comp = None if (not aa or v_comp is None) else _c(v_comp)
         # the pose: one more output of the same kernel, and only the scene gradients that are wanted
         pose = ctx.needs_input_grad[3]
-        want = tuple(ctx.needs_input_grad[:3]) if pose else (True, True, True)
-        v_means, v_quats, v_scales, _, v_viewmat = _project_bwd(
-            lib, cam, _proj_flags(False, aa, kb), means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii, v_means2d,
-            v_depths, v_conics, None, v_comp, want + (False,), pose)
-        return v_means, v_quats, v_scales, v_viewmat, None, None, None, None, None, None, None, None, None, None
+        args = (lib, cam, _proj_flags(False, aa, kb), means, quats, scales, None, 1.0, viewmat, K, width, height, eps2d, radii,
+                v_means2d, v_depths, v_conics, None, v_comp)
+        v_K = None
+        if ctx.needs_input_grad[4]:  # (N23: the intrinsics too; the calib entry, like the pose's, stores only what is wanted)
+            v_means, v_quats, v_scales, _, v_viewmat, v_K = _project_bwd_calib(*args, tuple(ctx.needs_input_grad[:3]) + (False,), pose)
+        else:
+            want = tuple(ctx.needs_input_grad[:3]) if pose else (True, True, True)
+            v_means, v_quats, v_scales, _, v_viewmat = _project_bwd(*args, want + (False,), pose)
+        return v_means, v_quats, v_scales, v_viewmat, v_K, None, None, None, None, None, None, None, None, None
 
 
 class _ProjectRaw(torch.autograd.Function):
@@ -140,11 +169,15 @@ class _ProjectRaw(torch.autograd.Function):
         v_depths = None if v_depths is None else _c(v_depths)
         v_opac = None if v_opac is None else _c(v_opac)
         pose = ctx.needs_input_grad[4]  # (see _Project.backward)
-        want = tuple(ctx.needs_input_grad[:4]) if pose else (True, True, True, ctx.needs_input_grad[3])
-        v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd(
-            lib, cam, _proj_flags(True, aa, kb), means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d, radii,
-            v_means2d, v_depths, v_conics, v_opac, None, want, pose)
-        return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, None, None, None, None,
+        args = (lib, cam, _proj_flags(True, aa, kb), means, rotation, scaling_log, logit, modifier, viewmat, K, width, height, eps2d,
+                radii, v_means2d, v_depths, v_conics, v_opac, None)
+        v_K = None
+        if ctx.needs_input_grad[5]:
+            v_means, v_rot, v_scal, v_logit, v_viewmat, v_K = _project_bwd_calib(*args, tuple(ctx.needs_input_grad[:4]), pose)
+        else:
+            want = tuple(ctx.needs_input_grad[:4]) if pose else (True, True, True, ctx.needs_input_grad[3])
+            v_means, v_rot, v_scal, v_logit, v_viewmat = _project_bwd(*args, want, pose)
+        return (v_means, v_rot, v_scal, None if v_logit is None else v_logit.reshape(oshape), v_viewmat, v_K, None, None, None,
                 None, None, None, None, None, None, None, None)
 
 

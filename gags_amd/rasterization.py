@@ -52,7 +52,8 @@ def _need_cuda(*ts):
                                f"cuda:{cur}; one process per GPU, torch.cuda.set_device(local_rank) first")
 
 
-def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh, render_mode, raw_params, aa=False):
+def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh, render_mode, raw_params, aa=False,
+                 radial_coeffs=None):
     """What _Rasterize will be handed, known before anything runs: (d, f16, needs) = the final channel count (after SH
     evaluation and the depth channel of RGB+D / RGB+ED), whether the final table is fp16 (only a table passed through as it
     is), and which of (means2d, conics, colors, opacities, backgrounds) will require grad -- autograd's own rule: an output
@@ -60,7 +61,7 @@ def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrou
     against the tensors themselves before it rasterizes.  aa: the opacities are multiplied by the projection's compensations."""
     def rg(*ts):
         return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
-    proj = rg(means, quats, scales, viewmats, Ks) or (raw_params and rg(opacities))  # (means2d, conics, depths)
+    proj = rg(means, quats, scales, viewmats, Ks, radial_coeffs) or (raw_params and rg(opacities))  # (means2d, conics, depths)
     v_opac = proj if raw_params else (rg(opacities) or (aa and proj))
     if render_mode in ("D", "ED"):
         return 1, False, (proj, proj, proj, v_opac, False)
@@ -73,7 +74,11 @@ def _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrou
 
 def _kb_block(K, coeffs):
     """The 13 floats GAGS_PROJ_KB reads, [K row-major, k1 .. k4] (N21).  When K [3,3] and coeffs already lie so in memory
-    (render() keeps the block in its context's k_cache and hands over two views of it) that memory is the block: no launch."""
+    (render() keeps the block in its context's k_cache and hands over two views of it) that memory is the block: no launch.
+    When K or coeffs requires grad (N23) the block is a torch.cat of the two, not detached: autograd splits the block's
+    13-float gradient into Ks.grad and radial_coeffs.grad."""
+    if torch.is_grad_enabled() and (K.requires_grad or coeffs.requires_grad):
+        return torch.cat([K.reshape(9).float(), coeffs.reshape(4)])
     K, c = K.detach(), coeffs.detach().reshape(4)
     if (K.dtype == torch.float32 and K.is_contiguous() and c.is_contiguous() and K.device == c.device
             and K.untyped_storage().data_ptr() == c.untyped_storage().data_ptr() and c.storage_offset() == K.storage_offset() + 9):
@@ -111,8 +116,13 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     projection backward produces it on the way (GAGS_PROJ_POSE, a deterministic sum over N, row 3 exactly zero), and the
     SH view direction reaches it through campos = inverse(viewmat)[:3, 3], as in gsplat (torch's backward of the 4 x 4 inverse:
     with sh_degree row 3 gets what that puts there).  Scene tensors that need no gradient
-    get none computed (pose refinement against a frozen scene).  Ks gets NO gradient, as in gsplat.  With viewmats not
-    requiring grad nothing changes: same launches, same bits.
+    get none computed (pose refinement against a frozen scene).  With viewmats not requiring grad nothing changes: same
+    launches, same bits.
+    Ks.requires_grad / radial_coeffs.requires_grad (N23): after backward(), Ks.grad [1,3,3] holds the
+    cotangents of fx, fy, cx, cy (exact zeros in the five constant entries) and radial_coeffs.grad (shaped as given) those of
+    k1 .. k4: the exact derivative of the projection as it is written, the culls not differentiated, a deterministic sum over
+    N (gags_project_bwd_calib: the pose kernel with eight more sums; it composes with viewmats.requires_grad and with frozen
+    scene tensors).  With neither requiring grad nothing changes: the same two projection entries, same launches, same bits.
     camera_model (N20): "pinhole", "ortho" (means2d = (fx x + cx, fy y + cy); fx, fy pixels per world unit)
     or "fisheye" (equidistant, distortion coefficients through radial_coeffs; z < near_plane is still culled, so the field of view stays below
     180 degrees).  Only the projection kernels differ: every model, the pinhole included, goes through the flagged pair
@@ -123,8 +133,9 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     model / COLMAP's OPENCV_FISHEYE, theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), a float32 tensor
     [4] or [1,4] on the GPU.  They reach the projection kernels as 13 floats [K, k1 .. k4] behind GAGS_PROJ_KB and go through
     the same linearisation (cov2d = J Sc J^T) as every model; a Gaussian past the angle where theta_d stops growing is culled;
-    they get no gradient, as Ks gets none.  The block is built on the device with one copy kernel -- unless Ks[0] and
-    radial_coeffs already lie so in memory, as the views render() hands over do.  None: the call without the argument, same
+    they get a gradient when they require one (N23, above).  The block is built on the device with one copy kernel -- unless
+    Ks[0] and radial_coeffs already lie so in memory, as the views render() hands over do (and neither requires grad: then the
+    block is a torch.cat autograd can split).  None: the call without the argument, same
     launches, flags and bits.  info["radial_coeffs"] repeats the tensor (or None).
     absgrad=True: after backward(), info["means2d"].absgrad is the [1,N,2] sum over pixels of the absolute per-pixel
     screen-space gradients (AbsGS), overwritten by each backward; set only where a geometry gradient is produced."""
@@ -162,8 +173,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
 
     # the final channel count -- after SH evaluation and the depth channel of RGB+D / RGB+ED -- and with it the route, once
     d, f16, needs = _table_ahead(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, sh_degree is not None,
-                                 render_mode, raw_params, aa)
-    route = _route(n, d, f16, needs, int(raster_flags), profiler.ENABLED, rctx.capacity_mode, rctx.early_rowmap,
+                                 render_mode, raw_params, aa, radial_coeffs=radial_coeffs)
+    route =_route(n, d, f16, needs, int(raster_flags), profiler.ENABLED, rctx.capacity_mode, rctx.early_rowmap,
                    rctx.overlap_zero_fill, rctx.grad_range_hook is not None, rctx.trim_lists, absgrad=absgrad)
     _check_absgrad_route(route, d)  # (before any launch, and before the tensors are looked at: plain values decide it)
     _need_cuda(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, radial_coeffs)

@@ -153,7 +153,7 @@ int gags_device_count(void);
  *   maps that way; every other cull is shared and unchanged.  The backward is the exact derivative of this forward: the
  *   cotangents v_g (from g(theta) / rho), v_gb (from b) and v_dg (from a and the third column) return through
  *   v_theta += v_g g'(theta) and v_tb += v_gb g'(tb) + v_dg g''(tb), then the fisheye's chain.  K and the coefficients get no
- *   gradient.  POSE as for every model.
+ *   gradient from this entry (since N23: gags_project_bwd_calib, below).  POSE as for every model.
  *
  * GAGS_EINVAL before any launch: an unknown camera_model, unknown flag bits, GAGS_PROJ_KB with a camera_model other than
  * GAGS_CAM_FISHEYE, n < 0 (before any pointer is looked at), width or height <= 0, a missing pointer, with POSE a NULL
@@ -178,6 +178,44 @@ int gags_project_bwd_cam(int camera_model, int flags, int n, const float *means,
                          const float *v_depths, const float *v_conics, const float *v_opacities,
                          const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
                          float *v_opacity_logit, float *v_viewmat, float *partials, int64_t partials_bytes, void *stream);
+
+/* N23: the intrinsics' gradients.  gags_project_bwd_calib is gags_project_bwd_cam -- its argument list, its variants (flags:
+ * GAGS_PROJ_RAW | GAGS_PROJ_AA | GAGS_PROJ_POSE | GAGS_PROJ_KB), its scene gradients and, with POSE, its v_viewmat, bit for
+ * bit -- with the cotangent of K and of the distortion coefficients on the way.  gags_project_bwd_cam itself has no flag for
+ * it and is unchanged.
+ *   v_K[9] (overwritten): d loss / d K, row-major 3 x 3; the entries of fx, cx, fy, cy, and exact zeros in the five others.
+ *   v_coeffs[4] (overwritten; required with GAGS_PROJ_KB, neither read nor written without): d loss / d (k1, k2, k3, k4).
+ * The rule.  The cotangent is the exact derivative of the projection forward as it is written above, summed over the
+ * Gaussians with radii > 0; a culled Gaussian contributes exact zeros.  The culls, radii and tile decisions are not
+ * differentiated (nowhere are they).  With vm2 the cotangent of means2d, vJ that of J (the antialiased compensation reaches K
+ * through vJ; v_depths does not depend on K), rz = 1 / z, the y row mirroring the x row:
+ *   every model      v_cx += vm2x.
+ *   GAGS_CAM_PINHOLE v_fx += vm2x x rz + vJ[0][0] rz - [x inside the clamp] vJ[0][2] tx rz^2.  The clamp limits are functions
+ *                    of K, x_pos = (1.15 W - cx) / fx and x_neg = (cx + 0.15 W) / fx, so past the clamp J[0][2] = -(fx lim) / z
+ *                    does not depend on fx, and v_cx += vJ[0][2] rz there, on either side: the derivative of the code as written.
+ *   GAGS_CAM_ORTHO   v_fx += vm2x x + vJ[0][0].
+ *   GAGS_CAM_FISHEYE (with or without KB) row 0 of J is linear in fx: v_fx += vm2x (x k) + sum_c vJ[0][c] (J[0][c] / fx), k =
+ *                    g(theta) / rho, the unscaled row formed once, nothing divided.
+ *   GAGS_PROJ_KB     with t = theta^2, tt = tb^2 and the backward's v_g, v_gb, v_dg (v_dg after both of its contributions), for
+ *                    j = 1 .. 4:  v_kj += v_g theta t^j + v_gb tb tt^j + v_dg (2 j + 1) tt^j, the powers by successive
+ *                    multiplication.  They do not vanish at k1 .. k4 = 0: a calibration can start from the plain fisheye.
+ * The sums over N are the pose's: a wave sum per term, the four waves of a workgroup in double, one row per workgroup, then
+ * the column sums of the rows in gags_colsum_f32's fixed order (one launch for all of them); no atomics, the same bits from run
+ * to run.  partials:
+ * gags_project_calib_partials(n) rows of GAGS_CALIB_PARTIAL_FLOATS floats (12 pose, 6 K, 4 coefficients), partials_bytes >=
+ * rows * GAGS_CALIB_PARTIAL_FLOATS * 4.  The kernel always runs in the pose kernel's structure; v_viewmat is stored only with
+ * GAGS_PROJ_POSE (else ignored).  v_means, v_quats, v_scales, v_opacity_logit may each be NULL (not wanted: not stored).
+ * GAGS_EINVAL before any launch: what gags_project_bwd_cam refuses, a NULL v_K or partials, with KB a NULL v_coeffs, with POSE
+ * a NULL v_viewmat, a short partials_bytes.  n = 0 is GAGS_OK: v_K (v_coeffs with KB, v_viewmat with POSE) is written, zeros. */
+#define GAGS_CALIB_PARTIAL_FLOATS 22
+int64_t gags_project_calib_partials(int n);
+int gags_project_bwd_calib(int camera_model, int flags, int n, const float *means, const float *quats, const float *scales,
+                           const float *opacity_logit, float scaling_modifier, const float *viewmat, const float *K,
+                           int width, int height, float eps2d, const int32_t *radii, const float *v_means2d,
+                           const float *v_depths, const float *v_conics, const float *v_opacities,
+                           const float *v_compensations, float *v_means, float *v_quats, float *v_scales,
+                           float *v_opacity_logit, float *v_viewmat, float *v_K, float *v_coeffs, float *partials,
+                           int64_t partials_bytes, void *stream);
 
 /* The compatibility forms: nothing of their own but the argument list. */
 /* = gags_project_fwd_cam(GAGS_CAM_PINHOLE, 0): opacity_logit, opacities, quats_act, scales_act, grec, compensations NULL,
