@@ -9,6 +9,7 @@ Public surface (mirrors the reference's):
     gags_amd.prompts.depth_point_grids / mindepth_point_grids / prompt_scene   (preprocess.py's and SAM_utils.py's prompt grids)
     gags_amd.tilecut.cut_tiles / level_tiles / embed_levels / language_features   (preprocess.py's CLIP tiles from SAM masks)
     gags_amd.mcmc.MCMCStrategy / relocate / sample_add / inject_noise / regularisation   (gsplat's MCMC density strategy)
+    gags_amd.bilagrid.BilateralGrid / slice / total_variation_loss   (gsplat's bilateral grid; render(..., bilateral_grid=))
 All device work goes through the C-ABI library gags_amd/csrc/libgags_hip.so
 (include/gags_raster.h); there is no CPU or PyTorch fallback -- a missing library raises.
 """

@@ -177,6 +177,14 @@ SIGNATURES = {
                                     _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gags_photometric_bwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
                                     _i64, _i64, _i64, _vp]),
+    # N24: bilateral grid colour correction (csrc/bilagrid.hip): (L, gh, gw, h, w, grid, rgb + 3 strides, ...)
+    "gags_bilagrid_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "gags_bilagrid_slice_fwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "gags_bilagrid_slice_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp,
+                                       _vp, _i64, _vp]),
+    "gags_bilagrid_tv_partials": (_i64, [_i32, _i32, _i32, _i32]),
+    "gags_bilagrid_tv_fwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gags_bilagrid_tv_bwd": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     # N8: adaptive density control (csrc/densify.hip)
     "gags_densify_stats": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
     "gags_densify_decide": (_i32, [_i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),

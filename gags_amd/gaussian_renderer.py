@@ -156,7 +156,8 @@ def _stored_parameters(pc):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True, scaling_modifier=1.0,
-           override_color=None, render_mode="RGB", raster_flags=0, context=None, rasterize_mode="classic", absgrad=False):
+           override_color=None, render_mode="RGB", raster_flags=0, context=None, rasterize_mode="classic", absgrad=False,
+           bilateral_grid=None):
     """Render the scene.  Background tensor (bg_color) must be on GPU!
     raster_flags / context are this package's additions to the reference's signature (kernel selection; the RasterContext
     holding this caller's hooks, capacities and caches -- None = the calling thread's default).
@@ -167,7 +168,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
     absent): a fisheye camera's distortion coefficients (k1 .. k4), resident on the device next to K after the first render.
     A `K` or `radial_coeffs` that is a tensor requiring grad (N23; pose.IntrinsicsDelta.camera makes such cameras) is handed to
     rasterization() as it is -- float32, on the scene's device, [3,3] / [4], else ValueError -- and gets its gradient; no cache
-    entry is made for such a camera."""
+    entry is made for such a camera.
+    bilateral_grid (N24): a bilagrid.BilateralGrid; "render" is then the image corrected by grid `viewpoint_camera.uid` and
+    "render_raw" the uncorrected view (gradients reach the scene through the transform and through the luminance that indexes
+    it).  RGB renders only: feature_mode=True is a ValueError, another render_mode a NotImplementedError, before any launch."""
+    if bilateral_grid is not None:
+        if feature_mode:
+            raise ValueError("render: a bilateral grid corrects colours; feature_mode=True renders features")
+        if render_mode != "RGB":
+            raise NotImplementedError(f"render: a bilateral grid is implemented for render_mode='RGB' only, not {render_mode!r}")
     rctx = context if context is not None else default_context()
     means3D = pc.get_xyz
     radial_coeffs = None
@@ -212,9 +221,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, feature_mode=True
         info["means2d"].retain_grad()  # [1, N, 2]
     except Exception:
         pass
-    return {"render": rendered_image,
-            "viewspace_points": info["means2d"],
-            "visibility_filter": radii > 0,
-            "radii": radii,
-            "alphas": render_alphas[0, ..., 0],
-            "info": info}
+    pkg = {"render": rendered_image,
+           "viewspace_points": info["means2d"],
+           "visibility_filter": radii > 0,
+           "radii": radii,
+           "alphas": render_alphas[0, ..., 0],
+           "info": info}
+    if bilateral_grid is not None:
+        pkg["render_raw"] = rendered_image
+        pkg["render"] = bilateral_grid(rendered_image, int(viewpoint_camera.uid))  # [3,H,W] over [H,W,3] memory, like the raw view
+    return pkg

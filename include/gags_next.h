@@ -747,6 +747,41 @@ int gags_scale_decoder_fwd_fused_head_h16(int64_t n_pix, int c_in, const float *
 int gags_softmax_head_bwd_y_h16(int64_t n_pix, int c, int ld, const float *y, const float *g, void *dz_bf16, void *stream);
 int gags_decoder_query_fused_h16(int64_t n_pix, int c_in, int n_last, const float *x, const void *const *w_bf16, const float *const *bias, const float *phrases, int n_pos, int n_neg, float *probs, void *stream);
 
+/* ---- N24: bilateral grid colour correction (csrc/bilagrid.hip) -------------------------------------------------------------
+ * A grid g [12, L, gh, gw] of floats holds a 3 x 4 colour transform per node: channel 4 r + c is entry (r, c), columns 0..2
+ * multiply (R, G, B), column 3 is the bias.  For pixel (row i, column j) of an h x w image with colour p = (R, G, B):
+ *     x = ((j + 0.5) / w) (gw - 1),  y = ((i + 0.5) / h) (gh - 1),
+ *     gray = 0.299 R + 0.587 G + 0.114 B,  z = clamp(gray, 0, 1) (L - 1),
+ *     A[ch] = sum_{l, m, n} g[ch, l, m, n] tent(z - l) tent(y - m) tent(x - n),   tent(t) = max(0, 1 - |t|),
+ *     out[r] = A[r, 0] R + A[r, 1] G + A[r, 2] B + A[r, 3]
+ * -- torch.nn.functional.grid_sample(mode "bilinear", align_corners = True, padding_mode "border") at (2 x / (gw - 1) - 1,
+ * 2 y / (gh - 1) - 1, 2 gray - 1).  Backward: v_g is the adjoint of the sum;
+ *     v_p[c] = sum_r A[r, c] v_out[r] + m (L - 1) w_c sum_ch (dA[ch] / dz) v_out[r(ch)] (p, 1)[c(ch)],
+ * m = 1 where 0 < gray (L - 1) < L - 1 and 0 otherwise (no gradient through a clamped or boundary coordinate; exact black is
+ * one), d / dz taken in the cell [floor z, floor z + 1]; x and y are constants.
+ * Supported: 2 <= L <= 16, 2 <= gh, gw <= 64, h, w >= 1 with h w <= 2^30; anything else, a NULL pointer or a negative
+ * stride is GAGS_EINVAL before any launch.  rgb and v_out are read through ELEMENT strides (plane, row, column): the
+ * rasterizer's [h, w, 3] memory is (1, 3 w, 3), a contiguous [3, h, w] is (h w, w, 1).  out and v_rgb are [h, w, 3] memory.
+ * Backward: v_rgb and v_grid are each optional (not both NULL).  v_grid [12, L, gh, gw] is computed without atomics and is
+ * bit-reproducible: a workgroup per (xy-node, chunk of the node's rows) gathers its pixels into registers and stores its
+ * sums into one of the scratch's slabs, a second kernel adds the slabs in order; every element is written, nodes no pixel
+ * reaches as 0.  scratch (needed for v_grid only): gags_bilagrid_scratch_bytes(L, gh, gw) bytes, less is GAGS_ESCRATCH. */
+int64_t gags_bilagrid_scratch_bytes(int L, int gh, int gw); /* host only; 0 for a grid the entries reject */
+int gags_bilagrid_slice_fwd(int L, int gh, int gw, int h, int w, const float *grid, const float *rgb, int64_t sp, int64_t sr,
+                            int64_t sc, float *out, void *stream);
+int gags_bilagrid_slice_bwd(int L, int gh, int gw, int h, int w, const float *grid, const float *rgb, int64_t sp, int64_t sr,
+                            int64_t sc, const float *v_out, int64_t v_sp, int64_t v_sr, int64_t v_sc, float *v_rgb,
+                            float *v_grid, void *scratch, int64_t scratch_bytes, void *stream);
+/* Total variation of grids [n_images, 12, L, gh, gw]:
+ *     tv = (2 / n_images) sum_{d in (L, gh, gw)} sum (g[.. d + 1 ..] - g[.. d ..])^2 / n_d,
+ * n_d the number of differences of ONE image along d (12 (L - 1) gh gw for d = L, and so on).  Forward: the differences and
+ * their squares in double, three doubles per workgroup in partials [gags_bilagrid_tv_partials(...), 3], added in a fixed order
+ * by one more workgroup; out [1] float.  Backward: v_grids = v[0] (4 / (n_images n_d)) (second difference), v a DEVICE float.
+ * 1 <= n_images <= 65536. */
+int64_t gags_bilagrid_tv_partials(int n_images, int L, int gh, int gw); /* host only; 0 for sizes the entries reject */
+int gags_bilagrid_tv_fwd(int n_images, int L, int gh, int gw, const float *grids, double *partials, float *out, void *stream);
+int gags_bilagrid_tv_bwd(int n_images, int L, int gh, int gw, const float *grids, const float *v, float *v_grids, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -37,7 +37,11 @@ DEPTH = [(1, 1, 1, 1), (1000, 2, 32, 40), (1000, 3, 32, 40), (1000, 2, 32, 32), 
          (I31, 2, 8, 8)]
 # added after the first file was recorded: function -> (its own fixture under tests/golden, its table)
 # (N22: gags_depthsample_scratch_bytes with a 96-byte camera block where that one has 64 bytes)
-LATER = {"gags_rig_depth_scratch_bytes": ("scratch_bytes_rig_depth.json", DEPTH)}
+# (N24: the slabs of the bilateral grid's v_grid; arguments (L, gh, gw))
+BILAGRID = [(2, 2, 2), (4, 3, 5), (8, 16, 16), (16, 64, 64), (8, 32, 32), (3, 7, 9), (16, 2, 2), (8, 45, 46), (1, 16, 16),
+            (17, 16, 16), (8, 1, 16), (8, 16, 1), (8, 16, 65), (8, 65, 16), (8, 0, 16), (-8, 16, 16)]
+LATER = {"gags_rig_depth_scratch_bytes": ("scratch_bytes_rig_depth.json", DEPTH),
+         "gags_bilagrid_scratch_bytes": ("scratch_bytes_bilagrid.json", BILAGRID)}
 
 
 def table(lib):
